@@ -6,6 +6,8 @@ history), text-like data standing in for enwik8, JSON-like 4 KiB records, plus t
 hot path special-cases (all-equal bytes, short periods, incompressible noise).
 All generators are seeded numpy MT19937 streams, stable across numpy versions and machines.
 """
+import os
+
 import numpy as np
 
 SELFTEST_ALPHABETS = [1, 2, 3, 15, 30, 56, 96, 137, 178, 191, 255, 256]   # tool/zultra.c:534
@@ -348,10 +350,12 @@ def real_text(size):
     return d[:size].copy()
 
 
-BOOTSTRAP_JS = "/opt/conda/lib/python3.9/site-packages/notebook/static/components/bootstrap/dist/js/bootstrap.min.js"
+BOOTSTRAP_JS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "bootstrap_min_js.in.zz")
 
 
 def bootstrap_js():
-    """BASELINE.json configuration 1 stand-in: the image's bootstrap.min.js v3.4.1, 39 680 bytes (the
-    48 944-byte file of the reference's README is not in the image). Raises FileNotFoundError where the image lacks it."""
-    return np.fromfile(BOOTSTRAP_JS, dtype=np.uint8)
+    """BASELINE.json configuration 1 stand-in: bootstrap.min.js v3.4.1 (MIT), 39 680 bytes, stored zlib-packed
+    in tests/golden (the 48 944-byte file of the reference's README is not available)."""
+    import zlib
+    with open(BOOTSTRAP_JS, "rb") as f:
+        return np.frombuffer(zlib.decompress(f.read()), dtype=np.uint8).copy()

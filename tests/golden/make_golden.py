@@ -121,6 +121,9 @@ def main():
 
     with open(os.path.join(HERE, "manifest.json"), "w") as f:
         json.dump(manifest, f, indent=1)
+    # the reference's records of every case of tests/test_oracle_vs_ref.py (ref_answers.json)
+    import test_oracle_vs_ref  # noqa: E402
+    test_oracle_vs_ref.record_reference()
     total = sum(os.path.getsize(os.path.join(HERE, x)) for x in os.listdir(HERE))
     print("total bytes in tests/golden:", total)
 

@@ -347,7 +347,6 @@ inline uint32_t atomicOr(uint32_t *p, uint32_t v) {
    *p = o | v;
    return o;
 }
-inline uint64_t zh_clock() { return 0; }
 inline uint64_t zh_wall_clock() { return 0; }
 inline uint32_t zh_load_agent_u32(const uint32_t *p) { return *p; }
 inline uint32_t zh_load_agent_u16(const uint16_t *p) { return *p; }

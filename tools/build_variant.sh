@@ -1,5 +1,6 @@
 #!/bin/bash
-# Diagnostics: a build of the library with extra compile-time definitions, into build/libzultra_amd_<name>.so (A/B runs: tools/ab_lib.py).
+# Diagnostics: a build of the library with extra compile-time definitions — the #ifndef tunables of the kernel headers (ZH_MF_THREADS, ZH_LP_TASKS, ...)
+# or -DZH_TRACE_LAUNCH — into build/libzultra_amd_<name>.so (A/B runs: tools/ab_lib.py).
 # usage: tools/build_variant.sh <name> [-DX=Y ...]
 set -e
 cd "$(dirname "$0")/.."

@@ -49,6 +49,7 @@ static std::recursive_mutex g_emu_mutex;
 
 #define ZH_MAX_RUNS 8           // staggered runs of a batch (ZULTRA_HIP_STREAMS)
 #define ZH_TOK_SMALL_BATCH 32u  // a batch of at most this many max-blocks follows its token chain in small chunks (zh_split.h)
+#define ZH_LANE_WAVES 12u       // zh_parse_lanes waves per CU that stay next to chains (zh_parse_lanes.h)
 #define ZH_NCNT ((uint32_t)ZH_MAX_RUNS * ZH_CNT_STRIDE)   // device counters: one block of ZH_CNT_* words per run
 
 static_assert(sizeof(zultra_hip_block_t) == sizeof(zh_block_t), "ABI");
@@ -94,10 +95,7 @@ struct zultra_hip_ctx_s {
    bool run_nochains[ZH_MAX_RUNS];       // this batch: run k was enqueued without
    uint32_t streams_respread;   // streams replaced at creation because they shared a hardware queue with a more important one (zh_spread_streams)
    uint32_t grid_cap;           // ZULTRA_HIP_GRID_CAP (tests): the <false> grids of the per-sub-block / per-task kernels are capped here, so that the <true> forms behind them get work
-   uint32_t lane_tasks;         // zh_parse_lanes: tasks per wave when forced (0: chosen per run)
-   uint32_t lane_tasks_last;    // ... of the batch's last run, whose passes are the tail of the step (0: like the others)
-   uint32_t run_share[ZH_MAX_RUNS];   // shares of the runs of a batch in per mille of its max-blocks (run_share[0] == 0: equal shares, see first_run_pct / last_run_pct)
-   uint32_t mf_lds_cap;         // zh_mf_group: chunk size of the refinement in LDS, 0 = through HBM
+   uint32_t mf_lds_cap;         // zh_mf_group: chunk size of the refinement in LDS (at least 16 are taken)
    uint32_t *d_pay;             // zh_mf_group: 3 x sort_stride words per persistent workgroup (payload of the refining sort passes)
    uint32_t *d_longest;         // (round 2: a copy of slot 0 of every match row; no longer written — its readers take the rows)
    uint32_t *d_tok_pos;
@@ -122,21 +120,12 @@ struct zultra_hip_ctx_s {
    uint4 *d_segtasks;           // tasks cut into speculative segments (zh_parse_chain.h): per max-block seg_tasks_per_block entries
    uint2 *d_segitems;           // their segments, as jobs of zh_parse_chain: per max-block seg_items_per_block entries
    uint2 *d_segwaves;           // ... or as segment waves of zh_parse_lanes' launch (four segments each), likewise
-   uint32_t cut_len;            // ... into segments of about this many positions
    uint32_t demote_min;         // a cut task with this many failed cuts in a pass is parsed as one chain in the passes left (ZULTRA_HIP_DEMOTE; 0: never)
-   uint32_t coop_tasks;         // ... a run of at most this many tasks counts as small (ZULTRA_HIP_COOP_TASKS, default: the number of CUs)
    uint32_t coop_small;         // runs of fewer tasks than CUs: tasks with a barrier-free piece longer than this go to the chain kernel (ZULTRA_HIP_COOP_SMALL; ZH_COOP_MIN otherwise)
-   uint32_t cut_min;            // tasks of at least this many positions are cut into segments
    uint32_t seg_whole;          // ... with fewer, zh_parse_chain takes the segments — and the cut tasks shorter than this whole (ZULTRA_HIP_SEG_WHOLE)
    int auto_runs;               // ZULTRA_HIP_STREAMS not set: the number of runs follows the batch size
    int last_runs;               // runs the last batch was cut into
    uint32_t last_run_b0[ZH_MAX_RUNS];   // ... and the first max-block of each (diagnostics: zultra_hip_cut_tasks)
-   uint32_t lane_waves;         // zh_parse_lanes waves per CU that stay next to chains (zh_parse_lanes.h)
-   uint32_t mf_cu_pct;          // share of the CUs the matchfinder kernels' grids cover, percent
-   uint32_t split_waves;        // waves per splitter workgroup, 0 = by max-block size
-   int stagger_ev;              // event of the previous run that a run's matchfinder waits for (0: none)
-   uint32_t last_run_pct;       // share of the last run, likewise
-   uint32_t first_run_pct;      // share of the first run of a batch in percent of an equal share
    uint32_t seg_wide;           // a run with at least this many segments parses them in the segment workgroups of zh_parse_lanes' launch (ZULTRA_HIP_SEG_WIDE)
    int16_t *d_vecs;             // two cost vectors per segment
    uint64_t seg_tasks_per_block, seg_items_per_block;
@@ -164,7 +153,6 @@ struct zultra_hip_ctx_s {
       uint64_t used;   // (tick of the last launch: the older set is the one replaced)
    } rg[2];
    uint64_t rg_tick;
-   uint32_t files_chain_grid;                  // files mode: workgroups of zh_parse_chain per run and pass (ZULTRA_HIP_FILES_CHAIN_GRID; the count of chain tasks is not known to the host: the graph is fixed)
    int files_run_graphs;                       // ZULTRA_HIP_FILES_RUN_GRAPHS (default 1): 0 = several runs are launched kernel by kernel, and large batches stay one run
    uint32_t graph_nblocks;
    int graph_runs;
@@ -576,19 +564,10 @@ extern "C" void zultra_hip_destroy(zultra_hip_ctx_t *c) {
    delete c;
 }
 
-// Environment switches. zh_env: part of the shipped library's surface. zh_knob: tuning experiments — compiled to their defaults
-// unless the library is a probe build (-DZH_TUNING_KNOBS): a process environment cannot move the product off its measured settings.
+// Environment switches: part of the shipped library's surface
 static int zh_env(const char *name, int dflt) {
    const char *e = getenv(name);
    return e ? atoi(e) : dflt;
-}
-static int zh_knob(const char *name, int dflt) {
-#ifdef ZH_TUNING_KNOBS
-   return zh_env(name, dflt);
-#else
-   (void)name;
-   return dflt;
-#endif
 }
 
 #ifndef ZH_EMU
@@ -735,39 +714,6 @@ static int zh_create_buffers(zultra_hip_ctx_t *c) {
       if (c->nlanes < 1) c->nlanes = 1;
       if (c->nlanes > ZH_MAX_RUNS) c->nlanes = ZH_MAX_RUNS;
       c->files_run_graphs = zh_env("ZULTRA_HIP_FILES_RUN_GRAPHS", 1);  // files mode: 0 = several runs are launched kernel by kernel, and large batches stay one run
-      // ---- tuning knobs: read in probe builds only (-DZH_TUNING_KNOBS, tools/build_variant.sh); the shipped library has the defaults compiled in
-      c->cut_len = (uint32_t)zh_knob("ZULTRA_HIP_CUT_LEN", (int)ZH_CUT_LEN);   // positions per segment, about (ZH_CUT_WARM .. ZH_CUT_LEN)
-      if (c->cut_len < ZH_CUT_WARM) c->cut_len = ZH_CUT_WARM;
-      if (c->cut_len > ZH_CUT_LEN) c->cut_len = ZH_CUT_LEN;   // (the buffers are sized for ZH_CUT_WARM, the smallest)
-      c->files_chain_grid = (uint32_t)max(1, min((int)ZH_CHAIN_GRID, zh_knob("ZULTRA_HIP_FILES_CHAIN_GRID", (int)ZH_CHAIN_GRID)));
-      c->coop_tasks = (uint32_t)zh_knob("ZULTRA_HIP_COOP_TASKS", (int)c->num_cus);   // a run of at most this many tasks counts as small
-      c->cut_min = (uint32_t)zh_knob("ZULTRA_HIP_CUT_MIN", (int)ZH_CUT_MIN);         // tasks of at least this many positions are cut (>= 2 * ZH_CUT_WARM)
-      if (c->cut_min < 2u * ZH_CUT_WARM) c->cut_min = 2u * ZH_CUT_WARM;
-      c->split_waves = (uint32_t)zh_knob("ZULTRA_HIP_SPLIT_WAVES", 0);               // waves per splitter workgroup (2, 4, 8, 16; default by max-block size)
-      c->lane_waves = (uint32_t)max(1, min(16, zh_knob("ZULTRA_HIP_LANE_WAVES", 12)));
-      c->lane_tasks = (uint32_t)max(0, min((int)ZH_LP_TASKS, zh_knob("ZULTRA_HIP_LANE_TASKS", 0)));   // tasks per wave of zh_parse_lanes; 0: by the size of the run
-      c->lane_tasks_last = (uint32_t)max(0, min((int)ZH_LP_TASKS, zh_knob("ZULTRA_HIP_LANE_TASKS_LAST", 0)));
-      memset(c->run_share, 0, sizeof(c->run_share));
-#ifdef ZH_TUNING_KNOBS
-      if (const char *rs = getenv("ZULTRA_HIP_RUN_SHARES")) {   // probe builds: "500,300,150,50" — as many runs, of these shares (per mille)
-         int n = 0;
-         while (*rs && n < ZH_MAX_RUNS) {
-            c->run_share[n++] = (uint32_t)atoi(rs);
-            while (*rs && *rs != ',' && *rs != ':') rs++;
-            if (*rs) rs++;
-         }
-         if (n >= 1 && streams == 0) {
-            c->nlanes = n;
-            c->auto_runs = 0;
-         }
-      }
-#endif
-      c->mf_cu_pct = (uint32_t)max(1, min(100, zh_knob("ZULTRA_HIP_MF_CUS", 100)));  // share of the CUs the matchfinder's persistent workgroups take, in percent
-      c->stagger_ev = zh_knob("ZULTRA_HIP_STAGGER", 2);   // which stage of the previous run a run's matchfinder waits for: 0 none, 2 zh_mf_group, 3 zh_mf_frontier, 4 the splitter
-                                                          // (measured, 2 instead of 3: 100 MB of real text 51.9 -> 49.8 ms, configuration 3 31.6 -> 30.5, configuration 4 972 -> 910)
-      if (c->stagger_ev != 0 && (c->stagger_ev < 2 || c->stagger_ev > 4)) c->stagger_ev = 3;
-      c->first_run_pct = (uint32_t)max(10, min(100, zh_knob("ZULTRA_HIP_FIRST_RUN", 100)));   // share of the first run, in percent of an equal share
-      c->last_run_pct = (uint32_t)max(10, min(100, zh_knob("ZULTRA_HIP_LAST_RUN", 100)));     // share of the last run, likewise (three runs and more)
       for (int k = 0; k < c->nlanes; k++) {
          ZH_CHECK(c, hipStreamCreateWithFlags(&c->lane_stream[k], hipStreamNonBlocking));
          for (int i = 0; i < 24; i++) ZH_CHECK(c, hipEventCreate(&c->lane_ev[k][i]));
@@ -800,7 +746,7 @@ static int zh_create_buffers(zultra_hip_ctx_t *c) {
    }
    c->bar_stride = c->tok_stride / 64;
    c->max_tasks = B * (N / ZH_TASK + c->max_subs);
-   // a cut task has at least 2 * ZH_CUT_WARM positions (the floor of ZULTRA_HIP_CUT_MIN) and lies inside one max-block
+   // a cut task has at least 2 * ZH_CUT_WARM positions (the floor of ZH_CUT_MIN) and lies inside one max-block
    c->seg_tasks_per_block = c->files_mode ? 1 : N / (2u * ZH_CUT_WARM) + 1;
    c->seg_items_per_block = c->files_mode ? 1 : N / ZH_CUT_WARM + ZH_CUT_ROWS * (N / (2u * ZH_CUT_WARM) + 1) + 2;   // a task of len positions has at most len / ZH_CUT_LEN + ZH_CUT_ROWS segments
    if (zh_alloc(c, &c->d_bars, B * c->bar_stride) || zh_alloc(c, &c->d_states, B * c->max_subs) || zh_alloc(c, &c->d_taskmap, c->max_tasks) || zh_alloc(c, &c->d_taskinfo, c->max_tasks) ||
@@ -995,9 +941,7 @@ static int zh_build_segments(zultra_hip_ctx_t *c, const zultra_hip_block_t *bloc
 }
 
 // tasks a wave of zh_parse_lanes takes (zh_parse_lanes.h): as many as ZH_LP_TASKS, as few as it takes to fill the chip's wave slots
-static uint32_t zh_tasks_per_wave(const zultra_hip_ctx_t *c, uint32_t ntasks, bool last_run) {
-   if (last_run && c->lane_tasks_last) return c->lane_tasks_last;
-   if (c->lane_tasks) return c->lane_tasks;   // ZULTRA_HIP_LANE_TASKS, read once at context creation
+static uint32_t zh_tasks_per_wave(const zultra_hip_ctx_t *c, uint32_t ntasks) {
    const uint32_t slots = c->total_cus * 8u;   // (measured: eight tasks per wave at 16 K tasks per run beat four by 2 % of the step)
    return max(1u, min((uint32_t)ZH_LP_TASKS, (ntasks + slots - 1) / slots));
 }
@@ -1078,7 +1022,7 @@ static int zh_enqueue_run(zultra_hip_ctx_t *c, int k, uint32_t b0, uint32_t nb, 
    uint16_t *cost = c->d_cost + (uint64_t)b0 * c->best_stride;
    const uint64_t *bars = c->d_bars + (uint64_t)b0 * c->bar_stride;
    const zh_match_t *match = c->d_match + (uint64_t)b0 * c->match_stride;
-   const uint32_t mf_grid = min(nsg, max(1u, c->num_cus * c->mf_cu_pct / 100u));   // persistent workgroups, one per CU (zh_matchfinder.h)
+   const uint32_t mf_grid = min(nsg, c->num_cus);   // persistent workgroups, one per CU (zh_matchfinder.h)
    // grids: bounded by what the input bytes allow, sized for what data usually gives; the kernels stride
    const uint32_t est_tasks = (uint32_t)zh_min64(cap, total_n / ZH_TASK + 2ull * nb);                                   // tasks: ~ bytes / 2048 + one per sub-block
    uint32_t task_grid = cap <= 2048u ? cap : (uint32_t)zh_min64(cap, total_n / ZH_TASK + 4ull * nb);               // one wave per task (zh_list_huge, zh_post_tasks, zh_emit_tasks)
@@ -1102,7 +1046,7 @@ static int zh_enqueue_run(zultra_hip_ctx_t *c, int k, uint32_t b0, uint32_t nb, 
    }
    const uint64_t seg_bound = (uint64_t)nb * c->seg_items_per_block;                     // entries of segwaves (zh_list_huge)
    if (part != 2) {
-      ZH_LAUNCH_LDS(zh_mf_group<true>, mf_grid, ZH_MF_THREADS, ZH_MF_GROUP_LDS, st, c->cur_data, sgs, sa, sb, p3, rn, c->sort_stride, c->run_stride, 0, nsg, ctr + (size_t)nsg * 2 + 1, pay,
+      ZH_LAUNCH_LDS(zh_mf_group<true>, mf_grid, ZH_MF_THREADS, ZH_MF_GROUP_LDS, st, c->cur_data, sgs, sa, sb, p3, rn, c->sort_stride, c->run_stride, nsg, ctr + (size_t)nsg * 2 + 1, pay,
                     c->mf_lds_cap);
       // the bigram classes that fit no chunk of zh_mf_group, noted by it (zh_mf_group_lds.h): a kernel of their own (inputs of <= 4 KiB are one chunk: nothing is ever noted)
       if (c->mf_lds_cap && c->seg_W > (files ? (uint32_t)ZH_MFL_MAXCAP : min((uint32_t)ZH_MFL_MAXCAP, max(c->mf_lds_cap, 16u))))
@@ -1114,7 +1058,7 @@ static int zh_enqueue_run(zultra_hip_ctx_t *c, int k, uint32_t b0, uint32_t nb, 
    // (segment descriptors carry batch-wide block indices: the rows go to d_match + block * match_stride)
    // a run of fewer segments than CUs (one call on a few max-blocks: latency): the workgroups beyond one per segment find the tickets gone and help —
    // a segment of a 64 KiB max-block is ~1500 chunks, shared while a helper's share stays above ZH_MF_HELP_MIN of them (small inputs: nothing worth sharing)
-   const uint32_t fr_grid = files ? mf_grid : min(max(1u, c->num_cus * c->mf_cu_pct / 100u), mf_grid * 8u);
+   const uint32_t fr_grid = files ? mf_grid : min(c->num_cus, mf_grid * 8u);
    ZH_LAUNCH_LDS(zh_mf_frontier<true>, fr_grid, ZH_MF_THREADS, ZH_MF_FRONTIER_LDS, st, c->cur_data, sgs, (const uint32_t *)sa, (const uint2 *)p3, (const uint32_t *)rn, c->sort_stride,
                  c->run_stride, c->d_match, c->match_stride, c->d_longest, c->tok_stride, ctr, nsg, files ? 0u : 1u);
    if (!files) ZH_CHECK(c, hipEventRecord(ev[3], st));   // (timing marks)
@@ -1125,7 +1069,7 @@ static int zh_enqueue_run(zultra_hip_ctx_t *c, int k, uint32_t b0, uint32_t nb, 
 #define ZH_LAUNCH_SPLIT(W_)                                                                                                                                   \
    ZH_LAUNCH(zh_split<W_>, nb, 64 * W_, st, blk, (const uint32_t *)(c->d_tok_pos + b0 * c->tok_stride), (const uint16_t *)(c->d_tok_info + b0 * c->tok_stride), \
              c->tok_stride, (const uint32_t *)(c->d_ntok + b0), c->d_split_tok + (uint64_t)b0 * (ZH_MAX_SPLITS + 1), c->d_split_cnt + b0)
-      const uint32_t sw = c->split_waves ? c->split_waves : (max_n > 131072 ? 16u : 8u);   // (by the run's largest max-block, not the context's limit)
+      const uint32_t sw = max_n > 131072 ? 16u : 8u;   // (by the run's largest max-block, not the context's limit)
       if (sw >= 16)
          ZH_LAUNCH_SPLIT(16);
       else if (sw >= 8)
@@ -1150,19 +1094,19 @@ static int zh_enqueue_run(zultra_hip_ctx_t *c, int k, uint32_t b0, uint32_t nb, 
       ZH_LAUNCH_PLAN(256u);
 #undef ZH_LAUNCH_PLAN
    ZH_LAUNCH_BOTH(zh_sb_init, sb_grid, sb_bound, st, (const uint16_t *)(c->d_tok_info + (uint64_t)b0 * c->tok_stride), c->tok_stride, (const zh_work_t *)work, states, (const uint32_t *)cnt);
-   // (inputs of a files batch are never cut into speculative segments: seg_min = all ones; a run of at most coop_tasks tasks counts as small)
+   // (inputs of a files batch are never cut into speculative segments: seg_min = all ones; a run of at most as many tasks as CUs counts as small)
    ZH_LAUNCH_BOTH(zh_list_huge, task_grid, cap, st, blk, bars, c->bar_stride, (const zh_work_t *)work, (const uint2 *)taskmap, (const uint32_t *)(c->d_match + (uint64_t)b0 * c->match_stride),
-             c->match_stride, hugelist, cap, segtasks, segitems, segwaves, files ? 0xFFFFFFFFu : c->cut_min, files ? (uint32_t)ZH_CUT_LEN : c->cut_len, cnt, taskinfo, (uint32_t)ZH_COOP_MIN,
-             files ? (uint32_t)ZH_COOP_MIN : c->coop_small, files ? 0u : c->coop_tasks);
+             c->match_stride, hugelist, cap, segtasks, segitems, segwaves, files ? 0xFFFFFFFFu : (uint32_t)ZH_CUT_MIN, (uint32_t)ZH_CUT_LEN, cnt, taskinfo, (uint32_t)ZH_COOP_MIN,
+             files ? (uint32_t)ZH_COOP_MIN : c->coop_small, files ? 0u : c->num_cus);
    if (!files) ZH_CHECK(c, hipEventRecord(ev[5], st));   // (timing marks)
    // Persistent workgroups of zh_parse_chain take the listed chains from a ticket (none listed: they leave at once); zh_parse_lanes takes the task
-   // list in groups, as a grid that fills the chip's wave slots — next to chains only `lane_waves` per CU stay, so that the chain workgroups find
+   // list in groups, as a grid that fills the chip's wave slots — next to chains only ZH_LANE_WAVES per CU stay, so that the chain workgroups find
    // room the moment they are launched (the run's counters tell the kernel which); the first workgroups of zh_parse_lanes' grid take the cut tasks' segments when there are many.
-   const uint32_t tpw = zh_tasks_per_wave(c, est_tasks, !files && c->last_runs > 1 && k == c->last_runs - 1);
+   const uint32_t tpw = zh_tasks_per_wave(c, est_tasks);
    const uint32_t lane_grid = max(1u, min((est_tasks + tpw - 1) / tpw, c->num_cus * 16u));
    // (two chain workgroups fit a CU — 169 registers, four waves — and they are persistent: a third per CU would only queue behind them, find the tickets
    // gone and leave; and in a run without chains every workgroup of this grid has to find a slot among the quad kernel's waves before the pass can end)
-   uint32_t chain_grid = files ? min(nb, c->files_chain_grid) : (uint32_t)zh_min64(zh_min64(ZH_CHAIN_GRID, 2u * c->num_cus), total_n / 256u + nb);
+   uint32_t chain_grid = files ? min(nb, (uint32_t)ZH_CHAIN_GRID) : (uint32_t)zh_min64(zh_min64(ZH_CHAIN_GRID, 2u * c->num_cus), total_n / 256u + nb);
    // A stream without chains must not pay for them (round 6; zh_parse.h, zh_run_is_void): a run whose counterpart in the context's last batch listed nothing for
    // zh_parse_chain gets no chain kernel at all — no fork, no grid to schedule among the quad kernels' waves, no join — and a mark in its counters that says so.
    const bool chains_idle = !files && c->run_nochains[k];
@@ -1198,7 +1142,7 @@ static int zh_enqueue_run(zultra_hip_ctx_t *c, int k, uint32_t b0, uint32_t nb, 
          sg.seg_grid = files ? 0u : seg_grid;
          ZH_LAUNCH(zh_parse_lanes, sg.seg_grid + lane_grid, 64, st, c->cur_data, blk, match, c->match_stride, bars, c->bar_stride, (const zh_work_t *)work, (const uint2 *)taskmap, cnt,
                    (const zh_sbstate_t *)states, best, c->best_stride, cost, hist_part, pass, cnt + ZH_CNT_TASK_TICKET + pass, (const uint2 *)taskinfo, tpw,
-                   files ? 0xFFFFFFFFu : c->num_cus * c->lane_waves, sg);
+                   files ? 0xFFFFFFFFu : c->num_cus * ZH_LANE_WAVES, sg);
       }
       if (!chains_idle) ZH_CHECK(c, hipStreamWaitEvent(st, c->side_ev[k][2 * pass + 1], 0));
       if (!files) ZH_CHECK(c, hipEventRecord(ev[6 + 2 * pass], st));   // (timing marks)
@@ -1276,7 +1220,7 @@ static int zh_enqueue_files(zultra_hip_ctx_t *c, uint32_t nblocks, hipStream_t s
       hipStream_t st = k ? c->lane_stream[k] : st0;
       if (k) {
          ZH_CHECK(c, hipStreamWaitEvent(st, c->ev2[1], 0));
-         if (c->stagger_ev) ZH_CHECK(c, hipStreamWaitEvent(st, c->lane_ev[k - 1][2], 0));
+         ZH_CHECK(c, hipStreamWaitEvent(st, c->lane_ev[k - 1][2], 0));
       }
       const uint32_t b0 = zh_files_run_lo(c, nblocks, k), b1 = zh_files_run_lo(c, nblocks, k + 1);
       if (zh_enqueue_run(c, k, b0, b1 - b0, (uint64_t)(b1 - b0) * c->max_block, c->max_block, b0, b1 - b0, st, c->side_stream[k], 0) != 0) return -1;
@@ -1345,7 +1289,7 @@ static int zh_run_files(zultra_hip_ctx_t *c, uint32_t nblocks) {
          hipStream_t sk = c->lane_stream[k];
          if (k) {
             ZH_CHECK(c, hipStreamWaitEvent(sk, c->ev2[1], 0));
-            if (c->stagger_ev) ZH_CHECK(c, hipStreamWaitEvent(sk, c->lane_ev[k - 1][2], 0));   // behind the previous run's first matchfinder kernel
+            ZH_CHECK(c, hipStreamWaitEvent(sk, c->lane_ev[k - 1][2], 0));   // behind the previous run's first matchfinder kernel
          }
          ZH_CHECK(c, hipGraphLaunch(G->exec[2 * k], sk));
          ZH_CHECK(c, hipEventRecord(c->lane_ev[k][2], sk));
@@ -1439,26 +1383,15 @@ extern "C" int zultra_hip_compress_blocks(zultra_hip_ctx_t *c, const void *data,
    for (uint32_t b = 0; b < nblocks; b++) batch_bytes += blocks[b].n;
    const uint64_t want_runs = c->auto_runs ? (batch_bytes >= (256ull << 20) ? 4u : 3u) : (uint64_t)c->nlanes;
    const int lanes = c->last_runs = (int)zh_max64(1, zh_min64(want_runs, zh_min64((uint64_t)nblocks / 4u, batch_bytes >> 22)));   // at least four max-blocks and 4 MiB per run
-   // run k = blocks [run_lo(k), run_lo(k + 1)): the first run may be given a smaller share (c->first_run_pct of an equal share), so that the
-   // other runs' matchfinders start earlier
+   // run k = blocks [run_lo(k), run_lo(k + 1)): the first and the last run get nblocks / lanes max-blocks each (at least four: lanes <= nblocks / 4),
+   // the runs between them split the rest
    auto run_lo = [&](int k) -> uint32_t {
       if (k <= 0) return 0u;
       if (k >= lanes) return nblocks;
-      if (c->run_share[0]) {   // explicit shares (set for `lanes` runs); a run is never empty
-         uint64_t acc = 0, tot = 0;
-         for (int j = 0; j < lanes; j++) tot += c->run_share[j] ? c->run_share[j] : 1u;
-         for (int j = 0; j < k; j++) acc += c->run_share[j] ? c->run_share[j] : 1u;
-         const uint64_t lo = (uint64_t)nblocks * acc / tot;
-         return (uint32_t)zh_min64(zh_max64(lo, (uint64_t)k), (uint64_t)nblocks - (uint64_t)(lanes - k));
-      }
-      // (a run is never empty: with ZULTRA_HIP_FIRST_RUN / _LAST_RUN below 25 and four max-blocks per run the shares rounded to 0, and a
-      // zero-sized grid fails the batch)
-      const uint64_t first = zh_max64(1, (uint64_t)nblocks * c->first_run_pct / (100ull * (uint64_t)lanes));
-      if (lanes < 3) return (uint32_t)(first + ((uint64_t)nblocks - first) * (uint64_t)(k - 1) / (uint64_t)(lanes - 1));
-      const uint64_t last = zh_max64(1, (uint64_t)nblocks * c->last_run_pct / (100ull * (uint64_t)lanes));   // likewise the last run: its passes are the tail of the batch
-      const uint64_t mid = (uint64_t)nblocks - first - last;
-      if (k == lanes - 1) return (uint32_t)(nblocks - last);
-      return (uint32_t)(first + mid * (uint64_t)(k - 1) / (uint64_t)(lanes - 2));
+      const uint32_t share = nblocks / (uint32_t)lanes;
+      if (k == 1) return share;
+      if (k == lanes - 1) return nblocks - share;
+      return share + (uint32_t)((uint64_t)(nblocks - 2u * share) * (uint64_t)(k - 1) / (uint64_t)(lanes - 2));
    };
    hipStream_t st0 = c->lane_stream[0];
    bool any_nochains = false;
@@ -1517,7 +1450,7 @@ extern "C" int zultra_hip_compress_blocks(zultra_hip_ctx_t *c, const void *data,
          ZH_CHECK(c, hipStreamWaitEvent(st, c->ev_input, 0));
          // stagger the runs by one stage: this run's wide matchfinder kernels start when the previous run reaches its
          // narrow ones (token chain, splitter), so narrow and wide kernels of different runs share the chip
-         if (c->stagger_ev) ZH_CHECK(c, hipStreamWaitEvent(st, c->lane_ev[k - 1][c->stagger_ev], 0));
+         ZH_CHECK(c, hipStreamWaitEvent(st, c->lane_ev[k - 1][2], 0));
       }
       uint64_t total_n = 0;
       uint32_t max_n = 0;
@@ -1856,49 +1789,6 @@ extern "C" int zultra_hip_cut_tasks(zultra_hip_ctx_t *c, uint32_t run, uint32_t 
    if (out && n) ZH_CHECK(c, hipMemcpy(out, c->d_segtasks + (uint64_t)c->last_run_b0[run] * c->seg_tasks_per_block, (size_t)n * sizeof(uint4), hipMemcpyDeviceToHost));
    return (int)n;
 }
-
-#ifdef ZH_MF_PROFILE
-extern "C" int zultra_hip_mf_profile(unsigned long long *out, int reset) {
-   if (out && hipMemcpyFromSymbol(out, HIP_SYMBOL(zh_mf_prof), sizeof(zh_mf_prof)) != hipSuccess) return -1;
-   if (reset) {
-      unsigned long long z[16] = {0};
-      if (hipMemcpyToSymbol(HIP_SYMBOL(zh_mf_prof), z, sizeof(z)) != hipSuccess) return -1;
-   }
-   return 0;
-}
-#endif
-
-#ifdef ZH_MFG_PROFILE
-extern "C" int zultra_hip_mfg_profile(unsigned long long *out, int reset) {
-   if (out && hipMemcpyFromSymbol(out, HIP_SYMBOL(zh_mfg_prof), sizeof(zh_mfg_prof)) != hipSuccess) return -1;
-   if (reset) {
-      unsigned long long z[32] = {0};
-      if (hipMemcpyToSymbol(HIP_SYMBOL(zh_mfg_prof), z, sizeof(z)) != hipSuccess) return -1;
-   }
-   return 0;
-}
-#endif
-
-#ifdef ZH_LP_PROFILE
-extern "C" int zultra_hip_lp_profile(unsigned long long *out, int reset) {
-   if (out && hipMemcpyFromSymbol(out, HIP_SYMBOL(zh_lp_prof), sizeof(zh_lp_prof)) != hipSuccess) return -1;
-   if (reset) {
-      unsigned long long z[16] = {0};
-      if (hipMemcpyToSymbol(HIP_SYMBOL(zh_lp_prof), z, sizeof(z)) != hipSuccess) return -1;
-   }
-   return 0;
-}
-#endif
-
-#ifdef ZH_LP_TRACE
-extern "C" int zultra_hip_lp_trace(unsigned long long *out /* 4 passes x ZH_LP_TRACE_SLOTS x 4 */, unsigned int *slots) {
-   if (slots) *slots = ZH_LP_TRACE_SLOTS;
-   if (out && hipMemcpyFromSymbol(out, HIP_SYMBOL(zh_lp_trace), sizeof(zh_lp_trace)) != hipSuccess) return -1;
-   static unsigned long long z[4u * ZH_LP_TRACE_SLOTS * 4u];
-   if (out && hipMemcpyToSymbol(HIP_SYMBOL(zh_lp_trace), z, sizeof(z)) != hipSuccess) return -1;
-   return 0;
-}
-#endif
 
 extern "C" void zultra_hip_last_stats(const zultra_hip_ctx_t *c, zultra_hip_stats_t *out) {
    if (!c || !out) return;

@@ -16,11 +16,13 @@
 //     table of the window's runs (see "byte runs" below): the class "cccccc" is never walked.
 // The orders are built with exact stable counting passes, digits = bytes:
 //   zh_mf_group    persistent workgroups, one segment (zh_common.h) at a time.
-//                  trigram order (3 passes)      -> prev.x = previous occurrence of the same trigram;
-//                  + one pass on byte 3          -> 4-gram classes, contiguous and ascending in position -> prev4
-//                  + one pass on byte 4          -> 5-gram classes -> prev5
+//                  bigram order (2 passes)       -> then, chunk by chunk in LDS (zh_mf_group_lds.h):
+//                  + one pass on byte 2          -> trigram classes
+//                  + one pass on byte 3          -> 4-gram classes, contiguous and ascending in position -> prev3
+//                  + one pass on byte 4          -> 5-gram classes -> prev4
 //                  + one pass on byte 5          -> 6-gram order with class heads marked: candidate lists are contiguous
-//                                                   memory, no pointer chasing (hash chains would serialise on latency).
+//                                                   memory, no pointer chasing (hash chains would serialise on latency)
+//                                                   -> prev5.
 //                  Every pass gathers its digit from the window copy in LDS.
 //   zh_mf_frontier waves pull 64-entry chunks of the 6-gram order from a counter in HBM (any number of workgroups can
 //                  serve one segment: finished workgroups help unfinished segments). Neighbouring entries belong to the
@@ -29,8 +31,8 @@
 //                  the lanes with one DPP wave shift per step and refilled from one coalesced 64-entry load per 64
 //                  steps; the window sits in LDS.
 //
-// HBM traffic per segment: window read twice linearly, 6 x 2 x 4 B per window position for the sort ping-pong,
-// 8 B per position for the prev records, 32 B per block position for the rows.
+// HBM traffic per segment: window read twice linearly, 28 B per window position for the orders and the prev records
+// (zh_mf_group_lds.h), 32 B per block position for the rows.
 #pragma once
 #include <zh_platform.h>
 #include "zh_common.h"
@@ -87,13 +89,13 @@ __device__ inline void zh_stage_window(uint32_t *lwin32, const uint8_t *gwin, ui
 // ---------------------------------------------------------------------------------------------------------
 // One stable counting pass over M elements: wave w owns the contiguous slice [w*seg, (w+1)*seg), so element order
 // within a digit is preserved. hist = ZH_MF_WAVES x 256 counters in LDS.
-// MODE 0/1/2: the trigram's bytes 2/1/0 are the digits (exact order, three passes, elements are positions);
+// MODE 2: the byte at the element (a position) is the digit (the run starts by byte value, zh_mf_build_runs);
 // MODE 5/6/7: byte 3/4/5 of the string at the position: a stable pass over the k-gram order gives the (k+1)-gram classes,
 // contiguous and ascending in position (the classes come out ordered by their last byte first, which nobody minds).
-// Mode 0 reads the identity permutation and the window linearly (win); the others gather through gwin.
+// Every mode gathers its digit through gwin.
 // HAVE: hist already holds this pass's per-(wave, digit) counts — the previous pass counted them while it scattered
 // (its outputs are this pass's inputs), which saves this pass one read of its input and one digit gather per element.
-// NEXT >= 0: count the digits of pass mode NEXT into hist_next the same way (M_next = number of elements this pass writes).
+// NEXT = 11: count the digits of the mode-11 pass that follows into hist_next the same way (M_next = number of elements this pass writes).
 __device__ __forceinline__ uint32_t zh_mf_slice(uint32_t M) { return (((M + ZH_MF_WAVES - 1) / ZH_MF_WAVES) + 63) & ~63u; }
 
 // MODE 4: byte 2 likewise (a class of the bigram order that is refined through HBM, zh_mf_group_lds.h). MODE 10/11: the bigram order —
@@ -106,7 +108,7 @@ __device__ __forceinline__ uint32_t zh_mf_slice(uint32_t M) { return (((M + ZH_M
 // class. Recorded as distance - 1 in 16 bits (0xffff: none within ZH_MAX_DIST) and sent along as payload: K = 3: d3 | none << 16 ->
 // pdst; K = 4: d3 (read from psrc) | d4 << 16 -> pdst; K = 5: (psrc value, d5) -> pdst2. So the three distances of a position arrive
 // next to its entry of the 6-gram order, where zh_mf_frontier reads them with the entries, coalesced. (Round 1 scattered them into
-// a table indexed by position: 8.1 GB of HBM writes per 50 MB. Round 2 took them in a pass of their own over each order, zh_mf_prev_level:
+// a table indexed by position: 8.1 GB of HBM writes per 50 MB. Round 2 took them in a pass of their own over each order:
 // one more read of the order and one more write of the payload per level — 0.7 of this kernel's 4 ms per 50 MB and a quarter of its
 // HBM traffic.) The last five window positions drop out of the orders before they reach the 6-gram order: theirs go to tail[pos]
 // (the frontier's position-indexed table: entries from W - 5 on are free, the 6-gram order has at most W - 5 entries).
@@ -137,7 +139,7 @@ __device__ __forceinline__ bool zh_mf_prev_is_neighbour(const uint8_t *g, uint32
 }
 
 template <int MODE, bool HAVE = false, int NEXT = -1, int PAY = 0, int PREV = 0>
-__device__ inline void zh_mf_sort_pass(const uint8_t *win, const uint8_t *gwin, uint32_t M, const uint32_t *src, uint32_t *dst, uint32_t *hist,
+__device__ inline void zh_mf_sort_pass(const uint8_t *gwin, uint32_t M, const uint32_t *src, uint32_t *dst, uint32_t *hist,
                                        uint32_t *wave_tot, uint32_t W = 0, uint32_t *hist_next = nullptr, uint32_t M_next = 0,
                                        const uint32_t *aux_rs = nullptr, const uint32_t *aux_rl = nullptr, const uint32_t *psrc = nullptr,
                                        uint32_t *pdst = nullptr, const uint32_t *qsrc = nullptr, uint2 *pdst2 = nullptr, uint2 *tail = nullptr) {
@@ -148,6 +150,7 @@ __device__ inline void zh_mf_sort_pass(const uint8_t *win, const uint8_t *gwin, 
    const uint32_t hi = min(M, lo + seg);
    const uint64_t lt_mask = (1ull << lane) - 1;
    (void)M_next;
+   static_assert(NEXT == -1 || NEXT == 11, "only mode 11 is counted ahead");
 
    if (!HAVE)
       for (uint32_t k = tid; k < ZH_MF_WAVES * 256; k += ZH_MF_THREADS) hist[k] = 0;
@@ -158,13 +161,9 @@ __device__ inline void zh_mf_sort_pass(const uint8_t *win, const uint8_t *gwin, 
    // element and digit of slice index idx
 #define ZH_MF_FETCH(idx, e, d)                                                                      \
    do {                                                                                             \
-      if (MODE == 0) {                                                                              \
-         e = (idx);                                                                                 \
-         d = win[(idx) + 2];                                                                        \
-      }                                                                                             \
-      else if (MODE == 1 || MODE == 2) {                                                            \
+      if (MODE == 2) {                                                                              \
          e = src[idx];                                                                              \
-         d = gwin[e + (MODE == 1 ? 1 : 0)];                                                         \
+         d = gwin[e];                                                                               \
       }                                                                                             \
       else if (MODE == 8) {                                                                         \
          e = src ? src[idx] : (idx);                                                                \
@@ -192,9 +191,7 @@ __device__ inline void zh_mf_sort_pass(const uint8_t *win, const uint8_t *gwin, 
    // the same in two steps: the element (a load from HBM/L2 — issued a tile ahead), then its digit (LDS, or small tables)
 #define ZH_MF_FETCH_E(idx, e)                                             \
    do {                                                                   \
-      if (MODE == 0)                                                      \
-         e = (idx);                                                       \
-      else if (MODE == 10)                                                \
+      if (MODE == 10)                                                     \
          e = (idx) | ((uint32_t)gwin[idx] << 24);                         \
       else if (MODE == 8)                                                 \
          e = src ? src[idx] : (idx);                                      \
@@ -203,10 +200,8 @@ __device__ inline void zh_mf_sort_pass(const uint8_t *win, const uint8_t *gwin, 
    } while (0)
 #define ZH_MF_FETCH_D(idx, e, d)                                                                    \
    do {                                                                                             \
-      if (MODE == 0)                                                                                \
-         d = win[(idx) + 2];                                                                        \
-      else if (MODE == 1 || MODE == 2)                                                              \
-         d = gwin[e + (MODE == 1 ? 1 : 0)];                                                         \
+      if (MODE == 2)                                                                                \
+         d = gwin[e];                                                                               \
       else if (MODE == 8) {                                                                         \
          const uint32_t after_ = aux_rs[e] + aux_rl[e];                                             \
          d = after_ < W ? (uint32_t)gwin[after_] : 0u;                                              \
@@ -365,14 +360,8 @@ __device__ inline void zh_mf_sort_pass(const uint8_t *win, const uint8_t *gwin, 
             dst[out] = MODE == 11 ? (e & 0xffffffu) : e;
             if (PAY == 1) pdst[out] = p4[u];
             if (PAY == 2) pdst2[out] = make_uint2(p4[u], q4[u]);
-            if (NEXT >= 0) {
-               // the next pass's digit of this element (which wave counts it does not matter: the next pass adds them up)
-               const bool has = NEXT < 5 || NEXT == 11 || e + (uint32_t)(NEXT - 2) < W;
-               if (has) {
-                  const uint32_t d2 = NEXT == 11 ? e >> 24 : (uint32_t)gwin[(e & 0xffffffu) + (NEXT == 1 ? 1u : (NEXT == 2 ? 0u : (uint32_t)(NEXT - 2)))];
-                  atomicAdd(&hist_next[wave * 256 + d2], 1u);
-               }
-            }
+            // the next pass's digit of this element, byte 0 (which wave counts it does not matter: the next pass adds them up)
+            if (NEXT == 11) atomicAdd(&hist_next[wave * 256 + (e >> 24)], 1u);
          }
       }
       zh_lockstep_sync();   // (the next tile zeroes this wave's counters: after these reads)
@@ -408,21 +397,7 @@ __device__ __forceinline__ uint32_t zh_run_length(const uint8_t *g, uint32_t q, 
    return l;
 }
 
-#ifdef ZH_MFG_PROFILE
-// probe builds only (tools/mfg_profile.py): cycles of thread 0 of every workgroup by phase — 0 window staging and ticket, 1 the two passes through
-// HBM, 2 chunk load and boundary, 3 the four passes of a chunk, 4 its sweep, 5 oversized classes, 6 run starts, 7 first run order,
-// 8 run lengths, 9 second run order, 10 its table; counts — 12 chunks, 13 oversized classes, 14 their entries, 15 segments
-__device__ unsigned long long zh_mfg_prof[32];   // 16..23: inside a pass of a chunk — counting, wait, totals, wait, scan and places, wait, scatter, wait
-#define ZH_MFG_LAP(slot_) do { if (threadIdx.x == 0) { const uint64_t n_ = zh_clock(); atomicAdd(&zh_mfg_prof[slot_], (unsigned long long)(n_ - mfg_t_)); mfg_t_ = n_; } } while (0)
-#define ZH_MFG_COUNT(slot_, n_) do { if (threadIdx.x == 0) atomicAdd(&zh_mfg_prof[slot_], (unsigned long long)(n_)); } while (0)
-#define ZH_MFG_TIC() mfg_t_ = zh_clock()
-#else
-#define ZH_MFG_LAP(slot_)
-#define ZH_MFG_COUNT(slot_, n_)
-#define ZH_MFG_TIC()
-#endif
-
-__device__ inline void zh_mf_build_runs(const uint8_t *win, const uint8_t *gwin, uint32_t W, uint32_t Qn, uint32_t *T, uint32_t *runs, uint32_t *hist, uint32_t *wave_tot, uint64_t &mfg_t_) {
+__device__ inline void zh_mf_build_runs(const uint8_t *gwin, uint32_t W, uint32_t Qn, uint32_t *T, uint32_t *runs, uint32_t *hist, uint32_t *wave_tot) {
    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
    const uint32_t Q = zh_runs_q(W);
    uint32_t *RS = runs, *RL = runs + Q, *first = runs + 2 * Q, *end = first + 256, *count = end + 256;
@@ -453,9 +428,7 @@ __device__ inline void zh_mf_build_runs(const uint8_t *win, const uint8_t *gwin,
 #undef ZH_IS_RUN_START
    __threadfence_block();
    __syncthreads();
-   ZH_MFG_LAP(6);
-   zh_mf_sort_pass<2>(win, gwin, total, T, RS, hist, wave_tot);   // stable by byte value: digit = gwin[start]
-   ZH_MFG_LAP(7);
+   zh_mf_sort_pass<2>(gwin, total, T, RS, hist, wave_tot);   // stable by byte value: digit = gwin[start]
    for (uint32_t idx = tid; idx < total; idx += ZH_MF_THREADS) {
       const uint32_t q = RS[idx];
       const uint32_t c = gwin[q];
@@ -473,10 +446,8 @@ __device__ inline void zh_mf_build_runs(const uint8_t *win, const uint8_t *gwin,
    uint32_t *Pa = T + Q, *Pb = T + 2 * Q;
    __threadfence_block();
    __syncthreads();
-   ZH_MFG_LAP(8);
-   zh_mf_sort_pass<8>(win, gwin, total, nullptr, Pa, hist, wave_tot, W, nullptr, 0, RS, RL);
-   zh_mf_sort_pass<9>(win, gwin, total, Pa, Pb, hist, wave_tot, W, nullptr, 0, RS, RL);
-   ZH_MFG_LAP(9);
+   zh_mf_sort_pass<8>(gwin, total, nullptr, Pa, hist, wave_tot, W, nullptr, 0, RS, RL);
+   zh_mf_sort_pass<9>(gwin, total, Pa, Pb, hist, wave_tot, W, nullptr, 0, RS, RL);
    for (uint32_t idx = tid; idx < total; idx += ZH_MF_THREADS) {
       const uint32_t e = Pb[idx];
       const uint32_t st = RS[e], ln = RL[e];
@@ -484,112 +455,6 @@ __device__ inline void zh_mf_build_runs(const uint8_t *win, const uint8_t *gwin,
       RS2[idx] = st | (x << 24);
       RL2[idx] = ln;
    }
-   ZH_MFG_LAP(10);
-}
-
-// The nearest earlier position sharing K bytes (K = 3, 4, 5) with the position at entry idx of the K-gram order X (MK entries) is
-// the entry before it, when that one is in the same class (classes ascend in position). Recorded as distance - 1 in 16 bits
-// (0xffff: none within ZH_MAX_DIST) IN THE ORDER OF X, and carried along by the passes that refine the order (zh_mf_sort_pass,
-// PAY): in the end the three distances of a position sit next to its entry of the 6-gram order, where zh_mf_frontier reads them
-// with the entries, coalesced. (Round 1 scattered them into a table indexed by position: three partial writes per position,
-// to lines that had long left the L2 — 8.1 GB of HBM writes per 50 MB of input, most of this kernel's time.)
-//   K = 3: pay[idx] = d3 | none << 16        K = 4: pay[idx] = d3 (as carried) | d4 << 16        K = 5: pay[idx] = d5
-// The last five window positions drop out of the orders before they reach the 6-gram order: theirs go to tail[pos] (the
-// frontier's position-indexed table: entries from W - 5 on are free, the 6-gram order has at most W - 5 entries).
-template <int K>
-__device__ inline void zh_mf_prev_level(const uint32_t *__restrict__ X, uint32_t MK, const uint8_t *gwin, uint32_t W, uint32_t *pay, uint2 *tail) {
-   for (uint32_t idx0 = threadIdx.x; idx0 < MK; idx0 += 4 * ZH_MF_THREADS) {
-      uint32_t pos[4], q[4], old[4] = {0, 0, 0, 0};
-#pragma unroll
-      for (uint32_t u = 0; u < 4; u++) {
-         const uint32_t idx = idx0 + u * ZH_MF_THREADS;
-         pos[u] = idx < MK ? X[idx] : 0u;
-         q[u] = (idx < MK && idx > 0) ? X[idx - 1] : ZH_MF_NONE;
-         if (K == 4 && idx < MK) old[u] = pay[idx];
-      }
-#pragma unroll
-      for (uint32_t u = 0; u < 4; u++) {
-         const uint32_t idx = idx0 + u * ZH_MF_THREADS;
-         if (idx < MK) {
-            bool same = q[u] != ZH_MF_NONE;
-            if (same) {
-               if (K == 3)
-                  same = zh_ld24(gwin + q[u]) == zh_ld24(gwin + pos[u]);
-               else
-                  same = zh_ld32(gwin + q[u]) == zh_ld32(gwin + pos[u]) && (K == 4 || gwin[q[u] + 4] == gwin[pos[u] + 4]);
-            }
-            const uint32_t dist = pos[u] - q[u];
-            const uint32_t d = (same && dist <= ZH_MAX_DIST) ? dist - 1u : 0xffffu;
-            const uint32_t v = K == 3 ? (d | 0xffff0000u) : (K == 4 ? ((old[u] & 0xffffu) | (d << 16)) : d);
-            pay[idx] = v;
-            if (pos[u] + 5u >= W) {
-               if (K == 3)
-                  tail[pos[u]] = make_uint2(v, 0xffffu);
-               else if (K == 4)
-                  tail[pos[u]].x = v;
-               else
-                  tail[pos[u]].y = v;
-            }
-         }
-      }
-   }
-   __syncthreads();
-}
-
-// `win` is read linearly (global memory); `gwin` is the copy used for scattered reads (LDS when the window fits)
-__device__ inline void zh_mf_group_body(const uint8_t *win, const uint8_t *gwin, uint32_t W, uint32_t Qn, uint32_t first_needed, uint32_t *A, uint32_t *B,
-                                        uint2 *prev, uint32_t *pay, uint64_t pay_stride, uint32_t *runs, uint32_t *hist, uint32_t *wave_tot, int stop) {
-   uint32_t *Pa = pay, *Pb = pay + pay_stride;   // payload ping, pong
-   const uint32_t tid = threadIdx.x;
-   // W = window bytes, Qn = positions that are candidates or get rows (the rest of the window is look-ahead)
-   const uint32_t M3 = min(Qn, W >= 3 ? W - 2 : 0u);   // positions that start a trigram
-   const uint32_t M4 = min(Qn, W >= 4 ? W - 3 : 0u);   // positions that start a 4-gram
-
-   // ---- exact trigram order -> previous occurrence of every trigram -------------------------------------------
-   if (stop == 1) return;
-   uint32_t *hist2 = hist + ZH_MF_WAVES * 256 + ZH_MF_WAVES + 1;   // second counter table, behind the kernel's small variables
-   zh_mf_sort_pass<0, false, 1>(win, gwin, M3, nullptr, A, hist, wave_tot, W, hist2, M3);
-   if (stop == 2) return;
-   zh_mf_sort_pass<1, true, 2>(win, gwin, M3, A, B, hist2, wave_tot, W, hist, M3);
-   zh_mf_sort_pass<2, true, 5>(win, gwin, M3, B, A, hist, wave_tot, W, hist2, M3);
-   if (stop == 3) return;
-   if (stop == 4) return;
-
-   // ---- 4-, 5- and 6-gram classes: one more stable pass each over the previous order ------------------------------
-   // prev4 / prev5 (nearest earlier position sharing 4 / 5 bytes) give the records of length 4 and 5 directly; only
-   // matches of 6 and more are found by walking a class, and 6-gram classes are several times smaller than 4-gram
-   // classes (on text the walk shrinks 2.3x, on source code 1.5x). Each pass takes the distances of its input order as it reads it.
-   const uint32_t M5 = min(Qn, W >= 5 ? W - 4 : 0u), M6 = min(Qn, W >= 6 ? W - 5 : 0u);
-   zh_mf_sort_pass<5, true, 6, 1, 3>(win, gwin, M3, A, B, hist2, wave_tot, W, hist, M4, nullptr, nullptr, nullptr, Pb, nullptr, nullptr, prev);   // B: 4-gram order, M4 entries; Pb: d3
-   zh_mf_sort_pass<6, true, 7, 1, 4>(win, gwin, M4, B, A, hist, wave_tot, W, hist2, M5, nullptr, nullptr, Pb, Pa, nullptr, nullptr, prev);      // A: 5-gram order, M5 entries; Pa: d3 | d4 << 16
-   // B: 6-gram order, M6 entries; prev[idx] = the distances of the position at B[idx]
-   zh_mf_sort_pass<7, true, -1, 2, 5>(win, gwin, M5, A, B, hist2, wave_tot, W, nullptr, 0, nullptr, nullptr, Pa, nullptr, nullptr, prev, prev);
-   if (stop == 5) return;
-   {
-      const uint32_t *__restrict__ Br = B;
-      uint32_t *__restrict__ Aw = A;
-      for (uint32_t idx0 = tid; idx0 < M6; idx0 += 4 * ZH_MF_THREADS) {
-         uint32_t e[4], eq[4];
-#pragma unroll
-         for (uint32_t u = 0; u < 4; u++) {
-            const uint32_t idx = idx0 + u * ZH_MF_THREADS;
-            e[u] = idx < M6 ? Br[idx] : 0u;
-            eq[u] = (idx < M6 && idx > 0) ? Br[idx - 1] : 0u;
-         }
-#pragma unroll
-         for (uint32_t u = 0; u < 4; u++) {
-            const uint32_t idx = idx0 + u * ZH_MF_THREADS;
-            if (idx < M6) {
-               const bool head = idx == 0 || zh_ld32(gwin + eq[u]) != zh_ld32(gwin + e[u]) ||
-                                 (((uint32_t)gwin[eq[u] + 4] | ((uint32_t)gwin[eq[u] + 5] << 8)) != ((uint32_t)gwin[e[u] + 4] | ((uint32_t)gwin[e[u] + 5] << 8)));
-               Aw[idx] = e[u] | (head ? ZH_MF_HEAD : 0u);   // the scan stops after consuming a marked entry
-            }
-         }
-      }
-   }
-   __syncthreads();
-   uint64_t mfg_t_ = 0;
-   zh_mf_build_runs(win, gwin, W, Qn, B, runs, hist, wave_tot, mfg_t_);   // B is free again: scratch for the run starts
 }
 
 // 4 bytes at an arbitrary byte offset x of a dword-aligned buffer: two aligned dword reads + funnel shift
@@ -612,11 +477,11 @@ __device__ __forceinline__ uint32_t zh_load32_at(const uint32_t *w32, uint32_t x
 }
 #include "zh_mf_group_lds.h"
 
-// lds_cap: elements per chunk of the in-LDS refinement (zh_mf_group_lds.h; the layout may allow fewer); 0: rounds 1-3's six passes through HBM
+// lds_cap: elements per chunk of the in-LDS refinement (zh_mf_group_lds.h; the layout may allow fewer, and at least 16 are taken)
 template <bool LDS_WIN>
 __global__ void __launch_bounds__(ZH_MF_THREADS)
 zh_mf_group(const uint8_t *__restrict__ data, const zh_seg_t *__restrict__ segs, uint32_t *sort_a,
-            uint32_t *sort_b, uint2 *prev_all, uint32_t *runs_all, uint64_t sort_stride, uint64_t run_stride, int stop, uint32_t nsegs,
+            uint32_t *sort_b, uint2 *prev_all, uint32_t *runs_all, uint64_t sort_stride, uint64_t run_stride, uint32_t nsegs,
             uint32_t *ticket, uint32_t *pay_all /* 3 x sort_stride words per workgroup: the payload of the refining passes */, uint32_t lds_cap) {
    // All of this kernel's LDS is dynamic (ZH_MF_GROUP_LDS bytes at launch). Measured on gfx950: next to a workgroup with
    // 128 KiB of STATIC LDS, workgroups of another stream's kernel that use static LDS are not scheduled at all although
@@ -630,8 +495,6 @@ zh_mf_group(const uint8_t *__restrict__ data, const zh_seg_t *__restrict__ segs,
    // Persistent workgroups (the host launches one per CU) take segments from a ticket counter. A grid of one workgroup
    // per segment would keep workgroups of 114 KiB LDS waiting for a CU throughout the kernel, and while such a workgroup
    // waits the dispatcher holds back the small kernels of the other run's stream (measured: a 0.3 ms kernel took 6.4 ms).
-   uint64_t mfg_t_ = 0;
-   ZH_MFG_TIC();
    for (;;) {
    __syncthreads();   // the previous segment is done with LDS (and with cur_seg)
    if (threadIdx.x == 0) cur_seg = atomicAdd(ticket, 1u);
@@ -645,22 +508,9 @@ zh_mf_group(const uint8_t *__restrict__ data, const zh_seg_t *__restrict__ segs,
    uint32_t *B = sort_b + (uint64_t)seg * sort_stride;
    uint2 *prev3 = prev_all + (uint64_t)seg * sort_stride;
    uint32_t *runs = runs_all + (uint64_t)seg * run_stride;
-   const uint8_t *gwin = win;
-   if (LDS_WIN) {
-      zh_stage_window(lwin32, win, W);
-      gwin = (const uint8_t *)lwin32;
-   }
-#ifdef ZH_MF_GROUP_HBM   // A/B builds (tools/build_variant.sh): rounds 1-3's six passes through HBM when the host passes lds_cap = 0 (ZULTRA_HIP_MF_CAP=0)
-   if (!LDS_WIN || !lds_cap)
-   {
-      zh_mf_group_body(win, gwin, W, blk.prev + blk.n, blk.prev, A, B, prev3, pay_all + (uint64_t)blockIdx.x * 3u * sort_stride, sort_stride, runs, hist, wave_tot,
-                       stop);
-      if (threadIdx.x == 0) runs[run_stride - ZH_MFL_NOTE_WORDS] = 0;   // (nothing for zh_mf_group_big)
-   }
-   else
-#endif
-      zh_mf_group_body_lds(win, dyn_lds, W, blk.prev + blk.n, A, B, prev3, pay_all + (uint64_t)blockIdx.x * 3u * sort_stride, sort_stride, runs, runs + run_stride - ZH_MFL_NOTE_WORDS, hist, wave_tot, stop,
-                           lds_cap, mfg_t_);
+   if (LDS_WIN) zh_stage_window(lwin32, win, W);
+   zh_mf_group_body_lds(dyn_lds, W, blk.prev + blk.n, A, B, prev3, pay_all + (uint64_t)blockIdx.x * 3u * sort_stride, sort_stride, runs, runs + run_stride - ZH_MFL_NOTE_WORDS, hist, wave_tot,
+                        lds_cap);
    }
 }
 
@@ -738,36 +588,6 @@ __device__ __forceinline__ uint32_t zh_mf_len16(const uint32_t (&c16)[4], const 
    return xs ? base + ((uint32_t)__builtin_ctz(xs) >> 3) : 16u;
 }
 
-#ifdef ZH_MF_PROFILE
-// probe builds only (tools/mf_profile.py): wave-cycles of zh_mf_frontier by phase — 0 window staging, 1 chunk head (entries, prev
-// records, first records), 2 byte-run path, 3 class walk, 4 row store; counts — 6 chunks, 8 walk steps, 9 lanes alive in them, 10 cycles
-// up to the probes' answer, 11 cycles of the verification, 12 steps with a verification, 13 rounds of zh_mf_extend_wave. A wave keeps
-// them in registers and adds them up once per segment: an atomic per lap would sit in front of the next wait for a load.
-__device__ unsigned long long zh_mf_prof[16];
-#define ZH_MF_PROF_VARS() uint64_t pf_[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, pf_t_ = 0, pf_w_ = 0, pf_s_ = 0
-#define ZH_MF_PROF_FLUSH() do { if (lane == 0) { for (int k_ = 0; k_ < 16; k_++) { if (pf_[k_]) atomicAdd(&zh_mf_prof[k_], (unsigned long long)pf_[k_]); pf_[k_] = 0; } } } while (0)
-#define ZH_MF_TIC() pf_t_ = zh_clock()
-#define ZH_MF_LAP(slot_) do { const uint64_t now_ = zh_clock(); pf_[slot_] += now_ - pf_t_; pf_t_ = now_; } while (0)
-#define ZH_MF_COUNT(slot_, n_) pf_[slot_] += (n_)
-#define ZH_MF_SUBTIC() pf_s_ = zh_clock()
-#define ZH_MF_SUBLAP(slot_) do { const uint64_t now_ = zh_clock(); pf_[slot_] += now_ - pf_s_; pf_s_ = now_; } while (0)
-#define ZH_MF_WALK_TOP(mask_) do { pf_w_ = zh_clock(); pf_[8]++; pf_[9] += (uint32_t)zh_popc64(mask_); } while (0)
-#define ZH_MF_WALK_PROBED() do { const uint64_t n_ = zh_clock(); pf_[10] += n_ - pf_w_; pf_w_ = n_; } while (0)
-#define ZH_MF_WALK_VERIFIED() do { pf_[11] += zh_clock() - pf_w_; pf_[12]++; } while (0)
-#define ZH_MF_WALK_EXT(need_) pf_[13] += (uint32_t)zh_popc64(zh_ballot(need_))
-#else
-#define ZH_MF_PROF_VARS()
-#define ZH_MF_PROF_FLUSH()
-#define ZH_MF_TIC()
-#define ZH_MF_LAP(slot_)
-#define ZH_MF_COUNT(slot_, n_)
-#define ZH_MF_SUBTIC()
-#define ZH_MF_SUBLAP(slot_)
-#define ZH_MF_WALK_TOP(mask_) (void)(mask_)
-#define ZH_MF_WALK_PROBED()
-#define ZH_MF_WALK_VERIFIED()
-#define ZH_MF_WALK_EXT(need_)
-#endif
 
 // Matches that run past 16 bytes are finished by the whole wave: for every lane with `need` in turn, lane k compares the four
 // bytes at offset 16 + 4k of the two strings (64 lanes cover 16..271: every length up to 258 in one step), a ballot finds the
@@ -908,7 +728,6 @@ zh_mf_frontier(const uint8_t *__restrict__ data, const zh_seg_t *__restrict__ se
    const uint32_t lane = threadIdx.x & 63;
    uint32_t seg_id = 0;
    bool owner = true, tickets_left = true;
-   ZH_MF_PROF_VARS();
 
    for (;;) {
    if (tickets_left) {
@@ -966,10 +785,8 @@ zh_mf_frontier(const uint8_t *__restrict__ data, const zh_seg_t *__restrict__ se
    const uint8_t *win = gwin;
 
    if (LDS_WIN) {
-      ZH_MF_TIC();
       zh_stage_window(lwin32, gwin, W);
       win = (const uint8_t *)lwin32;
-      ZH_MF_LAP(0);
    }
    if (threadIdx.x == 0) {
       help_key = 0;
@@ -985,7 +802,7 @@ zh_mf_frontier(const uint8_t *__restrict__ data, const zh_seg_t *__restrict__ se
       if (i >= prev && i < Qn) {
          uint32_t e3 = 0, e4 = 0, e5 = 0;   // the entries of length 3, 4 and 5 (0: none)
          if (maxlen >= 3) {
-            const uint2 pv = prevs[i];   // (the last positions' records are indexed by position, zh_mf_prev_level)
+            const uint2 pv = prevs[i];   // (the last positions' records are indexed by position, zh_mf_sort_pass PREV)
             const uint32_t d3 = pv.x & 0xffffu;
             if (d3 != 0xffffu) {
                const uint32_t p3 = i - 1u - d3;
@@ -1029,8 +846,6 @@ zh_mf_frontier(const uint8_t *__restrict__ data, const zh_seg_t *__restrict__ se
       const uint32_t c = ((((ticket >> 6) * 40503u + 12345u) & cmask)) << 6;
       if (c >= M) continue;
 
-      ZH_MF_COUNT(6, 1);
-      ZH_MF_TIC();
       const uint32_t t = c + lane;
       const uint32_t own = t < M ? S[t] : ZH_MF_SENTINEL;
       const uint32_t i = own & ZH_MF_POS_MASK;
@@ -1059,7 +874,7 @@ zh_mf_frontier(const uint8_t *__restrict__ data, const zh_seg_t *__restrict__ se
       if (mine) {
          // nearest occurrence of the trigram: without it there is no match at all; if its 4th byte differs it is the
          // (only) length-3 entry. Likewise the nearest occurrences of the 4-gram and the 5-gram.
-         const uint2 pv = prevs[t];   // the record travels with the entry of the 6-gram order (zh_mf_prev_level)
+         const uint2 pv = prevs[t];   // the record travels with the entry of the 6-gram order (zh_mf_sort_pass PREV)
          const uint32_t d3 = pv.x & 0xffffu, p3 = i - 1u - d3;
          if (d3 != 0xffffu) {
             d4 = pv.x >> 16;
@@ -1093,11 +908,9 @@ zh_mf_frontier(const uint8_t *__restrict__ data, const zh_seg_t *__restrict__ se
             alive = !(own & ZH_MF_HEAD);   // a class head has no earlier occurrence of its 6-gram
          }
       }
-      ZH_MF_LAP(1);
       // ---- positions with six or more bytes of a byte run ahead: the frontier comes from the run table -----------------
       if (mine && has4 && isrun) {
          alive = false;
-         ZH_MF_SUBTIC();
          const uint32_t c = first4 & 0xffu;
          const uint32_t r = LDS_WIN ? zh_run_length(win, i, W, maxlen) : zh_run_length(gwin, i, W, maxlen);   // run bytes left, clamped to maxlen
          // a candidate with r_p run bytes left matches min(r, r_p) bytes unless r_p == r. Nearest first:
@@ -1124,7 +937,6 @@ zh_mf_frontier(const uint8_t *__restrict__ data, const zh_seg_t *__restrict__ se
             //     Four table entries are fetched per round trip.
             //     Only until the record reaches r: from then on the second order takes over (below).
             uint32_t j = a > g0 ? a - 1 : g0;
-            ZH_MF_SUBLAP(5);
             while (j > g0 && cur < r) {
                const uint32_t nf = min(4u, j - g0);
                uint32_t es[4], ls[4];
@@ -1172,7 +984,6 @@ zh_mf_frontier(const uint8_t *__restrict__ data, const zh_seg_t *__restrict__ se
             }
             // (3) a match longer than r: only the position with exactly r run bytes left of an earlier run (of at least r bytes)
             //     that is followed by the same byte as this run. Those runs are contiguous in the second order of the table.
-            ZH_MF_SUBLAP(7);
             if (cur >= r && cur < maxlen && a > g0) {
                const uint32_t *RS2 = runs + 2 * Q + 513, *RL2 = RS2 + Q;
                const uint32_t X = win[i + r];                              // cur < maxlen: i + r is inside the window
@@ -1185,7 +996,6 @@ zh_mf_frontier(const uint8_t *__restrict__ data, const zh_seg_t *__restrict__ se
                   else
                      hi = mid;
                }
-               ZH_MF_SUBLAP(14);
                uint32_t j2 = lo;                                           // entries below j2: runs that start earlier (or end in a smaller byte)
                // (the table is in HBM/L2: the entries of the round after this one are requested before this round is looked at — on
                // indented source code this loop is two thirds of the byte-run path, hundreds of runs of spaces followed by the same letter)
@@ -1238,11 +1048,9 @@ zh_mf_frontier(const uint8_t *__restrict__ data, const zh_seg_t *__restrict__ se
                   }
                }
 #undef ZH_MF_RUNS2_REQUEST
-               ZH_MF_SUBLAP(15);
             }
          }
       }
-      ZH_MF_LAP(2);
       // what a candidate must match to beat `cur`: the four bytes ending at position max(cur, 3) — for cur <= 3 that is
       // a window inside the first six bytes, which every member of the class shares
       uint32_t fo = max(cur, 3u) - 3u;
@@ -1269,7 +1077,7 @@ zh_mf_frontier(const uint8_t *__restrict__ data, const zh_seg_t *__restrict__ se
       //    verification once per candidate with a survivor in any lane, each time for a lane or two.
       // A probe taken before `cur` grew stays a valid pre-filter.
       while (const uint64_t alive_mask_ = zh_ballot(alive)) {
-         ZH_MF_WALK_TOP(alive_mask_);
+         (void)alive_mask_;   // (kept named: without it the compiler allocates this kernel's registers differently)
          // advance ZH_MF_STEP times: entries c+l-1-Nk .. c+l-N-Nk arrive at lane l, nearest first; lane 0 takes the next entries below the chunk
          uint32_t cs[ZH_MF_STEP], qs[ZH_MF_STEP], pbs[ZH_MF_STEP];
 #pragma unroll
@@ -1298,7 +1106,6 @@ zh_mf_frontier(const uint8_t *__restrict__ data, const zh_seg_t *__restrict__ se
          }
          // a class is ascending in position and walked downwards: while no head has been met, the step's last candidate is its farthest
          const bool inreach = i - qs[ZH_MF_STEP - 1u] <= ZH_MAX_DIST;
-         ZH_MF_WALK_PROBED();
          if (zh_ballot(pend != 0u)) {
             bool moved = false;   // a record of this step moved `cur`: the probes above were taken at the old one (still a valid pre-filter)
             do {
@@ -1325,7 +1132,6 @@ zh_mf_frontier(const uint8_t *__restrict__ data, const zh_seg_t *__restrict__ se
                      deep = LDS_WIN ? zh_load32_at(lwin32, q + fn) == zh_load32_at(lwin32, i + fn) : zh_ld32(win + q + fn) == zh_ld32(win + i + fn);
                   }
                }
-               ZH_MF_WALK_EXT(deep);
                if (LDS_WIN)
                   l = zh_mf_length_past16(lwin32, deep, q, i, maxlen, own32, l);
                else if (deep)
@@ -1343,13 +1149,11 @@ zh_mf_frontier(const uint8_t *__restrict__ data, const zh_seg_t *__restrict__ se
                fo = cur - 3;   // (a record of the class walk is at least 6)
                ci = LDS_WIN ? zh_load32_at(lwin32, i + fo) : zh_ld32(win + i + fo);
             }
-            ZH_MF_WALK_VERIFIED();
          }
          // the class ends at its head; beyond 32 KiB everything else is farther still; 258 (or the window end) cannot be beaten
          alive = alive && inreach && !(heads & ZH_MF_HEAD) && cur < maxlen;
       }
 #undef ZH_MF_FEED_NONE
-      ZH_MF_LAP(3);
       if (mine) {
          // rows are longest first: the ring read backwards from the last accepted match
          uint32_t m[8];
@@ -1361,10 +1165,8 @@ zh_mf_frontier(const uint8_t *__restrict__ data, const zh_seg_t *__restrict__ se
          rows_lo[i - prev] = a;
          if (nm >= 4) rows_hi[i - prev] = b2;   // readers fetch it whenever slot 3 holds a match
       }
-      ZH_MF_LAP(4);
    }
 
-   ZH_MF_PROF_FLUSH();
    __syncthreads();   // every wave is done with the window in LDS
    }
 }

@@ -28,9 +28,6 @@
 #ifndef ZH_MFL_CAP_LIMIT
 #define ZH_MFL_CAP_LIMIT ZH_MFL_MAXCAP   // (the emulator build takes a small one: several chunks and oversized classes in a window of a few KB)
 #endif
-#ifndef ZH_MFL_DEBUG
-#define ZH_MFL_DEBUG 0   // timing experiments (wrong output; with ZH_MF_STOP=5): 1 no distances, 2 no ranks, 4 no digit gather
-#endif
 #define ZH_MFL_NOTE_WORDS 59u        // the run table's slack: run_stride = sort_stride + 576 words, zh_mf_build_runs writes at most W + 517
 #define ZH_MFL_MAX_NOTES ((ZH_MFL_NOTE_WORDS - 1u) / 2u)   // 29: a class above `cap` (~3900 of at most 98304 entries) happens at most 25 times
 #define ZH_MF_LDS_TOTAL 163840u    // all of a CU's LDS: one workgroup per CU anyway (1024 threads)
@@ -83,7 +80,7 @@ __device__ __forceinline__ zh_mfl_t zh_mfl_layout(uint32_t *dyn_lds, uint32_t W,
 // zh_mf_sort_pass). Wave w takes the w-th stretch of IN; the lanes of a 64-element step with the same digit find each other with eight
 // ballots and the first of them counts them all (no atomics), a 256-thread scan turns the counts into places.
 template <int K, int PREVK>
-__device__ inline uint32_t zh_mfl_pass(const zh_mfl_t &L, const uint32_t *lwin32, uint32_t W, uint32_t n, const uint32_t *IN, uint32_t *OUT, uint2 *tail, bool excl, uint64_t &mfg_t_) {
+__device__ inline uint32_t zh_mfl_pass(const zh_mfl_t &L, const uint32_t *lwin32, uint32_t W, uint32_t n, const uint32_t *IN, uint32_t *OUT, uint2 *tail, bool excl) {
    const uint8_t *gwin = (const uint8_t *)lwin32;
    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
    const uint32_t stretch = (((n + ZH_MF_WAVES - 1u) / ZH_MF_WAVES) + 63u) & ~63u;   // <= 256
@@ -95,7 +92,7 @@ __device__ inline uint32_t zh_mfl_pass(const zh_mfl_t &L, const uint32_t *lwin32
    zh_lockstep_sync();
    // A lane's place among the wave's elements of its digit: the lanes of a step with the same digit find each other with eight ballots
    // (zh_peers8), the first of them moves the wave's counter of the digit — two digits to a word, 16-bit stores — and everybody reads it
-   // before: what the steps before put there. (Measured on MI355X, tools/mfg_profile.py: a returning LDS atomic per lane — the LDS serves
+   // before: what the steps before put there. (Measured on MI355X with an in-kernel profiler, since removed: a returning LDS atomic per lane — the LDS serves
    // the lanes that meet at an address in lane order, tools/probes/lds_rank_probe.hip — costs a wave about a cycle per lane whatever the
    // addresses: 5200 of a pass's 9500 cycles with sixteen waves at it.)
    uint32_t e4[4], d4[4], o4[4];
@@ -109,7 +106,7 @@ __device__ inline uint32_t zh_mfl_pass(const zh_mfl_t &L, const uint32_t *lwin32
          if (idx < hi) {
             const uint32_t e = IN[idx], pos = e & ZH_MFL_POS_MASK;
             e4[u] = e;
-            if (PREVK && !(ZH_MFL_DEBUG & 1)) {
+            if (PREVK) {
                const uint32_t id = e >> ZH_MFL_ID_SHIFT;
                uint32_t dd = 0xffffu;
                if (idx > 0) {
@@ -137,7 +134,7 @@ __device__ inline uint32_t zh_mfl_pass(const zh_mfl_t &L, const uint32_t *lwin32
                      tail[pos].y = dd;
                }
             }
-            if (pos + (uint32_t)K < W) d4[u] = (ZH_MFL_DEBUG & 4) ? (pos >> 3) & 0xffu : (uint32_t)gwin[pos + (uint32_t)K];
+            if (pos + (uint32_t)K < W) d4[u] = gwin[pos + (uint32_t)K];
          }
       }
    }
@@ -155,9 +152,7 @@ __device__ inline uint32_t zh_mfl_pass(const zh_mfl_t &L, const uint32_t *lwin32
          o4[u] = before + rank;
       }
    }
-   ZH_MFG_LAP(16);
    zh_sync_lds();
-   ZH_MFG_LAP(17);
    uint32_t c[ZH_MF_WAVES];
    if (tid < 256u) {
       uint32_t t = 0;
@@ -168,9 +163,7 @@ __device__ inline uint32_t zh_mfl_pass(const zh_mfl_t &L, const uint32_t *lwin32
       }
       L.tot[tid] = t;
    }
-   ZH_MFG_LAP(18);
    zh_sync_lds();
-   ZH_MFG_LAP(19);
    if (tid < 256u) {
       // every one of the four waves scans all 256 totals (four per lane) and keeps the 64 it needs: no barrier between scan and use
       uint32_t v[4], t = 0;
@@ -196,9 +189,7 @@ __device__ inline uint32_t zh_mfl_pass(const zh_mfl_t &L, const uint32_t *lwin32
       }
       if (tid == 255u) L.misc[2] = run;   // everything that has a digit
    }
-   ZH_MFG_LAP(20);
    zh_sync_lds();
-   ZH_MFG_LAP(21);
 #pragma unroll
    for (uint32_t u = 0; u < 4; u++) {
       if (u * 64u < stretch) {
@@ -206,20 +197,17 @@ __device__ inline uint32_t zh_mfl_pass(const zh_mfl_t &L, const uint32_t *lwin32
          if (d != 0xffffffffu) OUT[(uint32_t)myhist[d] + o4[u]] = e4[u];
       }
    }
-   ZH_MFG_LAP(22);
    zh_sync_lds();
-   ZH_MFG_LAP(23);
    return L.misc[2];
 }
 
 // The chunk X[0 .. n) — whole bigram classes, each ascending in position — to its part of the 6-gram order: S_out / P_out point at the
 // chunk's first entry of the segment's order. Returns the number of entries written.
-__device__ inline uint32_t zh_mfl_refine(const zh_mfl_t &L, const uint32_t *lwin32, uint32_t W, uint32_t n, uint32_t *S_out, uint2 *P_out, uint2 *tail, bool excl, uint64_t &mfg_t_) {
-   const uint32_t n1 = zh_mfl_pass<2, 0>(L, lwin32, W, n, L.X, L.Y, tail, excl, mfg_t_);
-   const uint32_t n2 = zh_mfl_pass<3, 3>(L, lwin32, W, n1, L.Y, L.X, tail, excl, mfg_t_);
-   const uint32_t n3 = zh_mfl_pass<4, 4>(L, lwin32, W, n2, L.X, L.Y, tail, excl, mfg_t_);
-   const uint32_t n4 = zh_mfl_pass<5, 5>(L, lwin32, W, n3, L.Y, L.X, tail, excl, mfg_t_);
-   ZH_MFG_LAP(3);
+__device__ inline uint32_t zh_mfl_refine(const zh_mfl_t &L, const uint32_t *lwin32, uint32_t W, uint32_t n, uint32_t *S_out, uint2 *P_out, uint2 *tail, bool excl) {
+   const uint32_t n1 = zh_mfl_pass<2, 0>(L, lwin32, W, n, L.X, L.Y, tail, excl);
+   const uint32_t n2 = zh_mfl_pass<3, 3>(L, lwin32, W, n1, L.Y, L.X, tail, excl);
+   const uint32_t n3 = zh_mfl_pass<4, 4>(L, lwin32, W, n2, L.X, L.Y, tail, excl);
+   const uint32_t n4 = zh_mfl_pass<5, 5>(L, lwin32, W, n3, L.Y, L.X, tail, excl);
    for (uint32_t idx = threadIdx.x; idx < n4; idx += ZH_MF_THREADS) {
       const uint32_t e = L.X[idx], pos = e & ZH_MFL_POS_MASK, id = e >> ZH_MFL_ID_SHIFT;
       bool head = idx == 0;
@@ -231,7 +219,6 @@ __device__ inline uint32_t zh_mfl_refine(const zh_mfl_t &L, const uint32_t *lwin
       P_out[idx] = make_uint2(L.D34[id], (uint32_t)L.D5[id]);
    }
    zh_sync_lds();   // the chunk's arrays are free again
-   ZH_MFG_LAP(4);
    return n4;
 }
 
@@ -245,12 +232,12 @@ __device__ inline uint32_t zh_mfl_oversized(const uint8_t *gwin, uint32_t W, uin
    uint32_t *T = pay, *Pa = pay + n0, *Pb = pay + 2u * n0;
    uint2 *P2 = (uint2 *)(pay + 2u * n0);
    const uint32_t *cursor = wave_tot + ZH_MF_WAVES + 1 + ZH_MF_WAVES * 256;   // zh_mf_sort_pass leaves the end of digit d's run in cursor[d]
-   zh_mf_sort_pass<4>(gwin, gwin, n0, SBc, T, hist, wave_tot, W);
-   zh_mf_sort_pass<5, false, -1, 1, 3>(gwin, gwin, n0, T, SBc, hist, wave_tot, W, nullptr, 0, nullptr, nullptr, nullptr, Pb, nullptr, nullptr, tail);
+   zh_mf_sort_pass<4>(gwin, n0, SBc, T, hist, wave_tot, W);
+   zh_mf_sort_pass<5, false, -1, 1, 3>(gwin, n0, T, SBc, hist, wave_tot, W, nullptr, 0, nullptr, nullptr, nullptr, Pb, nullptr, nullptr, tail);
    const uint32_t n2 = cursor[255];
-   zh_mf_sort_pass<6, false, -1, 1, 4>(gwin, gwin, n2, SBc, T, hist, wave_tot, W, nullptr, 0, nullptr, nullptr, Pb, Pa, nullptr, nullptr, tail);
+   zh_mf_sort_pass<6, false, -1, 1, 4>(gwin, n2, SBc, T, hist, wave_tot, W, nullptr, 0, nullptr, nullptr, Pb, Pa, nullptr, nullptr, tail);
    const uint32_t n3 = cursor[255];
-   zh_mf_sort_pass<7, false, -1, 2, 5>(gwin, gwin, n3, T, SBc, hist, wave_tot, W, nullptr, 0, nullptr, nullptr, Pa, nullptr, nullptr, P2, tail);
+   zh_mf_sort_pass<7, false, -1, 2, 5>(gwin, n3, T, SBc, hist, wave_tot, W, nullptr, 0, nullptr, nullptr, Pa, nullptr, nullptr, P2, tail);
    const uint32_t n4 = cursor[255];
    const uint32_t *lwin32 = (const uint32_t *)gwin;
    for (uint32_t idx = threadIdx.x; idx < n4; idx += ZH_MF_THREADS) {
@@ -269,34 +256,29 @@ __device__ inline uint32_t zh_mfl_oversized(const uint8_t *gwin, uint32_t W, uin
 }
 
 // the window is staged in LDS at dyn_lds (W bytes); SA receives the 6-gram order, prev the distances next to it
-__device__ inline void zh_mf_group_body_lds(const uint8_t *win, uint32_t *dyn_lds, uint32_t W, uint32_t Qn, uint32_t *SA, uint32_t *SB, uint2 *prev, uint32_t *pay,
-                                            uint64_t pay_stride, uint32_t *runs, uint32_t *notes /* ZH_MFL_NOTE_WORDS words behind the run table */, uint32_t *hist, uint32_t *wave_tot, int stop, uint32_t cap_limit, uint64_t &mfg_t_) {
+__device__ inline void zh_mf_group_body_lds(uint32_t *dyn_lds, uint32_t W, uint32_t Qn, uint32_t *SA, uint32_t *SB, uint2 *prev, uint32_t *pay,
+                                            uint64_t pay_stride, uint32_t *runs, uint32_t *notes /* ZH_MFL_NOTE_WORDS words behind the run table */, uint32_t *hist, uint32_t *wave_tot, uint32_t cap_limit) {
    const uint32_t *lwin32 = dyn_lds;
    const uint8_t *gwin = (const uint8_t *)dyn_lds;
    const uint32_t tid = threadIdx.x;
    const uint32_t M3 = min(Qn, W >= 3 ? W - 2 : 0u);   // positions that start a trigram
    const zh_mfl_t L = zh_mfl_layout(dyn_lds, W, cap_limit);
    uint32_t nover = 0;   // classes too large for a chunk, noted for zh_mf_group_big
-   if (stop == 1) return;
-   ZH_MFG_LAP(0);
-   ZH_MFG_COUNT(15, 1);
    if (M3 != 0 && M3 <= L.cap) {
       // the whole window is one chunk: the bigram order is two more passes in LDS
       for (uint32_t k = tid; k < M3; k += ZH_MF_THREADS) L.X[k] = k | (k << ZH_MFL_ID_SHIFT);
       zh_sync_lds();
-      zh_mfl_pass<1, 0>(L, lwin32, W, M3, L.X, L.Y, prev, false, mfg_t_);
-      zh_mfl_pass<0, 0>(L, lwin32, W, M3, L.Y, L.X, prev, false, mfg_t_);
-      zh_mfl_refine(L, lwin32, W, M3, SA, prev, prev, false, mfg_t_);
+      zh_mfl_pass<1, 0>(L, lwin32, W, M3, L.X, L.Y, prev, false);
+      zh_mfl_pass<0, 0>(L, lwin32, W, M3, L.Y, L.X, prev, false);
+      zh_mfl_refine(L, lwin32, W, M3, SA, prev, prev, false);
    }
    else if (M3 != 0) {
       uint32_t *hist2 = hist + ZH_MF_WAVES * 256 + ZH_MF_WAVES + 1;
       // (run-interior positions get no digit in the first pass and drop out: zh_mf_run_interior)
-      zh_mf_sort_pass<10, false, 11>(gwin, gwin, M3, nullptr, SA, hist, wave_tot, W, hist2, M3);   // by byte 1; elements position | byte 0 << 24
+      zh_mf_sort_pass<10, false, 11>(gwin, M3, nullptr, SA, hist, wave_tot, W, hist2, M3);   // by byte 1; elements position | byte 0 << 24
       const uint32_t Mb = (wave_tot + ZH_MF_WAVES + 1 + ZH_MF_WAVES * 256)[255];                  // what it wrote (the end of the last digit's run: cursor[255])
       const bool excl = Mb != M3;                                                                // this window has run-interior positions
-      zh_mf_sort_pass<11, true>(gwin, gwin, Mb, SA, SB, hist2, wave_tot, W);                        // by byte 0: SB = the bigram order, Mb entries
-      if (stop == 2) return;
-      ZH_MFG_LAP(1);
+      zh_mf_sort_pass<11, true>(gwin, Mb, SA, SB, hist2, wave_tot, W);                        // by byte 0: SB = the bigram order, Mb entries
       uint32_t s = 0, out_base = 0;
       uint32_t en[4];
 #define ZH_MFL_REQUEST(from_)                                                          \
@@ -331,7 +313,6 @@ __device__ inline void zh_mf_group_body_lds(const uint8_t *win, uint32_t *dyn_ld
          zh_sync_lds();
          const uint32_t n = (s + nload == Mb) ? nload : L.misc[0];
          if (n == 0) {
-            ZH_MFG_LAP(2);
             // one class fills the chunk and goes on: its end is the first entry of another bigram, found in two rounds of probes
             const uint32_t big0 = zh_load32_at(lwin32, L.X[0] & ZH_MFL_POS_MASK) & 0xffffu;
             const uint32_t rem = Mb - s;
@@ -366,20 +347,14 @@ __device__ inline void zh_mf_group_body_lds(const uint8_t *win, uint32_t *dyn_ld
             nover++;
             out_base += nv;
             s += n0;
-            ZH_MFG_LAP(5);
-            ZH_MFG_COUNT(13, 1);
-            ZH_MFG_COUNT(14, n0);
             ZH_MFL_REQUEST(s);
             continue;
          }
          ZH_MFL_REQUEST(s + n);   // the next chunk's elements are on their way while this one is refined
-         ZH_MFG_LAP(2);
-         ZH_MFG_COUNT(12, 1);
-         out_base += zh_mfl_refine(L, lwin32, W, n, SA + out_base, prev + out_base, prev, excl, mfg_t_);
+         out_base += zh_mfl_refine(L, lwin32, W, n, SA + out_base, prev + out_base, prev, excl);
          s += n;
       }
 #undef ZH_MFL_REQUEST
-      ZH_MFG_LAP(5);
       // the run-interior positions: entries of their own at the top of the order (the sorted part ends exactly where they begin: together
       // they are the M6 positions with six bytes ahead), each marked as a class head — nothing walks into them, zh_mf_frontier takes their
       // frontier from the run table — with the position before them as the nearest earlier occurrence of their 3-, 4- and 5-gram
@@ -402,9 +377,8 @@ __device__ inline void zh_mf_group_body_lds(const uint8_t *win, uint32_t *dyn_ld
          }
       }
    }
-   if (stop == 5) return;
    __threadfence_block();
    __syncthreads();
-   zh_mf_build_runs(win, gwin, W, Qn, pay, runs, hist, wave_tot, mfg_t_);   // (scratch for the run starts: the workgroup's `pay` — SB still holds the bigram order of the classes noted for zh_mf_group_big)
+   zh_mf_build_runs(gwin, W, Qn, pay, runs, hist, wave_tot);   // (scratch for the run starts: the workgroup's `pay` — SB still holds the bigram order of the classes noted for zh_mf_group_big)
    if (tid == 0) notes[0] = min(nover, (uint32_t)ZH_MFL_MAX_NOTES);   // (behind what zh_mf_build_runs writes)
 }

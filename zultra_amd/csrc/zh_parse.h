@@ -79,7 +79,8 @@ __device__ __forceinline__ uint32_t zh_ring_wrap(uint32_t x) { return min(x, x -
 #ifndef ZH_CUT_WARM
 #define ZH_CUT_WARM 1024u         // warm-up positions right of a cut (a multiple of 32, 288 .. ZH_CUT_LEN)
 #endif
-#define ZH_CUT_MIN ZH_CUT_LEN      // tasks shorter than this stay whole (measured on JSON-like records, 50 MB: 8192 -> 45.4 ms, 4096 -> 43.6 ms, 2048 -> 43.3 ms)
+// tasks shorter than this stay whole (measured on JSON-like records, 50 MB: 8192 -> 45.4 ms, 4096 -> 43.6 ms, 2048 -> 43.3 ms); at least two warm-ups
+#define ZH_CUT_MIN (ZH_CUT_LEN >= 2u * ZH_CUT_WARM ? ZH_CUT_LEN : 2u * ZH_CUT_WARM)
 #define ZH_CUT_ROWS 4u            // segments per wave (one per 16-lane row)
 // segtasks[].y: number of segments | their length / 32 << 12
 #define ZH_CUT_PACK(K, S) ((K) | (((S) >> 5) << 12))

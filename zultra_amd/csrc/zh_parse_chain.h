@@ -57,10 +57,6 @@ struct zh_chain_job_t {
    int16_t *export_left;   // relative costs of [t0, t0 + 258] at the end (t1 - t0 a multiple of the tile), or NULL
 };
 
-#ifdef ZH_CHAIN_PROFILE
-__device__ uint64_t zh_chain_profile[4];   // probe builds only (tools/probes/chain2_probe.hip): busy cycles per role of the last chain
-#endif
-
 struct zh_chain_ws_t {
    union {
       struct {
@@ -343,14 +339,6 @@ __device__ inline void zh_chain_parse(zh_chain_ws_t &ws, const uint4 *rows, cons
    else
       zh_set_wave_priority_mid();
 
-#ifdef ZH_CHAIN_PROFILE
-   uint64_t busy = 0, tic = 0;
-#define ZH_CHAIN_TIC() tic = zh_clock()
-#define ZH_CHAIN_TOC() busy += zh_clock() - tic
-#else
-#define ZH_CHAIN_TIC()
-#define ZH_CHAIN_TOC()
-#endif
    // One loop per role, one workgroup barrier per tile period in each (every wave meets the same number of barriers).
    if (wave == 0) {
       zh_chain_state_t st;
@@ -363,11 +351,9 @@ __device__ inline void zh_chain_parse(zh_chain_ws_t &ws, const uint4 *rows, cons
          st.cv = (uint32_t)(ZH_VEC_BIAS + (int32_t)job.import[2 + lane]) << 9;
       }
       for (uint32_t k = 0; k < ntiles; k++) {
-         ZH_CHAIN_TIC();
          if (st.c1 >= ZH_CHAIN_REBASE) zh_chain_rebase(ws, st);
          zh_chain_consume(ws, k & 1u, ZH_CHAIN_TILE_HI(k), st);
          if (job.export_spec && ZH_CHAIN_TILE_HI(k) - ZH_CHAIN_TILE == job.store_hi) zh_chain_export(ws, job.export_spec, job.store_hi);
-         ZH_CHAIN_TOC();
          zh_sync_lds();
       }
       if (job.export_left) zh_chain_export(ws, job.export_left, t0);
@@ -381,14 +367,12 @@ __device__ inline void zh_chain_parse(zh_chain_ws_t &ws, const uint4 *rows, cons
          for (uint32_t q = 0; q < 3; q++) {
             const uint32_t k = k3 + q;
             if (k < ntiles) {
-               ZH_CHAIN_TIC();
                if (k + 3 < ntiles) zh_chain_fetch(fr[q], rows, rows_hi, win, prev, ZH_CHAIN_TILE_HI(k + 3), ZH_CHAIN_TILE_CNT(k + 3), pl);
                if (k + 1 < ntiles) {
                   ZH_CHAIN_AWAIT(min(ntiles - 1u, k + 3u) - (k + 1u));   // requests younger than tile k+1's: tiles k+2 .. min(k+3, last)
                   zh_async_landed(fr[(q + 1) % 3u]);
                   zh_chain_stage(ws, (k + 1) & 1u, (k + 1) & 3u, fr[(q + 1) % 3u], ZH_CHAIN_TILE_HI(k + 1), ZH_CHAIN_TILE_CNT(k + 1), sb_end, pl, lcw);
                }
-               ZH_CHAIN_TOC();
                zh_sync_lds();
             }
          }
@@ -396,19 +380,12 @@ __device__ inline void zh_chain_parse(zh_chain_ws_t &ws, const uint4 *rows, cons
    }
    else {
       for (uint32_t k = 0; k < ntiles; k++) {
-         ZH_CHAIN_TIC();
          if (k) zh_chain_flush(ws, (k - 1) & 1u, (k - 1) & 3u, prev, ZH_CHAIN_TILE_HI(k - 1), ZH_CHAIN_TILE, sb_end, lane, best, job.store_hi);
-         ZH_CHAIN_TOC();
          zh_sync_lds();
       }
       const uint32_t k = ntiles - 1;
       zh_chain_flush(ws, k & 1u, k & 3u, prev, ZH_CHAIN_TILE_HI(k), ZH_CHAIN_TILE_CNT(k), sb_end, lane, best, job.store_hi);
    }
-#ifdef ZH_CHAIN_PROFILE
-   if (lane == 0) zh_chain_profile[wave] = busy;
-#endif
-#undef ZH_CHAIN_TIC
-#undef ZH_CHAIN_TOC
    zh_set_wave_priority_normal();
 #undef ZH_CHAIN_AWAIT
 #undef ZH_CHAIN_TILE_HI

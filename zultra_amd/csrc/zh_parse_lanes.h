@@ -58,25 +58,6 @@ static_assert(ZH_LP_TASKS >= 1 && ZH_LP_TASKS <= 64, "the parsed-task mask of a 
 // write rows 9 q + k, whose LDS banks (16 per row) would coincide for lanes 0 / 2 and for lanes 1 / 3
 #define ZH_LP_PCOL(row_, piece_) ((piece_) ^ ((row_) >= 2u * ZH_LP_QSTRIDE ? 8u : 0u))
 
-#ifdef ZH_LP_PROFILE
-// probe builds only (tools/lp_profile.py): 0 steps, 1 quad-steps with a position, 2 cycles of the step loops, 3 groups, 4 cycles of the
-// group setup, 5 cycles of the histogram walks, 6 pieces, 7 batches with a second plane
-__device__ unsigned long long zh_lp_prof[16];   // 8..11: cycles of the batch staging, stage C, stage B, stage A of the step loop; 12..14: of the histogram phase — waiting for the
-                                                // group's own stores and clearing the counters, the walks, storing the counters
-#define ZH_LP_COUNT(slot_, n_) do { if (zh_lane() == 0) atomicAdd(&zh_lp_prof[slot_], (unsigned long long)(n_)); } while (0)
-#define ZH_LP_CLOCK() zh_clock()
-#else
-#define ZH_LP_COUNT(slot_, n_)
-#define ZH_LP_CLOCK() 0
-#endif
-
-#ifdef ZH_LP_TRACE
-// probe builds only (tools/lp_trace.py): per pass and ticket of the LAST launch that ran {wall clock when the wave started, when it took the ticket, when it was done with
-// it, blockIdx << 32 | HW_ID}
-#define ZH_LP_TRACE_SLOTS 8192u
-__device__ uint64_t zh_lp_trace[4u * ZH_LP_TRACE_SLOTS * 4u];
-#endif
-
 struct alignas(16) zh_lp_ws_t {
    union {
       struct {
@@ -138,7 +119,6 @@ __device__ __forceinline__ void zh_lp_group(zh_lp_ws_t &ws, uint32_t g0, uint32_
    const uint32_t sb_end = wk.start + wk.size;
    const uint64_t lt_mask = (1ull << lane) - 1ull, lt_quad = (1ull << (lane & ~3u)) - 1ull;
 
-   const uint64_t tic0 = ZH_LP_CLOCK();
    zh_wave_sync();   // the previous group is done with the workspace
    // ---- prices of the codes in force; unused symbols price at 9 / 6 bits (blockdeflate.c:873-881) ---------------
    for (uint32_t k = lane; k < ZH_NLIT; k += 64) {
@@ -196,16 +176,6 @@ __device__ __forceinline__ void zh_lp_group(zh_lp_ws_t &ws, uint32_t g0, uint32_
       zh_wave_sync();
    }
    const uint32_t npieces = nlongp + nshortp;
-   ZH_LP_COUNT(3, 1);
-   ZH_LP_COUNT(6, npieces);
-   ZH_LP_COUNT(4, ZH_LP_CLOCK() - tic0);
-   const uint64_t tic1 = ZH_LP_CLOCK();
-#ifdef ZH_LP_PROFILE
-   uint32_t prof_steps = 0, prof_quads = 0, prof_hi = 0;
-   uint64_t prof_lap[4] = {0, 0, 0, 0}, prof_t = ZH_LP_CLOCK();
-#define ZH_LP_LAP(k_) do { const uint64_t n_ = ZH_LP_CLOCK(); prof_lap[k_] += n_ - prof_t; prof_t = n_; } while (0)
-   (void)prof_hi;
-#endif
 
    // ---- the recurrences ----------------------------------------------------------------------------------------------------
    // The only thing a step needs from the step before it is cost[p + 1], for the literal: everything about the matches of p looks
@@ -342,9 +312,6 @@ __device__ __forceinline__ void zh_lp_group(zh_lp_ws_t &ws, uint32_t g0, uint32_
       ZH_LP_FETCH_HI();
       ZH_LP_FETCH(b2, a2, y2);
 
-#ifdef ZH_LP_PROFILE
-      ZH_LP_LAP(0);
-#endif
 #pragma unroll
       for (uint32_t j = 0; j < 4; j++) {
          // ======== stage A, first half, of entry (cur, j): its slots and its byte ==========================================================
@@ -357,14 +324,7 @@ __device__ __forceinline__ void zh_lp_group(zh_lp_ws_t &ws, uint32_t g0, uint32_
          na.e0 = ws.stage0[piece][j][q];
          na.e1 = cur_hi ? ws.stage1[piece][j][q] : 0u;
          const uint32_t abyte = ws.stageb[piece][j];
-#ifdef ZH_LP_PROFILE
-         prof_steps++;
-         prof_quads += (uint32_t)zh_popc64(zh_ballot(na.act && q == 0));
-#endif
 
-#ifdef ZH_LP_PROFILE
-         ZH_LP_LAP(3);
-#endif
          // ======== stage C of the entry two before: literal first; a match must be strictly cheaper (:292,:307) =====================
          {
             const uint32_t bestkey = zh_quad_min(min(eb.key0, eb.key1));
@@ -405,9 +365,6 @@ __device__ __forceinline__ void zh_lp_group(zh_lp_ws_t &ws, uint32_t g0, uint32_
             }
          }
 
-#ifdef ZH_LP_PROFILE
-         ZH_LP_LAP(1);
-#endif
          // ======== stage B of the entry before: its window, one position down; then the prefix minima over the lengths, P(L) = min over
          //          3 <= k <= L of (cost[pos + k] + price(k)) << 9 | (39 - k): the lane's own ten, then the minimum of the lanes below it ====
          zh_lp_b_t nb;
@@ -457,9 +414,6 @@ __device__ __forceinline__ void zh_lp_group(zh_lp_ws_t &ws, uint32_t g0, uint32_
             nb.fresh = ea.fresh;
          }
 
-#ifdef ZH_LP_PROFILE
-         ZH_LP_LAP(2);
-#endif
          // ======== stage A, second half: the slots' distance prices, the literal's price; for a slot stored with length >= 40 the
          //          price of its clamped length and the cost behind it ========================================================================
          {
@@ -502,15 +456,6 @@ __device__ __forceinline__ void zh_lp_group(zh_lp_ws_t &ws, uint32_t g0, uint32_
 #undef ZH_LP_FAR_ON
 #undef ZH_LP_FAR_AT
 #undef ZH_LP_FAR_PICK
-#ifdef ZH_LP_PROFILE
-   ZH_LP_COUNT(0, prof_steps);
-   ZH_LP_COUNT(1, prof_quads);
-   ZH_LP_COUNT(7, prof_hi);
-   for (int k = 0; k < 4; k++) ZH_LP_COUNT(8 + k, prof_lap[k]);
-#undef ZH_LP_LAP
-#endif
-   ZH_LP_COUNT(2, ZH_LP_CLOCK() - tic1);
-   const uint64_t tic2 = ZH_LP_CLOCK();
 
    // ---- histogram of the group's parse; the per-sub-block sum is taken by zh_sb_build ------------------------------------
    if (sb_dynamic) {
@@ -518,16 +463,12 @@ __device__ __forceinline__ void zh_lp_group(zh_lp_ws_t &ws, uint32_t g0, uint32_
       zh_wave_sync();
       for (uint32_t k = lane; k < ZH_NSYM; k += 64) ws.hist[k] = 0;
       zh_wave_sync();
-      ZH_LP_COUNT(12, ZH_LP_CLOCK() - tic2);
-      const uint64_t tic3 = ZH_LP_CLOCK();
       for (uint32_t gt = g0; gt < g1; gt++) {
          if (!((parsed >> (gt - g0)) & 1ull)) continue;
          const uint2 ti = taskinfo[gt];
          zh_walk_histogram_wave(ws.hist, win, prev, ti.x, ti.y, best);
       }
       zh_wave_sync();
-      ZH_LP_COUNT(13, ZH_LP_CLOCK() - tic3);
-      (void)tic3;
       bool first = true;
       for (uint32_t gt = g0; gt < g1; gt++) {
          if (!((parsed >> (gt - g0)) & 1ull)) continue;
@@ -536,7 +477,6 @@ __device__ __forceinline__ void zh_lp_group(zh_lp_ws_t &ws, uint32_t g0, uint32_
          first = false;
       }
    }
-   ZH_LP_COUNT(5, ZH_LP_CLOCK() - tic2);
 }
 
 // The cut tasks' segments, when a run has many (zh_parse.h, "speculative segments"; zh_segments_are_wide), are parsed by the FIRST seg_grid workgroups of
@@ -591,9 +531,6 @@ zh_parse_lanes(const uint8_t *__restrict__ data, const zh_block_t *__restrict__ 
       return;
    }
    zh_lp_ws_t &ws = sh.ws;
-#ifdef ZH_LP_TRACE
-   const uint64_t trace_born = zh_wall_clock();
-#endif
    const uint32_t ntasks = cnt[ZH_CNT_TASKS];
    if (blockIdx.x - sg.seg_grid >= bounded && (cnt[ZH_CNT_VLONG] | cnt[ZH_CNT_LONG] | cnt[ZH_CNT_SHORT] | cnt[ZH_CNT_SEGTASKS]) != 0u) return;
    for (;;) {
@@ -605,9 +542,6 @@ zh_parse_lanes(const uint8_t *__restrict__ data, const zh_block_t *__restrict__ 
       const uint32_t g0 = w * tasks_per_wave;
       if (g0 >= ntasks) return;
       const uint32_t g1 = min(ntasks, g0 + tasks_per_wave);
-#ifdef ZH_LP_TRACE
-      const uint64_t trace_t0 = zh_wall_clock();
-#endif
       // the wave's tasks, sub-block by sub-block
       for (uint32_t g = g0; g < g1;) {
          const uint32_t sb = taskmap[g].x;
@@ -616,15 +550,6 @@ zh_parse_lanes(const uint8_t *__restrict__ data, const zh_block_t *__restrict__ 
          zh_lp_group(ws, g, ge, data, blocks, match, match_stride, bars, bar_stride, work, taskmap, states, best_all, best_stride, cost_all, hist_part, pass, taskinfo);
          g = ge;
       }
-#ifdef ZH_LP_TRACE
-      if (zh_lane() == 0 && w < ZH_LP_TRACE_SLOTS) {
-         uint64_t *tr = zh_lp_trace + ((uint64_t)pass * ZH_LP_TRACE_SLOTS + w) * 4u;
-         tr[0] = trace_born;
-         tr[1] = trace_t0;
-         tr[2] = zh_wall_clock();
-         tr[3] = ((uint64_t)blockIdx.x << 32) | (uint64_t)__builtin_amdgcn_s_getreg((4 /* HW_REG_HW_ID */) | (0 << 6) | (31 << 11));
-      }
-#endif
       if (!ticket) return;
    }
 }

@@ -169,8 +169,6 @@ __device__ __forceinline__ void zh_set_wave_priority_high() { __builtin_amdgcn_s
 __device__ __forceinline__ void zh_set_wave_priority_mid() { __builtin_amdgcn_s_setprio(2); }
 __device__ __forceinline__ void zh_set_wave_priority_normal() { __builtin_amdgcn_s_setprio(0); }
 
-// shader-clock stamp for the optional in-kernel phase profile (diagnostics only)
-__device__ __forceinline__ uint64_t zh_clock() { return (uint64_t)clock64(); }
 // constant-rate (100 MHz) device clock, comparable between workgroups
 __device__ __forceinline__ uint64_t zh_wall_clock() { return (uint64_t)wall_clock64(); }
 

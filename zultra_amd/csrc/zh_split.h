@@ -28,7 +28,7 @@
 // (Round 5: a run of literals is one loop iteration, not one per literal — a ballot gives the tile's match positions; standing on a match the step is what it was
 // (mark, read its length, jump), standing on a literal everything up to the next match is marked at once. Rounds 1-4 took a dependent readlane-compare-add round per
 // token: on inputs that are mostly literals — the first kilobytes of every small file — 64 rounds per tile, 6600 cycles; the forward walks of zh_parse_lanes were
-// 29 % of that kernel on configuration 5, tools/lp_profile.py.)
+// 29 % of that kernel on configuration 5, measured with an in-kernel profiler since removed.)
 __device__ inline uint64_t zh_chain_mask(uint32_t len, uint32_t &carry, uint32_t limit) {
    const uint64_t below_limit = limit >= 64u ? ~0ull : ((1ull << limit) - 1ull);
    const uint64_t matches = zh_ballot(len >= ZH_MIN_MATCH) & below_limit;

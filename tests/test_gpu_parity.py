@@ -337,11 +337,14 @@ def test_full_size_properties(gpu, checker):
         check_window(gpu, checker, d[lo - prev: lo + 65536], prev, 65536, max_block=65536, tag="blk%d" % blk)
 
 
+@pytest.mark.parametrize("run_graphs", ["1", "0"])
 @pytest.mark.parametrize("runs", ["default", "3"])
-def test_files_mode_graph_replay_vs_oracle(gpu, checker, monkeypatch, runs):
+def test_files_mode_graph_replay_vs_oracle(gpu, checker, monkeypatch, runs, run_graphs):
     """BASELINE configuration 5 in miniature: many small JSON-like inputs, one raw deflate stream each, the kernel sequence
     captured in a hipGraph on the first batch and replayed on the second (different contents, same batch shape) — as one run of
-    inputs (the default for so few) and as three staggered runs forked inside the graph."""
+    inputs (the default for so few) and as three staggered runs, replayed from two graphs per run or, with
+    ZULTRA_HIP_FILES_RUN_GRAPHS=0, launched kernel by kernel."""
+    monkeypatch.setenv("ZULTRA_HIP_FILES_RUN_GRAPHS", run_graphs)
     if runs != "default":
         monkeypatch.setenv("ZULTRA_HIP_STREAMS", runs)
     nfiles = 300

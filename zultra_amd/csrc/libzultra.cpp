@@ -458,11 +458,25 @@ static std::vector<int> zh_pick_devices() {
    return v;
 }
 
-static uint32_t clamp_block(uint32_t n) {
-   if (!n) n = ZULTRA_DEFAULT_MAX_BLOCK_SIZE;
-   if (n < 32768) n = 32768;
-   if (n > 2097152) n = 2097152;
-   return n;
+__attribute__((visibility("hidden"))) uint32_t zh_clamp_block(uint32_t n);   // (zh_device.hip: the max-block size as the library takes it)
+
+// input bytes -> pinned staging, split over a few threads from 2 * piece bytes on. Shared with the device layer (zh_device.hip), not exported.
+__attribute__((visibility("hidden"))) void zh_threaded_copy(uint8_t *dst, const uint8_t *src, size_t n, size_t piece) {
+   if (n < 2 * piece) {
+      memcpy(dst, src, n);
+      return;
+   }
+   const size_t nt = n / piece < 4 ? n / piece : 4;
+   std::vector<std::thread> th;
+   size_t started = 1;   // pieces 1 .. started - 1 have a thread; nothing thrown here may cross the C ABI (extern "C" callers end in std::terminate)
+   try {
+      th.reserve(nt);
+      for (; started < nt; started++) th.emplace_back([=] { memcpy(dst + n * started / nt, src + n * started / nt, n * (started + 1) / nt - n * started / nt); });
+   } catch (...) {
+   }
+   memcpy(dst, src, n / nt);
+   if (started < nt) memcpy(dst + n * started / nt, src + n * started / nt, n - n * started / nt);   // (no thread for the rest: copied here)
+   for (auto &t : th) t.join();
 }
 
 static zultra_hip_ctx_t *ctx_acquire_on(int dev, uint32_t bs, uint32_t want_blocks) {
@@ -556,7 +570,7 @@ static void *default_zalloc(void *, unsigned int items, unsigned int size) { ret
 static void default_zfree(void *, void *p) { free(p); }
 
 static zultra_status_t stream_init_sized(zultra_stream_t *s, unsigned flags, unsigned bs_in, uint32_t batch_blocks) {
-   const uint32_t bs = clamp_block(bs_in);
+   const uint32_t bs = zh_clamp_block(bs_in);
    if (!s->zalloc) s->zalloc = default_zalloc;
    if (!s->zfree) s->zfree = default_zfree;
    s->adler = 0;
@@ -860,7 +874,7 @@ extern "C" zultra_status_t zultra_stream_compress(zultra_stream_t *s, const int 
 // ================================================================================================================
 
 extern "C" size_t zultra_memory_bound(size_t nInputSize, const unsigned int nFlags, unsigned int nMaxBlockSize) {
-   const size_t bs = clamp_block(nMaxBlockSize);
+   const size_t bs = zh_clamp_block(nMaxBlockSize);
    return (size_t)zultra_frame_get_header_size(nFlags, NULL, 0) + ((nInputSize + (bs - 1)) / bs) * (1 + 4 + 1) * 64 + nInputSize + 1 +
           (size_t)zultra_frame_get_footer_size(nFlags);
 }
@@ -891,26 +905,6 @@ struct MemLanes {
    std::condition_variable cv;
    bool abort;
 };
-
-// input bytes -> pinned staging: the copy is what a lane's first job waits for, so large ones are split over a few threads
-static void staged_copy(uint8_t *dst, const uint8_t *src, size_t n) {
-   const size_t piece = 16u << 20;
-   if (n < 2 * piece) {
-      memcpy(dst, src, n);
-      return;
-   }
-   const size_t nt = n / piece < 4 ? n / piece : 4;
-   std::vector<std::thread> th;
-   size_t started = 1;   // pieces 1 .. started - 1 have a thread; nothing thrown here may cross the C ABI (extern "C" callers end in std::terminate)
-   try {
-      th.reserve(nt);
-      for (; started < nt; started++) th.emplace_back([=] { memcpy(dst + n * started / nt, src + n * started / nt, n * (started + 1) / nt - n * started / nt); });
-   } catch (...) {
-   }
-   memcpy(dst, src, n / nt);
-   if (started < nt) memcpy(dst + n * started / nt, src + n * started / nt, n - n * started / nt);   // (no thread for the rest: copied here)
-   for (auto &t : th) t.join();
-}
 
 static void mem_lane_body(MemLanes *M, size_t lane);
 static void mem_lane_thread(MemLanes *M, size_t lane) {
@@ -955,7 +949,7 @@ static void mem_lane_body(MemLanes *M, size_t lane) {
       if (ok) {
          if (!in_place) {
             memcpy(stage, hsrc, hist);
-            staged_copy(stage + hist, M->in + first, last - first);
+            zh_threaded_copy(stage + hist, M->in + first, last - first, 16u << 20);   // (what a lane's first job waits for)
          }
          blocks.resize(J.nblocks);
          for (size_t b = 0; b < J.nblocks; b++) {
@@ -1129,7 +1123,7 @@ extern "C" size_t zultra_memory_compress_dict(const unsigned char *pIn, size_t n
                                               const unsigned int nFlags, unsigned int nMaxBlockSize, const void *pDict, int nDictSize) {
    zultra_stream_t strm;
    memset(&strm, 0, sizeof(strm));
-   const uint32_t bs = clamp_block(nMaxBlockSize);
+   const uint32_t bs = zh_clamp_block(nMaxBlockSize);
    // The whole input is at hand: shards of max-blocks over the devices asked for (ZULTRA_HIP_DEVICES / zultra_set_devices; "0,0" = two
    // contexts on device 0), at least two max-blocks per lane — or one lane on the one device, its batch staged and uploaded run by run.
    // (ZULTRA_HIP_MEMORY_LANES=0: through the stream API instead, as the reference does, libzultra.c:601-619.)

@@ -23,7 +23,6 @@
 #include <string.h>
 
 #include <mutex>
-#include <thread>
 #include <vector>
 
 #include "../../include/zultra_hip.h"
@@ -55,6 +54,41 @@ static std::recursive_mutex g_emu_mutex;
 static_assert(sizeof(zultra_hip_block_t) == sizeof(zh_block_t), "ABI");
 static_assert(sizeof(zultra_hip_subblock_t) == sizeof(zh_subblock_t), "ABI");
 
+// Events of one run of a batch (lane_ev[k]): the boundaries of its stages, between which the timing groups are taken (zh_timing_rows)
+enum zh_run_event {
+   ZH_EV_START,                              // the batch's first command (run 0 only)
+   ZH_EV_INPUT,                              // the run's input is on the device (files mode: the batch's kernels start)
+   ZH_EV_GROUP,                              // end of its first matchfinder kernel: where the next run's matchfinder starts
+   ZH_EV_FRONTIER, ZH_EV_SPLIT, ZH_EV_INIT,  // ends of the frontier kernel, of tokenize / split, of zh_sb_init + zh_list_huge
+   ZH_EV_PARSE0, ZH_EV_BUILD0, ZH_EV_PARSE1, ZH_EV_BUILD1, ZH_EV_PARSE2, ZH_EV_BUILD2, ZH_EV_PARSE3, ZH_EV_BUILD3,   // pass p: + 2p
+   ZH_EV_POST, ZH_EV_EMIT,                   // ends of zh_post_tasks, of zh_emit_tasks
+   ZH_EV_READBACK,                           // end of the run's copies to the host (files mode: of the batch)
+   ZH_EV_JOIN,                               // files mode: run k > 0 is done, run 0's stream waits for it
+   ZH_RUN_EVENTS
+};
+// ... and of a stitch (ev_stitch)
+enum zh_stitch_event { ZH_STITCH_EV_START, ZH_STITCH_EV_END, ZH_STITCH_EVENTS };
+
+// files mode: the captured graphs of one batch shape (batch size, input pointer, runs) — two per run, or one for the whole batch (zh_run_files)
+struct zh_graph_set_t {
+   hipGraph_t graph[2 * ZH_MAX_RUNS];
+   hipGraphExec_t exec[2 * ZH_MAX_RUNS];
+   uint32_t nblocks;   // (0: empty)
+   int runs;
+   const uint8_t *data;
+   uint64_t used;      // (tick of the last launch: the least recently used set is the one replaced)
+};
+
+static void zh_graph_clear(zh_graph_set_t *G) {
+   for (int g = 0; g < 2 * ZH_MAX_RUNS; g++) {
+      if (G->exec[g]) (void)hipGraphExecDestroy(G->exec[g]);
+      if (G->graph[g]) (void)hipGraphDestroy(G->graph[g]);
+      G->exec[g] = NULL;
+      G->graph[g] = NULL;
+   }
+   G->nblocks = 0;
+}
+
 struct zultra_hip_ctx_s {
    int device;
    uint32_t num_cus;            // persistent kernels launch one workgroup per CU
@@ -63,8 +97,8 @@ struct zultra_hip_ctx_s {
    uint64_t W, sort_stride, match_stride, tok_stride, best_stride, slot_stride;
    size_t data_cap;
    size_t device_bytes;         // sum of the context's device allocations (zultra_hip_ctx_info)
-   hipStream_t stream;
-   hipEvent_t ev[8];
+   hipStream_t stream;          // stitches of their own (zh_stitch_on_device)
+   hipEvent_t ev_stitch[ZH_STITCH_EVENTS];
 
    uint8_t *d_data;
    zh_block_t *d_blocks;
@@ -97,7 +131,6 @@ struct zultra_hip_ctx_s {
    uint32_t grid_cap;           // ZULTRA_HIP_GRID_CAP (tests): the <false> grids of the per-sub-block / per-task kernels are capped here, so that the <true> forms behind them get work
    uint32_t mf_lds_cap;         // zh_mf_group: chunk size of the refinement in LDS (at least 16 are taken)
    uint32_t *d_pay;             // zh_mf_group: 3 x sort_stride words per persistent workgroup (payload of the refining sort passes)
-   uint32_t *d_longest;         // (round 2: a copy of slot 0 of every match row; no longer written — its readers take the rows)
    uint32_t *d_tok_pos;
    uint16_t *d_tok_info;
    uint32_t *d_ntok, *d_split_tok, *d_split_cnt, *d_sub_base;
@@ -130,8 +163,7 @@ struct zultra_hip_ctx_s {
    int16_t *d_vecs;             // two cost vectors per segment
    uint64_t seg_tasks_per_block, seg_items_per_block;
    uint64_t *d_chain_trace;     // diagnostics (ZULTRA_HIP_CHAIN_TRACE=1): [run][pass][ticket] {positions, start, end}
-   hipEvent_t ev2[16];
-   // sub-batch pipelining: a batch runs as up to ZH_MAX_LANES contiguous runs of max-blocks, each on its own stream
+   // sub-batch pipelining: a batch runs as up to ZH_MAX_RUNS contiguous runs of max-blocks, each on its own stream
    // "files" mode (zultra_hip_create_files): every max-block is a whole small input (< 8192 bytes, so the splitter can
    // never cut it, blockdeflate.c:646): no history, one sub-block and one task per block, no host decision anywhere in
    // the sequence -> stages 1-3 are captured once in a hipGraph and replayed per batch.
@@ -139,31 +171,19 @@ struct zultra_hip_ctx_s {
    uint32_t max_file_size;      // files mode: the size the context was created for (inputs above it are rejected: from 8192 bytes on
                                 // the reference's splitter may cut an input, which the files pipeline never does)
    uint32_t max_subs;           // sub-blocks a max-block can have: 64, or 1 in files mode
-   hipGraph_t graph;
-   hipGraphExec_t graph_exec;
-   // files mode as several runs: two graphs per run — up to the end of its first matchfinder kernel, and the rest — captured on the run's own stream
-   // (zh_run_files). Two sets are kept: a caller's batches are all of one size except the last (1 000 000 inputs in batches of 65 536), and capturing
-   // a set costs several milliseconds.
-   struct zh_run_graphs_t {
-      hipGraph_t graph[2 * ZH_MAX_RUNS];
-      hipGraphExec_t exec[2 * ZH_MAX_RUNS];
-      uint32_t nblocks;
-      int runs;
-      const uint8_t *data;
-      uint64_t used;   // (tick of the last launch: the older set is the one replaced)
-   } rg[2];
-   uint64_t rg_tick;
+   // files mode as one run: the whole batch in one graph. As several runs: two graphs per run — up to the end of its first matchfinder kernel, and the
+   // rest — captured on the run's own stream (zh_run_files). Two sets of those are kept: a caller's batches are all of one size except the last
+   // (1 000 000 inputs in batches of 65 536), and capturing a set costs several milliseconds.
+   zh_graph_set_t batch_graph, run_graphs[2];
+   uint64_t graph_tick;
    int files_run_graphs;                       // ZULTRA_HIP_FILES_RUN_GRAPHS (default 1): 0 = several runs are launched kernel by kernel, and large batches stay one run
-   uint32_t graph_nblocks;
-   int graph_runs;
-   const uint8_t *graph_data;
-   std::vector<uint64_t> file_off;
    int nlanes;
    hipStream_t lane_stream[ZH_MAX_RUNS];
-   hipEvent_t lane_ev[ZH_MAX_RUNS][24];
+   hipEvent_t lane_ev[ZH_MAX_RUNS][ZH_RUN_EVENTS];
    hipStream_t side_stream[ZH_MAX_RUNS];     // per run: zh_parse_chain runs next to zh_parse_lanes
    hipEvent_t side_ev[ZH_MAX_RUNS][8];       // per pass: fork, join
-   hipEvent_t ev_input;
+   hipEvent_t ev_input;         // the batch's input and descriptors are on the device
+   hipEvent_t ev_fork;          // files mode: the runs' streams fork from run 0's here
    zh_subblock_t *d_results_compact;
    uint8_t *h_stage[2];         // pinned staging for callers that hand over pageable host memory (zultra_hip_staging)
    size_t h_stage_size[2];
@@ -186,7 +206,6 @@ struct zultra_hip_ctx_s {
    uint32_t *d_crc, *d_crc_tables, *d_adler;
    uint32_t *h_adler;
    std::vector<uint32_t> adler;
-   std::vector<zh_stitch_item_t> items;
    std::vector<uint32_t> crc;
    int payload_on_host;       // lazily copied
 
@@ -215,12 +234,16 @@ struct zultra_hip_ctx_s {
 static inline uint64_t zh_min64(uint64_t a, uint64_t b) { return a < b ? a : b; }
 static inline uint64_t zh_max64(uint64_t a, uint64_t b) { return a > b ? a : b; }
 
-static uint32_t zh_clamp_block(uint32_t n) {
-   if (!n) n = 1048576;   // libzultra.c:87-92
+// Shared with the host layer (libzultra.cpp), not exported: a caller's max-block size as the library takes it (libzultra.c:87-92), and the copy of
+// large inputs into pinned staging over a few threads
+__attribute__((visibility("hidden"))) uint32_t zh_clamp_block(uint32_t n) {
+   if (!n) n = 1048576;
    if (n < ZH_MIN_BLOCK) n = ZH_MIN_BLOCK;
    if (n > ZH_MAX_BLOCK) n = ZH_MAX_BLOCK;
    return n;
 }
+
+__attribute__((visibility("hidden"))) void zh_threaded_copy(uint8_t *dst, const uint8_t *src, size_t n, size_t piece);   // (libzultra.cpp)
 
 // ---- wave primitive self-check -------------------------------------------------------------------------------
 __global__ void __launch_bounds__(64) zh_selftest_kernel(uint32_t seed, uint32_t *bad) {
@@ -486,7 +509,6 @@ extern "C" void zultra_hip_destroy(zultra_hip_ctx_t *c) {
    (void)hipFree(c->d_segs);
    (void)hipFree(c->d_chunk_ctr);
    (void)hipFree(c->d_match);
-   (void)hipFree(c->d_longest);
    (void)hipFree(c->d_pay);
    (void)hipFree(c->d_tok_pos);
    (void)hipFree(c->d_tok_info);
@@ -525,10 +547,8 @@ extern "C" void zultra_hip_destroy(zultra_hip_ctx_t *c) {
    (void)hipFree(c->d_chain_trace);
    (void)hipFree(c->d_hist_part);
    (void)hipFree(c->d_task_bits);
-   for (int i = 0; i < 16; i++)
-      if (c->ev2[i]) (void)hipEventDestroy(c->ev2[i]);
    for (int k = 0; k < ZH_MAX_RUNS; k++) {
-      for (int i = 0; i < 24; i++)
+      for (int i = 0; i < ZH_RUN_EVENTS; i++)
          if (c->lane_ev[k][i]) (void)hipEventDestroy(c->lane_ev[k][i]);
       if (c->lane_stream[k]) (void)hipStreamDestroy(c->lane_stream[k]);
       for (int i = 0; i < 8; i++)
@@ -536,13 +556,9 @@ extern "C" void zultra_hip_destroy(zultra_hip_ctx_t *c) {
       if (c->side_stream[k]) (void)hipStreamDestroy(c->side_stream[k]);
    }
    if (c->ev_input) (void)hipEventDestroy(c->ev_input);
-   for (int i = 0; i < 2; i++)
-      for (int k = 0; k < 2 * ZH_MAX_RUNS; k++) {
-         if (c->rg[i].exec[k]) (void)hipGraphExecDestroy(c->rg[i].exec[k]);
-         if (c->rg[i].graph[k]) (void)hipGraphDestroy(c->rg[i].graph[k]);
-      }
-   if (c->graph_exec) (void)hipGraphExecDestroy(c->graph_exec);
-   if (c->graph) (void)hipGraphDestroy(c->graph);
+   if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
+   zh_graph_clear(&c->batch_graph);
+   for (int i = 0; i < 2; i++) zh_graph_clear(&c->run_graphs[i]);
    for (int k = 0; k < 2; k++)
       if (c->h_stage[k]) (void)hipHostFree(c->h_stage[k]);
    if (c->h_crc) (void)hipHostFree(c->h_crc);
@@ -558,8 +574,8 @@ extern "C" void zultra_hip_destroy(zultra_hip_ctx_t *c) {
    if (c->h_adler) (void)hipHostFree(c->h_adler);
    (void)hipFree(c->d_crc_tables);
    if (c->h_payload) (void)hipHostFree(c->h_payload);
-   for (int i = 0; i < 8; i++)
-      if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
+   for (int i = 0; i < ZH_STITCH_EVENTS; i++)
+      if (c->ev_stitch[i]) (void)hipEventDestroy(c->ev_stitch[i]);
    if (c->stream) (void)hipStreamDestroy(c->stream);
    delete c;
 }
@@ -687,8 +703,8 @@ static int zh_create_buffers(zultra_hip_ctx_t *c) {
       ZH_CHECK(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&zh_mf_group_big), hipFuncAttributeMaxDynamicSharedMemorySize, ZH_MF_GROUP_LDS));
    }
    ZH_CHECK(c, hipStreamCreate(&c->stream));
-   for (int i = 0; i < 8; i++) ZH_CHECK(c, hipEventCreate(&c->ev[i]));
-   for (int i = 0; i < 16; i++) ZH_CHECK(c, hipEventCreate(&c->ev2[i]));
+   for (int i = 0; i < ZH_STITCH_EVENTS; i++) ZH_CHECK(c, hipEventCreate(&c->ev_stitch[i]));
+   ZH_CHECK(c, hipEventCreate(&c->ev_fork));
    {
       // ---- switches of the shipped library (INTEGRATION.md lists them): they pick between product paths that the size and kind of the data
       //      would otherwise pick, so that tests can force every path on small inputs; and one diagnostic
@@ -716,7 +732,7 @@ static int zh_create_buffers(zultra_hip_ctx_t *c) {
       c->files_run_graphs = zh_env("ZULTRA_HIP_FILES_RUN_GRAPHS", 1);  // files mode: 0 = several runs are launched kernel by kernel, and large batches stay one run
       for (int k = 0; k < c->nlanes; k++) {
          ZH_CHECK(c, hipStreamCreateWithFlags(&c->lane_stream[k], hipStreamNonBlocking));
-         for (int i = 0; i < 24; i++) ZH_CHECK(c, hipEventCreate(&c->lane_ev[k][i]));
+         for (int i = 0; i < ZH_RUN_EVENTS; i++) ZH_CHECK(c, hipEventCreate(&c->lane_ev[k][i]));
          {
             // zh_parse_chain is a few workgroups following long chains: it should never queue behind the wide kernels
             int lo_prio = 0, hi_prio = 0;
@@ -757,7 +773,7 @@ static int zh_create_buffers(zultra_hip_ctx_t *c) {
        zh_alloc(c, &c->d_vecs, B * c->seg_items_per_block * 2 * ZH_VEC) || zh_alloc(c, &c->d_hist_part, c->max_tasks * ZH_NSYM) || zh_alloc(c, &c->d_task_bits, c->max_tasks))
       return -1;
    if (zh_alloc(c, &c->d_data, c->data_cap + 64) || zh_alloc(c, &c->d_blocks, B) || zh_alloc(c, &c->d_sort_a, B * c->segs_per_block * c->sort_stride) ||
-       zh_alloc(c, &c->d_sort_b, B * c->segs_per_block * c->sort_stride) || zh_alloc(c, &c->d_match, B * c->match_stride) || zh_alloc(c, &c->d_longest, 64) ||
+       zh_alloc(c, &c->d_sort_b, B * c->segs_per_block * c->sort_stride) || zh_alloc(c, &c->d_match, B * c->match_stride) ||
        zh_alloc(c, &c->d_pay, (size_t)c->nlanes * zh_min64(c->total_cus, B * c->segs_per_block) * 3 * c->sort_stride) ||   // (the runs' kernels may overlap)
        zh_alloc(c, &c->d_tok_pos, B * c->tok_stride) || zh_alloc(c, &c->d_tok_info, B * c->tok_stride) ||
        zh_alloc(c, &c->d_ntok, B) || zh_alloc(c, &c->d_chunkmax, B * c->chunks_per_block) || zh_alloc(c, &c->d_spanstart, B * c->chunks_per_block) ||
@@ -1054,14 +1070,14 @@ static int zh_enqueue_run(zultra_hip_ctx_t *c, int k, uint32_t b0, uint32_t nb, 
                        ctr + (size_t)nsg * 2 + 2, pay);
    }
    if (part == 1) return 0;
-   if (part == 0) ZH_CHECK(c, hipEventRecord(ev[2], st));   // the next run's matchfinder starts here (part 2: the caller records it between the two graphs)
+   if (part == 0) ZH_CHECK(c, hipEventRecord(ev[ZH_EV_GROUP], st));   // the next run's matchfinder starts here (part 2: the caller records it between the two graphs)
    // (segment descriptors carry batch-wide block indices: the rows go to d_match + block * match_stride)
    // a run of fewer segments than CUs (one call on a few max-blocks: latency): the workgroups beyond one per segment find the tickets gone and help —
    // a segment of a 64 KiB max-block is ~1500 chunks, shared while a helper's share stays above ZH_MF_HELP_MIN of them (small inputs: nothing worth sharing)
    const uint32_t fr_grid = files ? mf_grid : min(c->num_cus, mf_grid * 8u);
    ZH_LAUNCH_LDS(zh_mf_frontier<true>, fr_grid, ZH_MF_THREADS, ZH_MF_FRONTIER_LDS, st, c->cur_data, sgs, (const uint32_t *)sa, (const uint2 *)p3, (const uint32_t *)rn, c->sort_stride,
-                 c->run_stride, c->d_match, c->match_stride, c->d_longest, c->tok_stride, ctr, nsg, files ? 0u : 1u);
-   if (!files) ZH_CHECK(c, hipEventRecord(ev[3], st));   // (timing marks)
+                 c->run_stride, c->d_match, c->match_stride, (uint32_t *)nullptr, c->tok_stride, ctr, nsg, files ? 0u : 1u);
+   if (!files) ZH_CHECK(c, hipEventRecord(ev[ZH_EV_FRONTIER], st));   // (timing marks)
    if (zh_enqueue_tokenize(c, st, blk, b0, nb) != 0) return -1;
    if (files)
       ZH_LAUNCH(zh_nosplit, (nb + 255) / 256, 256, st, nb, (const uint32_t *)(c->d_ntok + b0), c->d_split_tok + (uint64_t)b0 * (ZH_MAX_SPLITS + 1), c->d_split_cnt + b0);
@@ -1069,18 +1085,13 @@ static int zh_enqueue_run(zultra_hip_ctx_t *c, int k, uint32_t b0, uint32_t nb, 
 #define ZH_LAUNCH_SPLIT(W_)                                                                                                                                   \
    ZH_LAUNCH(zh_split<W_>, nb, 64 * W_, st, blk, (const uint32_t *)(c->d_tok_pos + b0 * c->tok_stride), (const uint16_t *)(c->d_tok_info + b0 * c->tok_stride), \
              c->tok_stride, (const uint32_t *)(c->d_ntok + b0), c->d_split_tok + (uint64_t)b0 * (ZH_MAX_SPLITS + 1), c->d_split_cnt + b0)
-      const uint32_t sw = max_n > 131072 ? 16u : 8u;   // (by the run's largest max-block, not the context's limit)
-      if (sw >= 16)
+      if (max_n > 131072)   // (by the run's largest max-block, not the context's limit)
          ZH_LAUNCH_SPLIT(16);
-      else if (sw >= 8)
-         ZH_LAUNCH_SPLIT(8);
-      else if (sw >= 4)
-         ZH_LAUNCH_SPLIT(4);
       else
-         ZH_LAUNCH_SPLIT(2);
+         ZH_LAUNCH_SPLIT(8);
 #undef ZH_LAUNCH_SPLIT
    }
-   if (!files) ZH_CHECK(c, hipEventRecord(ev[4], st));   // (timing marks)
+   if (!files) ZH_CHECK(c, hipEventRecord(ev[ZH_EV_SPLIT], st));   // (timing marks)
    // ---- stage 3: the sub-block coder, one kernel per step over the run (zh_encode.h) -----------------------------------------------------
 #define ZH_LAUNCH_PLAN(T_)                                                                                                                                                               \
    ZH_LAUNCH(zh_plan_subblocks<T_>, 1, T_, st, blk, nb, (const uint32_t *)(c->d_tok_pos + (uint64_t)b0 * c->tok_stride), c->tok_stride, (const uint32_t *)(c->d_ntok + b0),              \
@@ -1098,7 +1109,7 @@ static int zh_enqueue_run(zultra_hip_ctx_t *c, int k, uint32_t b0, uint32_t nb, 
    ZH_LAUNCH_BOTH(zh_list_huge, task_grid, cap, st, blk, bars, c->bar_stride, (const zh_work_t *)work, (const uint2 *)taskmap, (const uint32_t *)(c->d_match + (uint64_t)b0 * c->match_stride),
              c->match_stride, hugelist, cap, segtasks, segitems, segwaves, files ? 0xFFFFFFFFu : (uint32_t)ZH_CUT_MIN, (uint32_t)ZH_CUT_LEN, cnt, taskinfo, (uint32_t)ZH_COOP_MIN,
              files ? (uint32_t)ZH_COOP_MIN : c->coop_small, files ? 0u : c->num_cus);
-   if (!files) ZH_CHECK(c, hipEventRecord(ev[5], st));   // (timing marks)
+   if (!files) ZH_CHECK(c, hipEventRecord(ev[ZH_EV_INIT], st));   // (timing marks)
    // Persistent workgroups of zh_parse_chain take the listed chains from a ticket (none listed: they leave at once); zh_parse_lanes takes the task
    // list in groups, as a grid that fills the chip's wave slots — next to chains only ZH_LANE_WAVES per CU stay, so that the chain workgroups find
    // room the moment they are launched (the run's counters tell the kernel which); the first workgroups of zh_parse_lanes' grid take the cut tasks' segments when there are many.
@@ -1145,16 +1156,16 @@ static int zh_enqueue_run(zultra_hip_ctx_t *c, int k, uint32_t b0, uint32_t nb, 
                    files ? 0xFFFFFFFFu : c->num_cus * ZH_LANE_WAVES, sg);
       }
       if (!chains_idle) ZH_CHECK(c, hipStreamWaitEvent(st, c->side_ev[k][2 * pass + 1], 0));
-      if (!files) ZH_CHECK(c, hipEventRecord(ev[6 + 2 * pass], st));   // (timing marks)
+      if (!files) ZH_CHECK(c, hipEventRecord(ev[ZH_EV_PARSE0 + 2 * pass], st));   // (timing marks)
       ZH_LAUNCH_BOTH(zh_sb_build, sb_grid, sb_bound, st, (const zh_work_t *)work, states, (const uint32_t *)hist_part, payload, pass, cnt);
-      if (!files) ZH_CHECK(c, hipEventRecord(ev[7 + 2 * pass], st));   // (timing marks)
+      if (!files) ZH_CHECK(c, hipEventRecord(ev[ZH_EV_BUILD0 + 2 * pass], st));   // (timing marks)
    }
    ZH_LAUNCH_BOTH(zh_post_tasks, task_grid, cap, st, c->cur_data, blk, bars, c->bar_stride, (const zh_work_t *)work, (const uint2 *)taskmap, (const uint32_t *)cnt, (const zh_sbstate_t *)states, best,
              c->best_stride, task_bits, (const uint2 *)taskinfo);
-   if (!files) ZH_CHECK(c, hipEventRecord(ev[14], st));   // (timing marks)
+   if (!files) ZH_CHECK(c, hipEventRecord(ev[ZH_EV_POST], st));   // (timing marks)
    ZH_LAUNCH_BOTH(zh_emit_tasks, task_grid, cap, st, c->cur_data, blk, bars, c->bar_stride, (const zh_work_t *)work, (const uint2 *)taskmap, (const uint32_t *)cnt, (const zh_sbstate_t *)states,
              (const uint32_t *)best, c->best_stride, (const uint32_t *)task_bits, payload, c->d_results + s0, (const uint2 *)taskinfo);
-   if (!files) ZH_CHECK(c, hipEventRecord(ev[15], st));   // (timing marks)
+   if (!files) ZH_CHECK(c, hipEventRecord(ev[ZH_EV_EMIT], st));   // (timing marks)
    // per-max-block CRC-32 (linear part) and Adler-32 for the framing's footer (a batch of max-blocks computes them next to its matchfinder: zultra_hip_compress_blocks)
    if (files) {
       // (several inputs to a workgroup: zh_crc32_small)
@@ -1209,26 +1220,73 @@ static int zh_enqueue_files_tail(zultra_hip_ctx_t *c, uint32_t nblocks, hipStrea
    return 0;
 }
 
-static int zh_enqueue_files(zultra_hip_ctx_t *c, uint32_t nblocks, hipStream_t st0) {
+// files mode, run k (blocks [b0, b1)) on stream st: part 0 the whole run, 1 / 2 its halves (zh_enqueue_run)
+static int zh_enqueue_files_run(zultra_hip_ctx_t *c, uint32_t nblocks, int k, hipStream_t st, int part) {
+   const uint32_t b0 = zh_files_run_lo(c, nblocks, k), b1 = zh_files_run_lo(c, nblocks, k + 1);
+   return zh_enqueue_run(c, k, b0, b1 - b0, (uint64_t)(b1 - b0) * c->max_block, c->max_block, b0, b1 - b0, st, c->side_stream[k], part);
+}
+
+// The runs of a files batch: what they need cleared, on the stream they fork from; every run's kernels — or, G, its two captured graphs — on its own
+// stream, behind the previous run's first matchfinder kernel; the join and what follows
+static int zh_enqueue_files(zultra_hip_ctx_t *c, uint32_t nblocks, hipStream_t st0, const zh_graph_set_t *G) {
    const int runs = c->last_runs;
-   // what the runs need cleared, and (below) the copies of what they produce, on the stream the runs fork from
    ZH_CHECK(c, hipMemsetAsync(c->d_chunk_ctr, 0, ((size_t)nblocks * 2 + 3 * (size_t)runs) * sizeof(uint32_t), st0));
    ZH_CHECK(c, hipMemsetAsync(c->d_ntasks, 0, ZH_NCNT * sizeof(uint32_t), st0));
    ZH_CHECK(c, hipMemsetAsync(c->d_payload, 0, (size_t)nblocks * c->slot_stride, st0));
-   ZH_CHECK(c, hipEventRecord(c->ev2[1], st0));   // fork
+   ZH_CHECK(c, hipEventRecord(c->ev_fork, st0));
    for (int k = 0; k < runs; k++) {
       hipStream_t st = k ? c->lane_stream[k] : st0;
       if (k) {
-         ZH_CHECK(c, hipStreamWaitEvent(st, c->ev2[1], 0));
-         ZH_CHECK(c, hipStreamWaitEvent(st, c->lane_ev[k - 1][2], 0));
+         ZH_CHECK(c, hipStreamWaitEvent(st, c->ev_fork, 0));
+         ZH_CHECK(c, hipStreamWaitEvent(st, c->lane_ev[k - 1][ZH_EV_GROUP], 0));
       }
-      const uint32_t b0 = zh_files_run_lo(c, nblocks, k), b1 = zh_files_run_lo(c, nblocks, k + 1);
-      if (zh_enqueue_run(c, k, b0, b1 - b0, (uint64_t)(b1 - b0) * c->max_block, c->max_block, b0, b1 - b0, st, c->side_stream[k], 0) != 0) return -1;
-      if (k) ZH_CHECK(c, hipEventRecord(c->lane_ev[k][17], st));
+      if (G) {
+#ifndef ZH_EMU   // (the emulator captures nothing: G is NULL there)
+         ZH_CHECK(c, hipGraphLaunch(G->exec[2 * k], st));
+         ZH_CHECK(c, hipEventRecord(c->lane_ev[k][ZH_EV_GROUP], st));   // (inside the graph it would be a node, not the stream's mark)
+         ZH_CHECK(c, hipGraphLaunch(G->exec[2 * k + 1], st));
+#endif
+      }
+      else if (zh_enqueue_files_run(c, nblocks, k, st, 0) != 0)
+         return -1;
+      if (k) ZH_CHECK(c, hipEventRecord(c->lane_ev[k][ZH_EV_JOIN], st));
    }
-   for (int k = 1; k < runs; k++) ZH_CHECK(c, hipStreamWaitEvent(st0, c->lane_ev[k][17], 0));   // join
+   for (int k = 1; k < runs; k++) ZH_CHECK(c, hipStreamWaitEvent(st0, c->lane_ev[k][ZH_EV_JOIN], 0));   // join
    return zh_enqueue_files_tail(c, nblocks, st0);
 }
+#ifndef ZH_EMU
+// The set of `sets` captured for this batch shape, or the least recently used one, emptied (nblocks == 0): the caller captures into it and keys it
+static zh_graph_set_t *zh_graph_lookup(zultra_hip_ctx_t *c, zh_graph_set_t *sets, int nsets, uint32_t nblocks) {
+   zh_graph_set_t *G = &sets[0];
+   for (int i = 0; i < nsets; i++) {
+      if (sets[i].nblocks == nblocks && sets[i].data == c->cur_data && sets[i].runs == c->last_runs) return &sets[i];
+      if (sets[i].used < G->used) G = &sets[i];
+   }
+   zh_graph_clear(G);
+   return G;
+}
+
+// ... keyed once it is captured, and stamped at every launch
+static void zh_graph_use(zultra_hip_ctx_t *c, zh_graph_set_t *G, uint32_t nblocks) {
+   G->nblocks = nblocks;
+   G->data = c->cur_data;
+   G->runs = c->last_runs;
+   G->used = ++c->graph_tick;
+}
+
+// graph g of set G: what `enqueue` puts on stream st, captured and instantiated
+template <typename F>
+static int zh_graph_capture(zultra_hip_ctx_t *c, zh_graph_set_t *G, int g, hipStream_t st, F enqueue) {
+   ZH_CHECK(c, hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
+   const int rc = enqueue();
+   const hipError_t e = hipStreamEndCapture(st, &G->graph[g]);
+   if (rc != 0) return -1;
+   ZH_CHECK(c, e);
+   ZH_CHECK(c, hipGraphInstantiate(&G->exec[g], G->graph[g], NULL, NULL, 0));
+   return 0;
+}
+#endif
+
 
 static int zh_run_files(zultra_hip_ctx_t *c, uint32_t nblocks) {
    hipStream_t st = c->lane_stream[0];
@@ -1240,96 +1298,50 @@ static int zh_run_files(zultra_hip_ctx_t *c, uint32_t nblocks) {
       const uint64_t want = c->auto_runs ? ((c->files_run_graphs && nblocks >= 8192u && c->nlanes >= 2) ? 2u : 1u) : zh_min64((uint64_t)c->nlanes, (uint64_t)nblocks / 4u);
       c->last_runs = (int)zh_max64(1, want);
    }
+   const int runs = c->last_runs;
 #ifndef ZH_EMU
-   if (c->last_runs > 1 && c->files_run_graphs) {
+   if (runs > 1 && c->files_run_graphs) {
       // Several runs, each a captured graph of its own on its own stream (the capture of ONE stream that forks into the runs' streams is what
       // crashes next to torch's runtime; a run's capture only forks to its chain stream, like the single graph's). What the runs share — clearing
       // the counters and the payload slots before, the copies of the results after — is launched around them. A run is TWO graphs, cut behind its
       // first matchfinder kernel: the event the next run's matchfinder waits for (the stagger of DESIGN.md 3.6) is recorded between them, by
       // the stream — without it the runs march in step, parse on parse, and two runs are no faster than one.
-      const int runs = c->last_runs;
-      zultra_hip_ctx_s::zh_run_graphs_t *G = NULL;
-      for (int i = 0; i < 2; i++)
-         if (c->rg[i].nblocks == nblocks && c->rg[i].data == c->cur_data && c->rg[i].runs == runs) G = &c->rg[i];
-      if (!G) {
-         G = c->rg[0].used <= c->rg[1].used ? &c->rg[0] : &c->rg[1];
-         for (int k = 0; k < 2 * ZH_MAX_RUNS; k++) {
-            if (G->exec[k]) (void)hipGraphExecDestroy(G->exec[k]);
-            if (G->graph[k]) (void)hipGraphDestroy(G->graph[k]);
-            G->exec[k] = NULL;
-            G->graph[k] = NULL;
-         }
-         G->nblocks = 0;
+      zh_graph_set_t *G = zh_graph_lookup(c, c->run_graphs, 2, nblocks);
+      if (!G->nblocks) {
          ZH_CHECK(c, hipStreamSynchronize(st));   // the input upload is not part of the graphs
          for (int k = 0; k < runs; k++) {
             hipStream_t sk = c->lane_stream[k];
-            const uint32_t b0 = zh_files_run_lo(c, nblocks, k), b1 = zh_files_run_lo(c, nblocks, k + 1);
             ZH_CHECK(c, hipStreamSynchronize(sk));
-            for (int part = 1; part <= 2; part++) {
-               const int g = 2 * k + part - 1;
-               ZH_CHECK(c, hipStreamBeginCapture(sk, hipStreamCaptureModeThreadLocal));
-               const int rc = zh_enqueue_run(c, k, b0, b1 - b0, (uint64_t)(b1 - b0) * c->max_block, c->max_block, b0, b1 - b0, sk, c->side_stream[k], part);
-               const hipError_t e = hipStreamEndCapture(sk, &G->graph[g]);
-               if (rc != 0) return -1;
-               ZH_CHECK(c, e);
-               ZH_CHECK(c, hipGraphInstantiate(&G->exec[g], G->graph[g], NULL, NULL, 0));
-            }
+            for (int part = 1; part <= 2; part++)
+               if (zh_graph_capture(c, G, 2 * k + part - 1, sk, [&] { return zh_enqueue_files_run(c, nblocks, k, sk, part); }) != 0) return -1;
          }
-         G->nblocks = nblocks;
-         G->data = c->cur_data;
-         G->runs = runs;
       }
-      G->used = ++c->rg_tick;
-      ZH_CHECK(c, hipEventRecord(c->lane_ev[0][1], st));
-      ZH_CHECK(c, hipMemsetAsync(c->d_chunk_ctr, 0, ((size_t)nblocks * 2 + 3 * (size_t)runs) * sizeof(uint32_t), st));
-      ZH_CHECK(c, hipMemsetAsync(c->d_ntasks, 0, ZH_NCNT * sizeof(uint32_t), st));
-      ZH_CHECK(c, hipMemsetAsync(c->d_payload, 0, (size_t)nblocks * c->slot_stride, st));
-      ZH_CHECK(c, hipEventRecord(c->ev2[1], st));
-      for (int k = 0; k < runs; k++) {
-         hipStream_t sk = c->lane_stream[k];
-         if (k) {
-            ZH_CHECK(c, hipStreamWaitEvent(sk, c->ev2[1], 0));
-            ZH_CHECK(c, hipStreamWaitEvent(sk, c->lane_ev[k - 1][2], 0));   // behind the previous run's first matchfinder kernel
-         }
-         ZH_CHECK(c, hipGraphLaunch(G->exec[2 * k], sk));
-         ZH_CHECK(c, hipEventRecord(c->lane_ev[k][2], sk));
-         ZH_CHECK(c, hipGraphLaunch(G->exec[2 * k + 1], sk));
-         if (k) ZH_CHECK(c, hipEventRecord(c->lane_ev[k][17], sk));
-      }
-      for (int k = 1; k < runs; k++) ZH_CHECK(c, hipStreamWaitEvent(st, c->lane_ev[k][17], 0));
-      if (zh_enqueue_files_tail(c, nblocks, st) != 0) return -1;
+      zh_graph_use(c, G, nblocks);
+      ZH_CHECK(c, hipEventRecord(c->lane_ev[0][ZH_EV_INPUT], st));
+      if (zh_enqueue_files(c, nblocks, st, G) != 0) return -1;
    }
-   else if (c->last_runs > 1) {
+   else if (runs > 1) {
       // Several runs: launched directly, ~35 launches per run and batch. (Forking the runs' streams inside a stream capture crashes in
       // hipStreamEndCapture when another HIP runtime — torch's — lives in the process; the launches of a batch are 0.5 ms of host time.)
-      ZH_CHECK(c, hipEventRecord(c->lane_ev[0][1], st));
-      if (zh_enqueue_files(c, nblocks, st) != 0) return -1;
+      ZH_CHECK(c, hipEventRecord(c->lane_ev[0][ZH_EV_INPUT], st));
+      if (zh_enqueue_files(c, nblocks, st, NULL) != 0) return -1;
    }
    else {
-   if (!c->graph_exec || c->graph_nblocks != nblocks || c->graph_data != c->cur_data || c->graph_runs != c->last_runs) {
-      if (c->graph_exec) (void)hipGraphExecDestroy(c->graph_exec);
-      if (c->graph) (void)hipGraphDestroy(c->graph);
-      c->graph_exec = NULL;
-      c->graph = NULL;
-      ZH_CHECK(c, hipStreamSynchronize(st));   // the input upload is not part of the graph
-      ZH_CHECK(c, hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-      const int rc = zh_enqueue_files(c, nblocks, st);
-      const hipError_t e = hipStreamEndCapture(st, &c->graph);
-      if (rc != 0) return -1;
-      ZH_CHECK(c, e);
-      ZH_CHECK(c, hipGraphInstantiate(&c->graph_exec, c->graph, NULL, NULL, 0));
-      c->graph_nblocks = nblocks;
-      c->graph_data = c->cur_data;
-      c->graph_runs = c->last_runs;
-   }
-   ZH_CHECK(c, hipEventRecord(c->lane_ev[0][1], st));
-   ZH_CHECK(c, hipGraphLaunch(c->graph_exec, st));
+      // one run: the whole batch as one graph
+      zh_graph_set_t *G = zh_graph_lookup(c, &c->batch_graph, 1, nblocks);
+      if (!G->nblocks) {
+         ZH_CHECK(c, hipStreamSynchronize(st));   // the input upload is not part of the graph
+         if (zh_graph_capture(c, G, 0, st, [&] { return zh_enqueue_files(c, nblocks, st, NULL); }) != 0) return -1;
+      }
+      zh_graph_use(c, G, nblocks);
+      ZH_CHECK(c, hipEventRecord(c->lane_ev[0][ZH_EV_INPUT], st));
+      ZH_CHECK(c, hipGraphLaunch(G->exec[0], st));
    }
 #else
-   ZH_CHECK(c, hipEventRecord(c->lane_ev[0][1], st));
-   if (zh_enqueue_files(c, nblocks, st) != 0) return -1;
+   ZH_CHECK(c, hipEventRecord(c->lane_ev[0][ZH_EV_INPUT], st));
+   if (zh_enqueue_files(c, nblocks, st, NULL) != 0) return -1;
 #endif
-   ZH_CHECK(c, hipEventRecord(c->lane_ev[0][16], st));
+   ZH_CHECK(c, hipEventRecord(c->lane_ev[0][ZH_EV_READBACK], st));
    ZH_CHECK(c, hipStreamSynchronize(st));
    ZH_CHECK(c, hipGetLastError());
    c->results.assign(c->h_results, c->h_results + nblocks);   // (batch coordinates: zh_compact_results)
@@ -1338,15 +1350,15 @@ static int zh_run_files(zultra_hip_ctx_t *c, uint32_t nblocks) {
    c->nsubs = nblocks;
    c->files_stitch_rc = zh_stitch_verdict(c, false);
    c->files_stitched = 1;   // (no stitch_ms of its own: inside a captured graph an event is a node, not a time stamp; the batch's encode_ms covers the assembly)
-   (void)hipEventElapsedTime(&c->timing.h2d_ms, c->lane_ev[0][0], c->ev_input);
-   (void)hipEventElapsedTime(&c->timing.encode_ms, c->lane_ev[0][1], c->lane_ev[0][16]);   // the whole graph
-   (void)hipEventElapsedTime(&c->timing.total_ms, c->lane_ev[0][0], c->lane_ev[0][16]);
+   (void)hipEventElapsedTime(&c->timing.h2d_ms, c->lane_ev[0][ZH_EV_START], c->ev_input);
+   (void)hipEventElapsedTime(&c->timing.encode_ms, c->lane_ev[0][ZH_EV_INPUT], c->lane_ev[0][ZH_EV_READBACK]);   // the whole graph
+   (void)hipEventElapsedTime(&c->timing.total_ms, c->lane_ev[0][ZH_EV_START], c->lane_ev[0][ZH_EV_READBACK]);
    return (int)nblocks;
 }
 
-extern "C" int zultra_hip_compress_blocks(zultra_hip_ctx_t *c, const void *data, size_t data_size, int data_on_device,
-                                          const zultra_hip_block_t *blocks, uint32_t nblocks) {
-   ZH_EMU_SERIALIZE();
+// ---- a batch of max-blocks, stage by stage (zultra_hip_compress_blocks) ----------------------------------------------------------------------------
+
+static int zh_check_batch(zultra_hip_ctx_t *c, const void *data, size_t data_size, int data_on_device, const zultra_hip_block_t *blocks, uint32_t nblocks) {
    if (!c || !data || !blocks || nblocks == 0 || nblocks > c->max_blocks) {
       if (c) snprintf(c->err, sizeof(c->err), "bad arguments");
       return -1;
@@ -1362,56 +1374,41 @@ extern "C" int zultra_hip_compress_blocks(zultra_hip_ctx_t *c, const void *data,
       snprintf(c->err, sizeof(c->err), "batch of %zu bytes exceeds the context's staging capacity %zu", data_size, c->data_cap);
       return -1;
    }
-   ZH_CHECK(c, hipSetDevice(c->device));
-   const bool stitch_now = c->ab_armed && !c->files_mode;   // (one batch only)
-   c->ab_armed = 0;
-   c->stitched_valid = 0;
-   c->files_stitched = 0;
-   c->nblocks = nblocks;
-   c->nsubs = 0;
-   c->blocks.assign((const zh_block_t *)blocks, (const zh_block_t *)blocks + nblocks);
-   c->crc.resize(nblocks);
-   c->payload_size = (size_t)nblocks * c->slot_stride;
-   c->payload_on_host = 0;
-   memset((void *)&c->timing, 0, sizeof(c->timing));
+   return 0;
+}
 
-   // The batch is cut into `lanes` contiguous runs of max-blocks, each driven through the whole kernel sequence on its
-   // own stream. Max-blocks are independent, every per-block buffer is addressed as base + block * stride, so a run
-   // simply sees base pointers advanced to its first block. The single-wave, latency-bound kernels of one run
-   // (zh_split, zh_sb_build, ...) then overlap with the wide kernels of the others.
+// The batch is cut into c->last_runs contiguous runs of max-blocks, run k = blocks [run_b0[k], run_b0[k + 1]), each driven through the whole kernel
+// sequence on its own stream. Max-blocks are independent, every per-block buffer is addressed as base + block * stride, so a run simply sees base
+// pointers advanced to its first block. The single-wave, latency-bound kernels of one run (zh_split, zh_sb_build, ...) then overlap with the wide
+// kernels of the others.
+static void zh_plan_runs(zultra_hip_ctx_t *c, const zultra_hip_block_t *blocks, uint32_t nblocks, uint32_t *run_b0 /* ZH_MAX_RUNS + 1 */) {
    uint64_t batch_bytes = 0;
    for (uint32_t b = 0; b < nblocks; b++) batch_bytes += blocks[b].n;
    const uint64_t want_runs = c->auto_runs ? (batch_bytes >= (256ull << 20) ? 4u : 3u) : (uint64_t)c->nlanes;
    const int lanes = c->last_runs = (int)zh_max64(1, zh_min64(want_runs, zh_min64((uint64_t)nblocks / 4u, batch_bytes >> 22)));   // at least four max-blocks and 4 MiB per run
-   // run k = blocks [run_lo(k), run_lo(k + 1)): the first and the last run get nblocks / lanes max-blocks each (at least four: lanes <= nblocks / 4),
-   // the runs between them split the rest
-   auto run_lo = [&](int k) -> uint32_t {
-      if (k <= 0) return 0u;
-      if (k >= lanes) return nblocks;
-      const uint32_t share = nblocks / (uint32_t)lanes;
-      if (k == 1) return share;
-      if (k == lanes - 1) return nblocks - share;
-      return share + (uint32_t)((uint64_t)(nblocks - 2u * share) * (uint64_t)(k - 1) / (uint64_t)(lanes - 2));
-   };
-   hipStream_t st0 = c->lane_stream[0];
-   bool any_nochains = false;
-   for (int k = 0; k < ZH_MAX_RUNS; k++) {
+   // the first and the last run get nblocks / lanes max-blocks each (at least four: lanes <= nblocks / 4), the runs between them split the rest
+   const uint32_t share = nblocks / (uint32_t)lanes;
+   run_b0[0] = 0;
+   for (int k = 1; k < lanes; k++)
+      run_b0[k] = k == 1 ? share : k == lanes - 1 ? nblocks - share : share + (uint32_t)((uint64_t)(nblocks - 2u * share) * (uint64_t)(k - 1) / (uint64_t)(lanes - 2));
+   run_b0[lanes] = nblocks;
+   for (int k = 0; k < lanes; k++) c->last_run_b0[k] = run_b0[k];
+   // (a batch with runs enqueued without chain kernels may have to be run again — as may one with a run enqueued without its <true> overflow forms: zh_read_back)
+   for (int k = 0; k < ZH_MAX_RUNS; k++)
       c->run_nochains[k] = !c->files_mode && c->chain_skip && k < lanes && c->chain_seen_runs == lanes && c->chain_seen[k] == 0;
-      any_nochains = any_nochains || c->run_nochains[k];
-   }
-   // (such a batch may have to be run again, see below — as may one with a run enqueued without its <true> overflow forms)
-   (void)any_nochains;
-   const bool stitch_with = stitch_now;   // (safe with void runs: zh_compact_results marks the batch, zh_stitch_scan and zh_stitch then write nothing)
+}
 
-   ZH_CHECK(c, hipEventRecord(c->lane_ev[0][0], st0));
-   // data_on_device == 2: pageable host memory, and the batch runs as staggered runs of max-blocks — every run's bytes are staged
-   // (host copy into the context's pinned buffer) and uploaded on the run's own stream just before its kernels are launched, so the
-   // copies of run k+1 go on under the kernels of run k: only the first run's are waited for. (Files mode runs from a captured graph:
-   // its input goes up in one piece like mode 0.)
-   uint8_t *per_run_stage = NULL;
+// The batch's descriptors, segment list and (data_on_device == 0) input on the device, on run 0's stream. data_on_device == 2: pageable host memory, and the
+// batch runs as staggered runs of max-blocks — every run's bytes are staged (host copy into the context's pinned buffer, *stage) and uploaded on the run's own
+// stream just before its kernels are launched (zh_enqueue_batch_run), so the copies of run k+1 go on under the kernels of run k: only the first run's are waited for.
+// (Files mode runs from a captured graph: its input goes up in one piece like mode 0.)
+static int zh_upload_batch(zultra_hip_ctx_t *c, const void *data, size_t data_size, int data_on_device, const zultra_hip_block_t *blocks, uint32_t nblocks, uint8_t **stage) {
+   hipStream_t st0 = c->lane_stream[0];
+   ZH_CHECK(c, hipEventRecord(c->lane_ev[0][ZH_EV_START], st0));
+   *stage = NULL;
    if (data_on_device == 2 && !c->files_mode) {
-      per_run_stage = (uint8_t *)zultra_hip_staging(c, 0, data_size);
-      if (!per_run_stage) {
+      *stage = (uint8_t *)zultra_hip_staging(c, 0, data_size);
+      if (!*stage) {
          snprintf(c->err, sizeof(c->err), "no pinned staging for %zu bytes", data_size);
          return -1;
       }
@@ -1419,7 +1416,7 @@ extern "C" int zultra_hip_compress_blocks(zultra_hip_ctx_t *c, const void *data,
    if (data_on_device == 1)
       c->cur_data = (const uint8_t *)data;
    else {
-      if (!per_run_stage) ZH_CHECK(c, hipMemcpyAsync(c->d_data, data, data_size, hipMemcpyHostToDevice, st0));
+      if (!*stage) ZH_CHECK(c, hipMemcpyAsync(c->d_data, data, data_size, hipMemcpyHostToDevice, st0));
       c->cur_data = c->d_data;
    }
    memcpy(c->h_blocks, blocks, nblocks * sizeof(zh_block_t));
@@ -1436,112 +1433,100 @@ extern "C" int zultra_hip_compress_blocks(zultra_hip_ctx_t *c, const void *data,
    }
    if (zh_build_segments(c, blocks, nblocks, st0) != 0) return -1;
    ZH_CHECK(c, hipEventRecord(c->ev_input, st0));
-   if (c->files_mode) return zh_run_files(c, nblocks);
+   return 0;
+}
 
-   // ---- every run, start to finish: nothing in it waits for the host (zh_enqueue_run) ---------------------------------------------
-   uint32_t run_b0[ZH_MAX_RUNS];
-   for (int k = 0; k < lanes; k++) {
-      hipStream_t st = c->lane_stream[k], side = c->side_stream[k];
-      hipEvent_t *ev = c->lane_ev[k];
-      const uint32_t b0 = run_lo(k), b1 = run_lo(k + 1);
-      const uint32_t nb = b1 - b0;
-      run_b0[k] = c->last_run_b0[k] = b0;
-      if (k) {
-         ZH_CHECK(c, hipStreamWaitEvent(st, c->ev_input, 0));
-         // stagger the runs by one stage: this run's wide matchfinder kernels start when the previous run reaches its
-         // narrow ones (token chain, splitter), so narrow and wide kernels of different runs share the chip
-         ZH_CHECK(c, hipStreamWaitEvent(st, c->lane_ev[k - 1][2], 0));
-      }
-      uint64_t total_n = 0;
-      uint32_t max_n = 0;
-      for (uint32_t b = b0; b < b1; b++) {
-         total_n += blocks[b].n;
-         max_n = max(max_n, blocks[b].n);
-      }
-      if (per_run_stage) {
-         // this run's windows: from the first block's history to the last block's end (the 32 KiB in front of the run go up twice,
-         // with the run before it: the same bytes)
-         // (min / max over the run's blocks: the windows of a batch need not ascend, nor be contiguous — what lies between them goes up too)
-         uint64_t lo = blocks[b0].win_off, hi = blocks[b0].win_off + blocks[b0].prev + blocks[b0].n;
-         for (uint32_t b = b0 + 1; b < b1; b++) {
-            lo = min(lo, (uint64_t)blocks[b].win_off);
-            hi = max(hi, (uint64_t)blocks[b].win_off + blocks[b].prev + blocks[b].n);
-         }
-         const uint8_t *src = (const uint8_t *)data + lo;
-         uint8_t *dst = per_run_stage + lo;
-         const size_t len = (size_t)(hi - lo), piece = 8u << 20;
-         if (len >= 2 * piece) {   // (a run of tens of MB: the host copy is split over a few threads)
-            const size_t nt = len / piece < 4 ? len / piece : 4;
-            std::vector<std::thread> th;
-            size_t started = 1;   // (nothing thrown here may cross the C ABI: pieces without a thread are copied by this one)
-            try {
-               th.reserve(nt);
-               for (; started < nt; started++) th.emplace_back([=] { memcpy(dst + len * started / nt, src + len * started / nt, len * (started + 1) / nt - len * started / nt); });
-            } catch (...) {
-            }
-            memcpy(dst, src, len / nt);
-            if (started < nt) memcpy(dst + len * started / nt, src + len * started / nt, len - len * started / nt);
-            for (auto &t : th) t.join();
-         }
-         else
-            memcpy(dst, src, len);
-         ZH_CHECK(c, hipMemcpyAsync(c->d_data + lo, dst, len, hipMemcpyHostToDevice, st));
-      }
-      ZH_CHECK(c, hipEventRecord(ev[1], st));
-      const uint32_t sg0 = c->seg_base[b0], nsg = c->seg_base[b1] - sg0;   // this run's matchfinder segments
-      ZH_CHECK(c, hipMemsetAsync(c->d_chunk_ctr + (size_t)sg0 * 2 + 3 * (size_t)k, 0, ((size_t)nsg * 2 + 3) * sizeof(uint32_t), st));
-      ZH_CHECK(c, hipMemsetAsync(c->d_ntasks + (size_t)k * ZH_CNT_STRIDE, 0, ZH_CNT_STRIDE * sizeof(uint32_t), st));   // the run's counters and tickets
-      // per-max-block CRC-32 (linear part) and Adler-32 for the framing's footer need the input only: on the run's side stream, next to its matchfinder
-      // (behind the run's last kernel they were the tail of the batch; behind its frontier, round 4, on the path to its first parse pass). The side
-      // stream's later kernels — the chains of every pass — are joined by the run's stream: so is this one.
-      ZH_CHECK(c, hipStreamWaitEvent(side, ev[1], 0));
-      ZH_LAUNCH(zh_crc32_blocks, nb, ZH_CRC_THREADS, side, c->cur_data, (const zh_block_t *)(c->d_blocks + b0), (const uint32_t *)c->d_crc_tables, c->d_crc + b0, c->d_adler + 2 * (size_t)b0);
-      // token bits are ORed into the payload slots: cleared there too, long before stage 3 needs them
-      ZH_CHECK(c, hipMemsetAsync(c->d_payload + (uint64_t)b0 * c->slot_stride, 0, (size_t)nb * c->slot_stride, side));
-      if (stitch_with && k == 0) {
-         // ... and so is the stream buffer of a stitch that goes out with the batch (zh_enqueue_stitch): nobody reads it between two batches' stitches
-         uint64_t bound = 16;
-         for (uint32_t b = 0; b < nblocks; b++) bound += (uint64_t)blocks[b].n + 5ull * (blocks[b].n / 65535u + 1u);
-         bound += 5ull * (uint64_t)nblocks * c->max_subs;
-         ZH_CHECK(c, hipMemsetAsync(c->d_stream, 0, (size_t)zh_min64((uint64_t)c->stream_cap + 16, (bound + 3) & ~3ull), side));
-      }
-      if (zh_enqueue_run(c, k, b0, nb, total_n, max_n, sg0, nsg, st, side, 0) != 0) return -1;
-      ZH_CHECK(c, hipMemcpyAsync(c->h_crc + b0, c->d_crc + b0, nb * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-      ZH_CHECK(c, hipMemcpyAsync(c->h_adler + 2 * (size_t)b0, c->d_adler + 2 * (size_t)b0, 2 * nb * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-      ZH_CHECK(c, hipEventRecord(ev[16], st));
+// What a stitch clears of the stream buffer for the last batch: everything the batch can fill — no sub-block takes more than its stored form, size + 5
+// bytes per 65535 + the three header bits
+static size_t zh_stream_clear_bytes(const zultra_hip_ctx_t *c) {
+   uint64_t bound = 16;
+   for (uint32_t b = 0; b < c->nblocks; b++) bound += (uint64_t)c->blocks[b].n + 5ull * (c->blocks[b].n / 65535u + 1u);
+   bound += 5ull * (uint64_t)c->nblocks * c->max_subs;
+   return (size_t)zh_min64((uint64_t)c->stream_cap + 16, (bound + 3) & ~3ull);
+}
+
+// Run k of a batch, start to finish — nothing in it waits for the host: staggered behind the run before it, its input staged, what it needs cleared,
+// the checksums on its side stream, its kernels (zh_enqueue_run), the copies of its checksums
+static int zh_enqueue_batch_run(zultra_hip_ctx_t *c, int k, const uint8_t *data, const zultra_hip_block_t *blocks, uint32_t b0, uint32_t b1, uint8_t *stage, bool stitch_now) {
+   hipStream_t st = c->lane_stream[k], side = c->side_stream[k];
+   hipEvent_t *ev = c->lane_ev[k];
+   const uint32_t nb = b1 - b0;
+   if (k) {
+      ZH_CHECK(c, hipStreamWaitEvent(st, c->ev_input, 0));
+      // stagger the runs by one stage: this run's wide matchfinder kernels start when the previous run reaches its
+      // narrow ones (token chain, splitter), so narrow and wide kernels of different runs share the chip
+      ZH_CHECK(c, hipStreamWaitEvent(st, c->lane_ev[k - 1][ZH_EV_GROUP], 0));
    }
-   // behind the last run: the descriptors in stream order and batch coordinates, the counts — the first thing the host waits for
-   for (int k = 1; k < lanes; k++) ZH_CHECK(c, hipStreamWaitEvent(st0, c->lane_ev[k][16], 0));
+   uint64_t total_n = 0;
+   uint32_t max_n = 0;
+   for (uint32_t b = b0; b < b1; b++) {
+      total_n += blocks[b].n;
+      max_n = max(max_n, blocks[b].n);
+   }
+   if (stage) {
+      // this run's windows: from the first block's history to the last block's end (the 32 KiB in front of the run go up twice, with the run before it:
+      // the same bytes; min / max over the run's blocks: the windows of a batch need not ascend, nor be contiguous — what lies between them goes up too)
+      uint64_t lo = blocks[b0].win_off, hi = blocks[b0].win_off + blocks[b0].prev + blocks[b0].n;
+      for (uint32_t b = b0 + 1; b < b1; b++) {
+         lo = min(lo, (uint64_t)blocks[b].win_off);
+         hi = max(hi, (uint64_t)blocks[b].win_off + blocks[b].prev + blocks[b].n);
+      }
+      zh_threaded_copy(stage + lo, data + lo, (size_t)(hi - lo), 8u << 20);   // (a run of tens of MB: the host copy is split over a few threads)
+      ZH_CHECK(c, hipMemcpyAsync(c->d_data + lo, stage + lo, (size_t)(hi - lo), hipMemcpyHostToDevice, st));
+   }
+   ZH_CHECK(c, hipEventRecord(ev[ZH_EV_INPUT], st));
+   const uint32_t sg0 = c->seg_base[b0], nsg = c->seg_base[b1] - sg0;   // this run's matchfinder segments
+   ZH_CHECK(c, hipMemsetAsync(c->d_chunk_ctr + (size_t)sg0 * 2 + 3 * (size_t)k, 0, ((size_t)nsg * 2 + 3) * sizeof(uint32_t), st));
+   ZH_CHECK(c, hipMemsetAsync(c->d_ntasks + (size_t)k * ZH_CNT_STRIDE, 0, ZH_CNT_STRIDE * sizeof(uint32_t), st));   // the run's counters and tickets
+   // per-max-block CRC-32 (linear part) and Adler-32 for the framing's footer need the input only: on the run's side stream, next to its matchfinder
+   // (behind the run's last kernel they were the tail of the batch; behind its frontier, round 4, on the path to its first parse pass). The side
+   // stream's later kernels — the chains of every pass — are joined by the run's stream: so is this one.
+   ZH_CHECK(c, hipStreamWaitEvent(side, ev[ZH_EV_INPUT], 0));
+   ZH_LAUNCH(zh_crc32_blocks, nb, ZH_CRC_THREADS, side, c->cur_data, (const zh_block_t *)(c->d_blocks + b0), (const uint32_t *)c->d_crc_tables, c->d_crc + b0, c->d_adler + 2 * (size_t)b0);
+   // token bits are ORed into the payload slots: cleared there too, long before stage 3 needs them
+   ZH_CHECK(c, hipMemsetAsync(c->d_payload + (uint64_t)b0 * c->slot_stride, 0, (size_t)nb * c->slot_stride, side));
+   // ... and so is the stream buffer of a stitch that goes out with the batch (zh_enqueue_stitch): nobody reads it between two batches' stitches
+   if (stitch_now && k == 0) ZH_CHECK(c, hipMemsetAsync(c->d_stream, 0, zh_stream_clear_bytes(c), side));
+   if (zh_enqueue_run(c, k, b0, nb, total_n, max_n, sg0, nsg, st, side, 0) != 0) return -1;
+   ZH_CHECK(c, hipMemcpyAsync(c->h_crc + b0, c->d_crc + b0, nb * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+   ZH_CHECK(c, hipMemcpyAsync(c->h_adler + 2 * (size_t)b0, c->d_adler + 2 * (size_t)b0, 2 * nb * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+   ZH_CHECK(c, hipEventRecord(ev[ZH_EV_READBACK], st));
+   return 0;
+}
+
+// Behind the last run: the descriptors in stream order and batch coordinates, the counts, the stitch that goes out with the batch — then the host's one
+// wait. *again: a run enqueued without chain kernels listed chains after all, or one enqueued without its <true> overflow forms outgrew its grids
+// (zh_run_is_void: its kernels left at once) — the batch has to run again, every run with what the counts just taken say it needs: one batch's time,
+// once, where the stream's content changes.
+static int zh_read_back(zultra_hip_ctx_t *c, const uint32_t *run_b0, int lanes, bool stitch_now, bool *again) {
+   hipStream_t st0 = c->lane_stream[0];
+   const uint32_t nblocks = c->nblocks;
+   for (int k = 1; k < lanes; k++) ZH_CHECK(c, hipStreamWaitEvent(st0, c->lane_ev[k][ZH_EV_READBACK], 0));
    if (zh_enqueue_compact(c, run_b0, lanes, st0) != 0) return -1;
    // (the host's copy of the descriptors — the getters' — needs the count: a small batch copies what it can hold with the counts, one wait instead of two)
    const bool copy_bound = (uint64_t)nblocks * c->max_subs * sizeof(zh_subblock_t) <= (256u << 10);
    if (copy_bound) ZH_CHECK(c, hipMemcpyAsync(c->h_results, c->d_results_compact, (size_t)nblocks * c->max_subs * sizeof(zh_subblock_t), hipMemcpyDeviceToHost, st0));
-   if (stitch_with) {
+   if (stitch_now) {
       // the stitch behind the batch's last kernel (zultra_hip_stitch_with_batch): scan, bit mover and the scan's report before the host's one wait
-      ZH_CHECK(c, hipEventRecord(c->ev[0], st0));
+      // (safe with void runs: zh_compact_results marks the batch, zh_stitch_scan and zh_stitch then write nothing)
+      ZH_CHECK(c, hipEventRecord(c->ev_stitch[ZH_STITCH_EV_START], st0));
       if (zh_enqueue_stitch(c, st0, c->ab_phase, c->ab_final, 0, false, false) != 0) return -1;
    }
    ZH_CHECK(c, hipStreamSynchronize(st0));
    ZH_CHECK(c, hipGetLastError());
+   *again = false;
    for (int k = 0; k < lanes; k++) {
       const uint32_t *cnt = c->h_ntasks + (size_t)k * ZH_CNT_STRIDE;
       c->chain_seen[k] = cnt[ZH_CNT_VLONG] + cnt[ZH_CNT_LONG] + cnt[ZH_CNT_SHORT] + cnt[ZH_CNT_SEGTASKS];
-   }
-   c->chain_seen_runs = lanes;
-   for (int k = 0; k < lanes; k++) {
-      const uint32_t *cnt = c->h_ntasks + (size_t)k * ZH_CNT_STRIDE;
       c->seen_nsubs[k] = cnt[ZH_CNT_NSUBS];
       c->seen_ntasks[k] = cnt[ZH_CNT_TASKS];
-   }
-   for (int k = 0; k < lanes; k++) {
       const bool outgrown = c->run_nomore[k] && (c->seen_nsubs[k] > c->run_grids[k][0] || c->seen_ntasks[k] > c->run_grids[k][1]);
-      if ((c->run_nochains[k] && c->chain_seen[k] != 0) || outgrown) {
-         // a run enqueued without chain kernels lists chains after all (zh_run_is_void: its kernels left at once): the batch again, every run with its chain
-         // kernels (the counts just taken say so) — one batch's time, once, where the stream's content changes
-         c->chain_redone++;
-         c->ab_armed = stitch_now ? 1 : 0;
-         return zultra_hip_compress_blocks(c, data, data_size, data_on_device, blocks, nblocks);
-      }
+      if ((c->run_nochains[k] && c->chain_seen[k] != 0) || outgrown) *again = true;
+   }
+   c->chain_seen_runs = lanes;
+   if (*again) {
+      c->chain_redone++;
+      return 0;
    }
    const uint32_t nsubs = c->h_nsubs[0];
    if (nsubs < nblocks || (uint64_t)nsubs > (uint64_t)nblocks * c->max_subs) {
@@ -1553,44 +1538,85 @@ extern "C" int zultra_hip_compress_blocks(zultra_hip_ctx_t *c, const void *data,
    memcpy(c->crc.data(), c->h_crc, nblocks * sizeof(uint32_t));
    c->adler.assign(c->h_adler, c->h_adler + 2 * (size_t)nblocks);
    c->nsubs = nsubs;
-
-   // device time per kernel group, summed over the runs (they overlap in wall time); total = first launch to last completion
-   for (int k = 0; k < lanes; k++) {
-      hipEvent_t *ev = c->lane_ev[k];
-      float t = 0;
-      auto add = [&](float &acc, hipEvent_t a, hipEvent_t b) {
-         if (hipEventElapsedTime(&t, a, b) == hipSuccess) acc += t;
-      };
-      add(c->timing.group_ms, ev[1], ev[2]);
-      add(c->timing.frontier_ms, ev[2], ev[3]);
-      add(c->timing.tokenize_split_ms, ev[3], ev[4]);
-      add(c->timing.init_ms, ev[4], ev[5]);
-      for (int pass = 0; pass <= 3; pass++) {
-         add(c->timing.parse_ms, ev[5 + 2 * pass], ev[6 + 2 * pass]);
-         add(c->timing.build_ms, ev[6 + 2 * pass], ev[7 + 2 * pass]);
-      }
-      add(c->timing.post_ms, ev[13], ev[14]);
-      add(c->timing.emit_ms, ev[14], ev[15]);
-      add(c->timing.d2h_ms, ev[15], ev[16]);
-      float tot = 0;
-      if (hipEventElapsedTime(&tot, c->lane_ev[0][0], ev[16]) == hipSuccess && tot > c->timing.total_ms) c->timing.total_ms = tot;
-   }
-   (void)hipEventElapsedTime(&c->timing.h2d_ms, c->lane_ev[0][0], c->ev_input);
-   (void)hipEventElapsedTime(&c->timing.head_ms, c->lane_ev[0][0], c->lane_ev[0][3]);
-   {
-      float last_mf = 0;
-      if (hipEventElapsedTime(&last_mf, c->lane_ev[0][0], c->lane_ev[lanes - 1][3]) == hipSuccess) c->timing.tail_ms = c->timing.total_ms - last_mf;
-   }
-   c->timing.matchfinder_ms = c->timing.group_ms + c->timing.frontier_ms;
-   c->timing.encode_ms = c->timing.init_ms + c->timing.parse_ms + c->timing.build_ms + c->timing.post_ms + c->timing.emit_ms;
-   if (stitch_with) {
-      (void)hipEventElapsedTime(&c->timing.stitch_ms, c->ev[0], c->ev[1]);
+   if (stitch_now) {
       c->stitched_rc = zh_stitch_verdict(c, false);
       c->stitched_phase = c->ab_phase;
       c->stitched_final = c->ab_final;
       c->stitched_valid = 1;
    }
-   return (int)nsubs;
+   return 0;
+}
+
+// the kernel groups of zultra_hip_timing_t: device time between two events of a run, summed over the runs (they overlap in wall time)
+static const struct {
+   float zultra_hip_timing_t::*field;
+   zh_run_event from, to;
+} zh_timing_rows[] = {
+   {&zultra_hip_timing_t::group_ms, ZH_EV_INPUT, ZH_EV_GROUP},         {&zultra_hip_timing_t::frontier_ms, ZH_EV_GROUP, ZH_EV_FRONTIER},
+   {&zultra_hip_timing_t::tokenize_split_ms, ZH_EV_FRONTIER, ZH_EV_SPLIT}, {&zultra_hip_timing_t::init_ms, ZH_EV_SPLIT, ZH_EV_INIT},
+   {&zultra_hip_timing_t::parse_ms, ZH_EV_INIT, ZH_EV_PARSE0},         {&zultra_hip_timing_t::build_ms, ZH_EV_PARSE0, ZH_EV_BUILD0},
+   {&zultra_hip_timing_t::parse_ms, ZH_EV_BUILD0, ZH_EV_PARSE1},       {&zultra_hip_timing_t::build_ms, ZH_EV_PARSE1, ZH_EV_BUILD1},
+   {&zultra_hip_timing_t::parse_ms, ZH_EV_BUILD1, ZH_EV_PARSE2},       {&zultra_hip_timing_t::build_ms, ZH_EV_PARSE2, ZH_EV_BUILD2},
+   {&zultra_hip_timing_t::parse_ms, ZH_EV_BUILD2, ZH_EV_PARSE3},       {&zultra_hip_timing_t::build_ms, ZH_EV_PARSE3, ZH_EV_BUILD3},
+   {&zultra_hip_timing_t::post_ms, ZH_EV_BUILD3, ZH_EV_POST},          {&zultra_hip_timing_t::emit_ms, ZH_EV_POST, ZH_EV_EMIT},
+   {&zultra_hip_timing_t::d2h_ms, ZH_EV_EMIT, ZH_EV_READBACK},
+};
+
+// device time per kernel group; total = first launch to last completion
+static void zh_batch_timing(zultra_hip_ctx_t *c, int lanes, bool stitch_now) {
+   zultra_hip_timing_t &T = c->timing;
+   const hipEvent_t start = c->lane_ev[0][ZH_EV_START];
+   for (int k = 0; k < lanes; k++) {
+      hipEvent_t *ev = c->lane_ev[k];
+      float t = 0;
+      for (const auto &row : zh_timing_rows)
+         if (hipEventElapsedTime(&t, ev[row.from], ev[row.to]) == hipSuccess) T.*row.field += t;
+      if (hipEventElapsedTime(&t, start, ev[ZH_EV_READBACK]) == hipSuccess && t > T.total_ms) T.total_ms = t;
+   }
+   (void)hipEventElapsedTime(&T.h2d_ms, start, c->ev_input);
+   (void)hipEventElapsedTime(&T.head_ms, start, c->lane_ev[0][ZH_EV_FRONTIER]);
+   {
+      float last_mf = 0;
+      if (hipEventElapsedTime(&last_mf, start, c->lane_ev[lanes - 1][ZH_EV_FRONTIER]) == hipSuccess) T.tail_ms = T.total_ms - last_mf;
+   }
+   T.matchfinder_ms = T.group_ms + T.frontier_ms;
+   T.encode_ms = T.init_ms + T.parse_ms + T.build_ms + T.post_ms + T.emit_ms;
+   if (stitch_now) (void)hipEventElapsedTime(&T.stitch_ms, c->ev_stitch[ZH_STITCH_EV_START], c->ev_stitch[ZH_STITCH_EV_END]);
+}
+
+extern "C" int zultra_hip_compress_blocks(zultra_hip_ctx_t *c, const void *data, size_t data_size, int data_on_device,
+                                          const zultra_hip_block_t *blocks, uint32_t nblocks) {
+   ZH_EMU_SERIALIZE();
+   if (zh_check_batch(c, data, data_size, data_on_device, blocks, nblocks) != 0) return -1;
+   ZH_CHECK(c, hipSetDevice(c->device));
+   const bool stitch_now = c->ab_armed && !c->files_mode;   // (one batch only)
+   c->ab_armed = 0;
+   c->stitched_valid = 0;
+   c->files_stitched = 0;
+   c->nblocks = nblocks;
+   c->nsubs = 0;
+   c->blocks.assign((const zh_block_t *)blocks, (const zh_block_t *)blocks + nblocks);
+   c->crc.resize(nblocks);
+   c->payload_size = (size_t)nblocks * c->slot_stride;
+   c->payload_on_host = 0;
+   memset((void *)&c->timing, 0, sizeof(c->timing));
+
+   uint32_t run_b0[ZH_MAX_RUNS + 1];
+   zh_plan_runs(c, blocks, nblocks, run_b0);
+   const int lanes = c->last_runs;
+   uint8_t *stage = NULL;
+   if (zh_upload_batch(c, data, data_size, data_on_device, blocks, nblocks, &stage) != 0) return -1;
+   if (c->files_mode) return zh_run_files(c, nblocks);
+   for (int k = 0; k < lanes; k++)
+      if (zh_enqueue_batch_run(c, k, (const uint8_t *)data, blocks, run_b0[k], run_b0[k + 1], stage, stitch_now) != 0) return -1;
+   bool again = false;
+   if (zh_read_back(c, run_b0, lanes, stitch_now, &again) != 0) return -1;
+   if (again) {
+      c->ab_armed = stitch_now ? 1 : 0;
+      return zultra_hip_compress_blocks(c, data, data_size, data_on_device, blocks, nblocks);
+   }
+   zh_batch_timing(c, lanes, stitch_now);
+   return (int)c->nsubs;
 }
 
 extern "C" const zultra_hip_subblock_t *zultra_hip_subblocks(const zultra_hip_ctx_t *c, uint32_t *count) {
@@ -1628,28 +1654,22 @@ extern "C" int zultra_hip_block_crc32(const zultra_hip_ctx_t *c, uint32_t *out) 
 // has (clear = false) —, the scan, the bit mover, the 80 bytes the scan reports. The grids need no count from the host: the scan is one workgroup, the mover strides
 // over scan->nsubs. Enqueues only.
 static int zh_enqueue_stitch(zultra_hip_ctx_t *c, hipStream_t st, uint32_t phase, int final_block, int files, bool scan_only, bool clear) {
-   if (!scan_only && clear) {
-      // the stream buffer must be zero where bits will be ORed in: everything the batch can fill — no sub-block takes more than its stored form,
-      // size + 5 bytes per 65535 + the three header bits
-      uint64_t bound = 16;
-      for (uint32_t b = 0; b < c->nblocks; b++) bound += (uint64_t)c->blocks[b].n + 5ull * (c->blocks[b].n / 65535u + 1u);
-      bound += 5ull * (uint64_t)c->nblocks * c->max_subs;
-      const size_t clear_bytes = (size_t)zh_min64((uint64_t)c->stream_cap + 16, (bound + 3) & ~3ull);
-      ZH_CHECK(c, hipMemsetAsync(c->d_stream, 0, clear_bytes, st));
-   }
+   if (!scan_only && clear) ZH_CHECK(c, hipMemsetAsync(c->d_stream, 0, zh_stream_clear_bytes(c), st));   // (zero where bits will be ORed in)
+   // (the inputs of a files context are smaller than any max-block: their streams are assembled with the buffer bound of the smallest)
+   const uint32_t block_size = c->max_block < ZH_MIN_BLOCK ? (uint32_t)ZH_MIN_BLOCK : c->max_block;
    // (the scan's chunk tables are 32-bit: a chunk of ceil(nblocks / 1024) max-blocks must stay below 2^32 bits — only HBM capacity has ruled that out so far)
-   if (((uint64_t)c->nblocks + ZH_SCAN_THREADS - 1) / ZH_SCAN_THREADS * zh_stitch_blockbuf_cap(c->max_block < ZH_MIN_BLOCK ? (uint32_t)ZH_MIN_BLOCK : c->max_block) * 8ull >= (1ull << 32)) {
+   if (((uint64_t)c->nblocks + ZH_SCAN_THREADS - 1) / ZH_SCAN_THREADS * zh_stitch_blockbuf_cap(block_size) * 8ull >= (1ull << 32)) {
       snprintf(c->err, sizeof(c->err), "batch too large for the stream assembly's 32-bit chunk tables (%u max-blocks of %u bytes)", c->nblocks, c->max_block);
       return -1;
    }
    ZH_LAUNCH(zh_stitch_scan, 1, ZH_SCAN_THREADS, st, (const zh_subblock_t *)c->d_results_compact, (const uint32_t *)c->d_nsubs, c->nblocks, phase,
-             files ? (c->max_block < ZH_MIN_BLOCK ? (uint32_t)ZH_MIN_BLOCK : c->max_block) : c->max_block, final_block, files, c->d_blk_start, c->d_items, c->d_file_off, c->d_scan_out);
+             files ? block_size : c->max_block, final_block, files, c->d_blk_start, c->d_items, c->d_file_off, c->d_scan_out);
    if (!scan_only) {
       const uint32_t grid = (uint32_t)zh_min64((uint64_t)c->nblocks * c->max_subs, zh_max64(4ull * c->nblocks, 1024));
       ZH_LAUNCH(zh_stitch, grid, ZH_STITCH_THREADS, st, (const zh_subblock_t *)c->d_results_compact, (const zh_stitch_item_t *)c->d_items, (const zh_block_t *)c->d_blocks, c->cur_data,
                 (const uint8_t *)c->d_payload, c->d_stream, (const zh_scan_out_t *)c->d_scan_out, (uint64_t)c->stream_cap);
    }
-   ZH_CHECK(c, hipEventRecord(c->ev[1], st));
+   ZH_CHECK(c, hipEventRecord(c->ev_stitch[ZH_STITCH_EV_END], st));
    ZH_CHECK(c, hipMemcpyAsync(c->h_scan_out, c->d_scan_out, sizeof(zh_scan_out_t), hipMemcpyDeviceToHost, st));
    return 0;
 }
@@ -1677,11 +1697,11 @@ static int zh_stitch_on_device(zultra_hip_ctx_t *c, uint32_t phase, int final_bl
    hipStream_t st = c->stream;
    c->stitched_valid = 0;   // (the items and the scan's report are rewritten)
    c->files_stitched = 0;
-   ZH_CHECK(c, hipEventRecord(c->ev[0], st));
+   ZH_CHECK(c, hipEventRecord(c->ev_stitch[ZH_STITCH_EV_START], st));
    if (zh_enqueue_stitch(c, st, phase, final_block, files, scan_only, true) != 0) return -1;
    ZH_CHECK(c, hipStreamSynchronize(st));
    ZH_CHECK(c, hipGetLastError());
-   if (!scan_only) (void)hipEventElapsedTime(&c->timing.stitch_ms, c->ev[0], c->ev[1]);
+   if (!scan_only) (void)hipEventElapsedTime(&c->timing.stitch_ms, c->ev_stitch[ZH_STITCH_EV_START], c->ev_stitch[ZH_STITCH_EV_END]);
    return zh_stitch_verdict(c, scan_only);
 }
 

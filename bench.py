@@ -2,7 +2,7 @@
 """bench.py — the BASELINE.json metric on MI355X: input MB/s of zultra's per-block deflate hot path, bit-exact with the
 CPU reference, one JSON line on rank 0.
 
-    python bench.py [--config 1|2|3|4|5] [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--config 1|2|3|4|5] [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 --config selects one of BASELINE.json's configurations (default 2, the one the metric is quoted on):
   1  bootstrap.min.js (the image's 39 680-byte v3.4.1 stands in), raw deflate, one max-block: known answer 10 523 B
@@ -19,9 +19,13 @@ transfers to rank 0 over RCCL) -> D2H of the finished deflate bytes on rank 0 ->
 one rank when a launcher (torch.distributed.run) already set RANK/WORLD_SIZE; a WORLD_SIZE that differs from --gpus is an
 error, and so are fewer visible GPUs than N. Weak scaling: every rank takes its own shard of ONE N-times-larger stream.
 
-Every line carries `roofline` (dominant kernel, live HIP-event duration on the library's streams) and `cpu_baseline` (the
-compiled reference oracle/_ref — or the oracle port where it did not travel — on a bounded sample, rank 0, N=1).
-The process exits non-zero when the inflate round trip or the bit-exactness check fails.
+A plain run does only what the headline needs: it sets up, warms up, times the steps, writes --dump-outputs and prints the
+line, which carries `roofline` (dominant kernel, live HIP-event duration on the library's streams during the timed steps).
+--full adds everything else: `cpu_baseline` (the compiled reference oracle/_ref — or the oracle port where it did not
+travel — on a bounded sample, rank 0, N=1), the byte-for-byte comparison with the reference, the inflate round trip, the
+size against zlib-9, the measured copy bandwidth, the end-to-end and three-jobs figures, the strong-scaling leg at N > 1,
+and, in the default configuration on one GPU, configurations 3, 4 and 5, the synthetic text and the strong-scaling
+projection as child processes. A --full run exits non-zero when a round trip or a bit-exactness check fails.
 """
 import argparse
 import glob
@@ -624,7 +628,7 @@ def prepare_stream_config(args, rank, world):
         flags, bs, size = 2, args.block or 65536, args.size or 100_000_000
         corp, data_note = text_corpus(world, size)
         metric = "input MB/s, gzip 64 KiB max-blocks, enwik8-sized text, bit-exact vs CPU zultra"
-        if getattr(args, "synthetic_leg", False):   # (a leg of the default run: round 1's headline corpus in a process of its own)
+        if getattr(args, "synthetic_leg", False):   # (a leg of the --full run: round 1's headline corpus in a process of its own)
             corp, data_note = SyntheticText(), "round 1's seeded Zipf word stream (tests/corpus.py: text_like_fast): never splits, never meets the chain parse"
             metric = "input MB/s, gzip 64 KiB max-blocks, synthetic text, bit-exact vs CPU zultra"
     elif cfg == 3:
@@ -650,7 +654,7 @@ def prepare_stream_config(args, rank, world):
         lead, shard = corp.shard(rank, size)
     cb = ref_out = check = None
     sample = shard[: min(args.cpu_sample, len(shard))]
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.profile_run:
+    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.profile_run and args.full:
         # what is checked against the reference, byte for byte: the WHOLE shard for configurations 2 and 3 (the stream the timed steps produce), the first
         # 64 MiB of configuration 4's GiB (its reference run would take three minutes of one core) — in a child process, next to everything else; the
         # reference's SPEED is taken on the first --cpu-sample bytes, best of three, with nothing else running
@@ -722,18 +726,21 @@ def run_stream_config(args, env, prep):
         if args.profile_run:
             L.traffic_probe(256 << 20)
             return line, False
-        bw = L.copy_bandwidth(1 << 30, 5)
-        if bw > 0:
-            line["roofline"]["peak_measured"] = round(bw, 1)
-            line["roofline"]["frac_of_measured"] = round(head["roofline"]["achieved"] / bw, 6)
-        framed = frame(L, flags, head["body"].tobytes(), head["checksum"], head["total_in"])
-        ok = inflate_check(flags, framed, shard, head["total_in"])
-        line["inflate_roundtrip_ok"] = ok
-        failed |= not ok
+        if args.full:
+            bw = L.copy_bandwidth(1 << 30, 5)
+            if bw > 0:
+                line["roofline"]["peak_measured"] = round(bw, 1)
+                line["roofline"]["frac_of_measured"] = round(head["roofline"]["achieved"] / bw, 6)
+            framed = frame(L, flags, head["body"].tobytes(), head["checksum"], head["total_in"])
+            ok = inflate_check(flags, framed, shard, head["total_in"])
+            line["inflate_roundtrip_ok"] = ok
+            failed |= not ok
     ctx, d_data = head.pop("ctx"), head.pop("d_data")
     if ctx is not None:
         ctx.close()
     del d_data
+    if not args.full:
+        return line, failed
     if world > 1 and not strong and not args.profile_run:
         # beside the weak-scaling value: the configuration's ONE stream (its own size) cut over the same ranks — what BASELINE.json's metric names
         args.strong_leg = True
@@ -839,6 +846,8 @@ def run_stream_config(args, env, prep):
 def prepare_config1(args, rank, world):
     import corpus
     data = corpus.bootstrap_js()
+    if not args.full:
+        return dict(data=data, cb=None, ref_out=None)
     p = find_file("ZULTRA_BOOTSTRAP", ["bootstrap.min.js"], 48944)   # the README's file (README.md:43: 12 599 B): reported beside the stand-in's known answer
     if p:
         args.readme_bootstrap = np.fromfile(p, dtype=np.uint8)
@@ -848,10 +857,8 @@ def prepare_config1(args, rank, world):
 
 def run_config1(args, env, prep):
     """Plumbing: one small file, raw deflate, default block size; known answer from the compiled reference (tests/golden)."""
-    import golden_util
     L = env["L"]
-    data, cb, ref_out = prep["data"], prep["cb"], prep["ref_out"]
-    case_raw, case_gz = golden_util.stream_case("bootstrap_raw_default"), golden_util.stream_case("bootstrap_gzip_default")
+    data = prep["data"]
     out = L.memory_compress(data, 0, 0)
     for _ in range(args.warmup):
         L.memory_compress(data, 0, 0)
@@ -860,6 +867,16 @@ def run_config1(args, env, prep):
         out = L.memory_compress(data, 0, 0)
     dt = (time.perf_counter() - t0) / args.steps
     env["outputs"] = {"raw_deflate": np.frombuffer(out, dtype=np.uint8)}
+    line = {"metric": "input MB/s, bootstrap.min.js raw deflate, one max-block, known answer", "value": round(len(data) / dt / 1e6, 3), "unit": "MB/s",
+            "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt * 1e3, 3), "higher_is_better": True, "scaling": "weak",
+            "vs_baseline": None, "dtype": "u8/int32", "data": "real",
+            "config": {"workload": "config 1: the image's bootstrap.min.js v3.4.1 (39 680 B; the README's 48 944-byte file is absent), raw deflate, default block size, through zultra_memory_compress (host buffer, PCIe-inclusive: a single latency-bound call)"},
+            "compressed_bytes": len(out)}
+    if not args.full:
+        return line, False
+    import golden_util
+    cb, ref_out = prep["cb"], prep["ref_out"]
+    case_raw, case_gz = golden_util.stream_case("bootstrap_raw_default"), golden_util.stream_case("bootstrap_gzip_default")
     gz = L.memory_compress(data, 2, 0)
     ok = out == case_raw["out"] and gz == case_gz["out"] and out == ref_out and zlib.decompress(out, -15) == data.tobytes()
     ctx = L.context(0, 1)
@@ -871,15 +888,11 @@ def run_config1(args, env, prep):
     nl = 4 if dom in ("parse_ms", "build_ms") else 1
     achieved = (len(data) + len(out)) / (kern[dom] / nl * 1e-3) / 1e9
     ctx.close()
-    line = {"metric": "input MB/s, bootstrap.min.js raw deflate, one max-block, known answer", "value": round(len(data) / dt / 1e6, 3), "unit": "MB/s",
-            "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt * 1e3, 3), "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "u8/int32", "data": "real",
-            "config": {"workload": "config 1: the image's bootstrap.min.js v3.4.1 (39 680 B; the README's 48 944-byte file is absent), raw deflate, default block size, through zultra_memory_compress (host buffer, PCIe-inclusive: a single latency-bound call)"},
-            "compressed_bytes": len(out), "expected_bytes_raw": case_raw["out_len"], "gzip_bytes": len(gz), "expected_bytes_gzip": case_gz["out_len"],
-            "known_answer_ok": bool(ok), "device_ms": {k: round(v, 3) for k, v in kern.items()},
-            "roofline": {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 5), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 8),
-                         "traffic": None, "launch_ms": round(kern[dom] / nl, 3), "launches_per_step": nl},
-            "cpu_baseline": cb}
+    line.update({"expected_bytes_raw": case_raw["out_len"], "gzip_bytes": len(gz), "expected_bytes_gzip": case_gz["out_len"],
+                 "known_answer_ok": bool(ok), "device_ms": {k: round(v, 3) for k, v in kern.items()},
+                 "roofline": {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 5), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 8),
+                              "traffic": None, "launch_ms": round(kern[dom] / nl, 3), "launches_per_step": nl},
+                 "cpu_baseline": cb})
     if getattr(args, "readme_bootstrap", None) is not None:
         rb = L.memory_compress(args.readme_bootstrap, 0, 0)
         line["readme_size_check"] = {"readme_bytes": 12599, "raw_deflate_default_block_bytes": len(rb), "equal": bool(len(rb) == 12599)}
@@ -892,7 +905,7 @@ def prepare_config5(args, rank, world):
     host = corpus.json_files(rank * nfiles, nfiles, size)
     cb = digest = None
     ncpu, per = min(nfiles, args.batch, args.cpu_check_files), 0   # files compared with the reference: inside the first device batch
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.profile_run:
+    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.profile_run and args.full:
         cb, digest, per = cpu_baseline_files(host[: ncpu * size], size, 2, args.cpu_files)   # forks: must precede any GPU call of this process
     return dict(host=host, cb=cb, digest=digest, ncpu=ncpu, per=per)
 
@@ -965,28 +978,14 @@ def run_config5(args, env, prep):
         tt = torch.tensor([dt], dtype=torch.float64, device=device)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
-    step(collect=True)
+    if args.full or args.dump_outputs:
+        step(collect=True)   # (outside the timed region: the batches --dump-outputs writes and --full checks)
     line, failed = None, False
     if rank == 0:
-        # checks on the first batch: every file framed as gzip inflates to its input; the first files equal the CPU reference
-        fo, stream, crcs = keep["fo"], keep["stream"], keep["crcs"]
         if args.dump_outputs:
             bt = [keep["batches"][b] for b in range(nb)]
-            env["outputs"] = {"first_batch_stream": stream, "file_offsets_by_batch": np.concatenate([x[0] for x in bt]), "file_crc32": np.concatenate([x[1] for x in bt]),
+            env["outputs"] = {"first_batch_stream": keep["stream"], "file_offsets_by_batch": np.concatenate([x[0] for x in bt]), "file_crc32": np.concatenate([x[1] for x in bt]),
                               "batch_stream_crc32_and_bytes": np.array([[x[2], x[3]] for x in bt], dtype=np.int64)}
-        k0 = min(batch, nfiles)
-        hdr = bytes([0x1f, 0x8b, 8, 0, 0, 0, 0, 0, 2, 255])
-        per = prep["per"] or ncpu or 1
-        hs = [hashlib.sha256() for _ in range((ncpu + per - 1) // per)]   # one digest per shard of the reference's worker pool (cpu_baseline_files)
-        ok = True
-        for k in range(min(k0, max(ncpu, 2048))):
-            raw = stream[int(fo[k]):int(fo[k + 1])].tobytes()
-            gz = hdr + raw + int(L.crc32_append(0, crcs[k], size)).to_bytes(4, "little") + int(size).to_bytes(4, "little")
-            if k < ncpu:
-                hs[k // per].update(gz)
-            if k < 2048 and zlib.decompress(gz, 31) != host[k * size:(k + 1) * size].tobytes():
-                ok = False
-        failed |= not ok
         avg_graph = float(np.mean([t["encode_ms"] for t in timings]))
         avg_stitch = float(np.mean([t["stitch_ms"] for t in timings]))
         in_b, out_b = min(batch, nfiles) * size, out_bytes / nb
@@ -999,10 +998,26 @@ def run_config5(args, env, prep):
                     "one device context" if nctx == 1 else "%d device contexts take alternate batches, one host thread each" % nctx), "contexts": nctx},
                 "rccl_ranks_seen": env["ranks_seen"], "input_MBps": round(world * nfiles * size / (dt / args.steps) / 1e6, 2),
                 "ratio": round(out_bytes / (nfiles * size), 4), "graph_ms_per_batch": round(avg_graph, 3), "stitch_ms_per_batch": round(avg_stitch, 3),
-                "gzip_roundtrip_ok_first_files": bool(ok),
                 "roofline": {"bound": "hbm", "kernel": "hipGraph of stages 1-3 (one replay per batch)", "achieved": round(achieved, 4), "peak": HBM_PEAK_GBS,
                              "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 6), "traffic": committed_traffic("graph", 5)[0], "traffic_source": committed_traffic("graph", 5)[1], "traffic_stale": committed_traffic("graph", 5)[2],
                              "algorithmic_bytes_per_launch": int(in_b + out_b), "launch_ms": round(avg_graph, 3), "launches_per_step": nb}}
+        if args.full:
+            # checks on the first batch: every file framed as gzip inflates to its input; the first files equal the CPU reference
+            fo, stream, crcs = keep["fo"], keep["stream"], keep["crcs"]
+            k0 = min(batch, nfiles)
+            hdr = bytes([0x1f, 0x8b, 8, 0, 0, 0, 0, 0, 2, 255])
+            per = prep["per"] or ncpu or 1
+            hs = [hashlib.sha256() for _ in range((ncpu + per - 1) // per)]   # one digest per shard of the reference's worker pool (cpu_baseline_files)
+            ok = True
+            for k in range(min(k0, max(ncpu, 2048))):
+                raw = stream[int(fo[k]):int(fo[k + 1])].tobytes()
+                gz = hdr + raw + int(L.crc32_append(0, crcs[k], size)).to_bytes(4, "little") + int(size).to_bytes(4, "little")
+                if k < ncpu:
+                    hs[k // per].update(gz)
+                if k < 2048 and zlib.decompress(gz, 31) != host[k * size:(k + 1) * size].tobytes():
+                    ok = False
+            line["gzip_roundtrip_ok_first_files"] = bool(ok)
+            failed |= not ok
         if args.profile_run:
             L.traffic_probe(256 << 20)
         elif cb is not None:
@@ -1019,8 +1034,8 @@ def run_config5(args, env, prep):
 
 # ---------------------------------------------------------------------------------------------------------------------
 def run_other_configs(args):
-    """The default run (configuration 2 on one GPU) also measures configurations 3, 4 and 5, bounded so that the whole command stays
-    within a few minutes: each as a child process of its own (started before this process touches the GPU), its JSON line condensed."""
+    """A --full run of the default configuration on one GPU also measures configurations 3, 4 and 5, bounded so that the whole command stays
+    within a few minutes: each as a --full child process of its own (started before this process touches the GPU), its JSON line condensed."""
     # (each leg compares its stream with the CPU reference's in full — configuration 4: the first 64 MiB of its GiB, configuration 5: its first 65 536 files —
     # and times the reference on a smaller sample: ~25 s each)
     legs = {3: ["--cpu-sample", str(8 << 20)], 4: ["--cpu-sample", str(4 << 20)], 5: ["--files", "1000000", "--cpu-files", "2048"]}
@@ -1033,7 +1048,7 @@ def run_other_configs(args):
     for cfg, extra in legs.items():
         cmd = [sys.executable, os.path.abspath(__file__), "--config", "2" if cfg in ("synthetic_text", "strong_scaling_projection") else str(cfg), "--gpus", "1",
                "--steps", "10" if cfg == "synthetic_text" else "5" if cfg == "strong_scaling_projection" else "2",
-               "--warmup", "3" if cfg in ("synthetic_text", "strong_scaling_projection") else "1", "--leg"] + extra
+               "--warmup", "3" if cfg in ("synthetic_text", "strong_scaling_projection") else "1", "--leg", "--full"] + extra
         t0 = time.perf_counter()
         try:
             r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
@@ -1084,17 +1099,21 @@ def main():
     ap.add_argument("--cpu-files", type=int, default=4096, help="config 5: files the CPU reference is timed on (one core)")
     ap.add_argument("--cpu-check-files", type=int, default=65536, help="config 5: files compared with the CPU reference (all host cores)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-synthetic", action="store_true", help="default run: skip the synthetic-text leg")
-    ap.add_argument("--synthetic-leg", action="store_true", help="(internal) configuration 2's settings on round 1's synthetic text: a leg of the default run")
-    ap.add_argument("--no-other-configs", action="store_true", help="default run (config 2, one GPU): skip the legs of configurations 3, 4 and 5")
+    ap.add_argument("--no-synthetic", action="store_true", help="--full run of config 2 on one GPU: skip the synthetic-text leg")
+    ap.add_argument("--synthetic-leg", action="store_true", help="(internal) configuration 2's settings on round 1's synthetic text: a leg of the --full run")
+    ap.add_argument("--no-other-configs", action="store_true", help="--full run of config 2 on one GPU: skip the legs of configurations 3, 4 and 5")
     ap.add_argument("--leg", action="store_true", help="(internal) this process is one of those legs: bounded extras")
     ap.add_argument("--projection", action="store_true", help="(internal; --config 2 --gpus 1 --scaling strong) strong-scaling PROJECTION from one GPU: every shard of the configuration's "
-                                                               "one stream cut over N = 2, 4, 8 ranks, timed on this GPU one after the other (a leg of the default run)")
+                                                               "one stream cut over N = 2, 4, 8 ranks, timed on this GPU one after the other (a leg of the --full run)")
     ap.add_argument("--profile-run", action="store_true",
                     help="for rocprofv3 passes: only the steps (no round-trip / ratio / CPU extras that would add dispatches), then the PMC calibration probe")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32/float64, at most 64 MB in all; config 5: every batch's file offsets "
                          "and CRCs and its stream's CRC-32, and the first batch's stream, from one more pass over the same inputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, everything else the benchmark measures and checks: CPU reference baseline, byte-for-byte comparison with "
+                         "the reference, round trips, size vs zlib-9, measured copy bandwidth, end-to-end and three-jobs figures, the strong-scaling leg "
+                         "at N > 1; config 2 on one GPU: the legs of configurations 3, 4 and 5, synthetic text and the strong-scaling projection")
     args = ap.parse_args()
 
     have_launcher = "RANK" in os.environ and "WORLD_SIZE" in os.environ
@@ -1118,7 +1137,7 @@ def main():
 
     # ---- the other configurations' legs, as child processes, before this process touches a GPU ---------------------------------------
     other = None
-    if args.config == 2 and world == 1 and not have_launcher and not args.profile_run and not args.leg and not args.no_other_configs:
+    if args.full and args.config == 2 and world == 1 and not have_launcher and not args.profile_run and not args.leg and not args.no_other_configs:
         other = run_other_configs(args)
 
     # ---- CPU side first: corpus generation and the CPU reference timing (config 5 forks worker processes) -------------------

@@ -613,7 +613,7 @@ def test_bench_config1_known_answer():
     if not os.path.exists(corpus.BOOTSTRAP_JS):
         pytest.skip("bootstrap.min.js is not in this image")
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--config", "1"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--config", "1", "--full"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert p.returncode == 0, p.stderr.decode()[-2000:]
     line = json.loads(p.stdout.decode().strip().splitlines()[-1])
     assert line["known_answer_ok"] and line["compressed_bytes"] == 10523 and line["gzip_bytes"] == 10541

@@ -490,3 +490,75 @@ def test_stream_memory_comes_from_the_callers_allocator(emu, oracle):
     s.end()
     assert not live
 
+
+
+# ---- max-block sizes that are not powers of two, stored pieces, preset dictionaries (the GPU suite covers the sizes and paths in full) ---
+# (mostly noise and byte runs with a little text: the emulator takes about ten seconds for 32 KiB of noise, fifty for 32 KiB of text)
+
+def _cheap(n, seed, text=3000):
+    """n bytes: `text` bytes of text, then noise and byte runs."""
+    d = corpus.noise(n, seed)
+    d[:min(n, text)] = corpus.text_like(min(n, text), seed)
+    if n > text + 12000:
+        d[text + 4000:text + 12000] = corpus.constant(8000, 32 + seed % 64)
+    return d
+
+
+def test_odd_max_block_stream_of_two_blocks_and_a_byte(emu, checker):
+    # 32769: the smallest max-block that is not the clamp bound; two full blocks (the second repeats text of the first from 32 KiB back)
+    # and a last block of one byte, gzip framing
+    bs = 32769
+    d = _cheap(2 * bs + 1, 21)
+    d[bs + 100:bs + 2100] = d[500:2500]
+    want = checker.memory_compress(d, 2, bs)
+    assert emu.memory_compress(d, 2, bs) == want
+    assert zlib.decompress(want, 31) == d.tobytes()
+
+
+def test_stored_fallback_cuts_pieces_of_65535_bytes(emu, checker):
+    # a max-block of 70001 bytes of noise is stored as pieces of 65535 and 4466 bytes (libzultra.c:350-397), then a block of 5 bytes
+    bs = 70001
+    d = np.concatenate([corpus.noise(bs, 22), corpus.text_like(5, 22)])
+    want = checker.memory_compress(d, 1, bs)
+    assert b"\xff\xff\x00\x00" in want          # (LEN = 65535, NLEN)
+    assert emu.memory_compress(d, 1, bs) == want
+
+
+@pytest.mark.parametrize("dsize,flags", [(1, 0), (3, 1), (32768, 2)])
+def test_preset_dictionaries_of_a_few_bytes_and_of_32_kib(emu, checker, dsize, flags):
+    """The dictionary is the first max-block's history: 1 and 3 bytes (windows whose history is shorter than a match), and a full 32 KiB
+    whose last bytes the input repeats."""
+    dic = _cheap(dsize, 23, text=2000) if dsize > 3 else corpus.text_like(dsize, 23)
+    d = corpus.text_like(4000, 24)
+    d[:1500] = np.resize(dic[-1500:], 1500)
+    want = checker.memory_compress(d, flags, 32768, dic)
+    assert emu.memory_compress(d, flags, 32768, dic) == want
+    if flags != 2:
+        assert zlib.decompressobj(15 if flags == 1 else -15, zdict=dic.tobytes()).decompress(want) == d.tobytes()
+
+
+def test_dictionary_over_two_device_lanes(emu, checker, monkeypatch):
+    """ZULTRA_HIP_DEVICES=0,0 over five max-blocks (two lanes from four on): jobs of three and two max-blocks, the first job's history is the
+    preset dictionary, the second's the 32 KiB of input in front of it."""
+    bs = 32768
+    dic = corpus.text_like(3000, 25)
+    d = _cheap(4 * bs + 300, 26)
+    d[:2000] = dic[-2000:]
+    d[3 * bs:3 * bs + 2000] = d[3 * bs - 5000:3 * bs - 3000]
+    want = checker.memory_compress(d, 1, bs, dic)
+    monkeypatch.setenv("ZULTRA_HIP_DEVICES", "0,0")
+    assert emu.memory_compress(d, 1, bs, dic) == want
+
+
+def test_chunked_stream_with_a_dictionary(emu, checker):
+    # zultra_stream_set_dictionary, then two max-blocks fed in 16 KiB chunks; a second dictionary is refused (libzultra.c:177-190)
+    dic = corpus.text_like(3, 27)
+    d = _cheap(36000, 28)
+    s = emu.stream(2, 32768)
+    assert s.set_dictionary(dic) == 0 and s.set_dictionary(d[:10]) == -5
+    out = bytearray()
+    for pos in range(0, len(d), 16384):
+        st, b = s.compress(d[pos:pos + 16384], finalize=(pos + 16384 >= len(d)), out_chunk=5000)
+        out += b
+    s.end()
+    assert st == 1 and bytes(out) == checker.memory_compress(d, 2, 32768, dic)

@@ -902,3 +902,249 @@ def test_stream_memory_comes_from_the_callers_allocator(gpu, checker):
     assert len(log) == n_init                           # compressing allocates nothing more on the host side of the stream
     s.end()
     assert not live
+
+
+# ---- max-block sizes that are not powers of two, preset dictionaries, batch edges --------------------------------------------
+
+def _clamped(bs):
+    """The max-block size the reference works with for a caller's `bs` (libzultra.c:87-92: 0 -> 1 MiB, then [32768, 2097152])."""
+    return min(max(bs or 1 << 20, 32768), 2 << 20)
+
+
+def _stretches(n, seed, noise_at=()):
+    """n bytes of text with stretches of byte runs and noise of a few KiB to 30 KiB in between; noise over each [lo, hi) of noise_at."""
+    rs = np.random.RandomState(seed)
+    d = corpus.text_like_fast(n, seed)
+    at = int(rs.randint(0, 20000))
+    while at < n:
+        m = min(int(rs.randint(2000, 30000)), n - at)
+        d[at:at + m] = corpus.indented(m, seed + at) if rs.randint(0, 2) else corpus.noise(m, seed + at)
+        at += m + int(rs.randint(10000, 60000))
+    for lo, hi in noise_at:
+        lo, hi = max(0, lo), min(n, hi)
+        if hi > lo:
+            d[lo:hi] = corpus.noise(hi - lo, seed + lo)
+    return d
+
+
+@pytest.mark.parametrize("case", [
+    ("odd40000", lambda: corpus.text_like(72768, 41), 32768, 40000, 40000),
+    ("odd65537_hist", lambda: corpus.text_like(98305, 42), 32768, 65537, 65537),
+    ("lds_cut_98305", lambda: np.concatenate([corpus.text_like(50000, 43), corpus.indented(48305, 6)]), 0, 98305, 98305),
+    ("lds_cut_100003", lambda: np.concatenate([corpus.indented(40000, 7), corpus.text_like(92771, 44)]), 32768, 100003, 100003),
+    ("byte_runs_odd", lambda: corpus.indented(32768 + 65537, 14), 32768, 65537, 65537),
+    ("noise_odd", lambda: corpus.noise(65537, 15), 0, 65537, 65537),
+], ids=lambda c: c[0])
+def test_stages_at_odd_max_block_sizes(gpu, checker, case):
+    """Max-blocks of sizes that are not powers of two (the reference takes any size and clamps it, libzultra.c:87-92): a window of
+    32768 + 40000, 65537 with history, byte runs and noise at 65537, and windows of 98305 and 32768 + 100003 bytes, just above the
+    matchfinder's 96 KiB LDS window (two segments). Every stage equals the checker's."""
+    name, gen, prev, n, bs = case
+    check_window(gpu, checker, gen(), prev, n, max_block=bs, tag=name)
+
+
+def test_odd_near_two_mib_max_block_of_real_text_stage_by_stage(gpu, checker):
+    # 2097151 bytes: one byte short of the largest max-block, so no chunk, segment or tile count of a power of two comes out even
+    d = corpus.real_text(1_000_000 + 32768 + 2097151)[1_000_000:]
+    check_window(gpu, checker, d, 32768, 2097151, max_block=2097151, tag="pysrc_2097151")
+
+
+# input lengths for the largest sizes: one to three streams each (the others take k * bs - 1, k * bs and k * bs + 1 for k = 1..3, and
+# last max-blocks of 2 and 3 bytes)
+_ODD_STREAM_LENGTHS = {
+    2097151: (2097152, 2 * 2097151 - 1),
+    2097152: (2 * 2097152 + 2,),
+    2097153: (2097152 + 3,),
+    0xFFFFFFFF: (2097152,),
+    1048577: (1048576, 2 * 1048577 + 1, 3 * 1048577 + 3),
+}
+
+
+@pytest.mark.parametrize("bs", [1, 32767, 32768, 32769, 40000, 65535, 65537, 100003, 131071, 1048577, 2097151, 2097152, 2097153, 0xFFFFFFFF])
+def test_streams_at_odd_and_clamped_max_block_sizes(gpu, checker, bs):
+    """Whole streams in the three framings at max-block sizes below, at and above the clamp bounds and at odd sizes between them, with
+    inputs that end one byte before, at and one byte after a multiple of the max-block, and last max-blocks of 1, 2 and 3 bytes: text,
+    byte runs and noise. From 131071 on, 140 000 bytes of noise straddle the first max-block boundary, so that the stored fallback cuts
+    the bodies on both sides into pieces of 65535 bytes (libzultra.c:350-397). zultra_memory_bound equals the reference's at every size."""
+    B = _clamped(bs)
+    if bs in _ODD_STREAM_LENGTHS:
+        lengths = _ODD_STREAM_LENGTHS[bs]
+    else:
+        lengths = sorted({k * x + e for x in {bs, B} for k in (1, 2, 3) for e in (-1, 0, 1)} | {2 * B + 2, 2 * B + 3})
+    noise = [(B - 70000, B + 70000)] if B >= 131071 else [(B - B // 4, B + B // 4)]
+    base = _stretches(max(lengths), bs & 0xffff, noise)
+    for i, n in enumerate(lengths):
+        d = base[:n]
+        flags = (i + bs) % 3
+        want = checker.memory_compress(d, flags, bs)
+        got = gpu.memory_compress(d, flags, bs)
+        assert got == want, (bs, n, flags, None if got is None else len(got), None if want is None else len(want))
+        if B >= 131071 and n > B + 70000:
+            assert b"\xff\xff\x00\x00" in want, (bs, n)   # (LEN = 65535, NLEN: a stored piece of full length)
+    for n in (0, 1, B - 1, B, B + 1, 3 * B + 1, 10 ** 9, (1 << 32) + 5):
+        for flags in (0, 1, 2):
+            assert gpu.memory_bound(n, flags, bs) == checker.memory_bound(n, flags, bs), (bs, n, flags)
+
+
+def _dict_case(dsize, n, seed):
+    """A dictionary of dsize bytes and an input of n bytes that takes matches from it: text from one word stream, the input's first
+    stretches repeating pieces of the dictionary's last 32 KiB (and of what lies before them, when there is more)."""
+    t = _stretches(dsize + n, seed)
+    dic, d = t[:dsize].copy(), t[dsize:].copy()
+    for k, lo in enumerate((max(0, dsize - 32768), max(0, dsize - 2000), max(0, dsize - 40000))):
+        m = min(1500, dsize - lo, n - 3000 * k)
+        if m > 0:
+            d[3000 * k:3000 * k + m] = dic[lo:lo + m]
+    return dic, d
+
+
+def _dict_want(checker, d, flags, bs, dic):
+    """The checker's stream for `d` behind the preset dictionary `dic`. Above 32 KiB the reference copies the whole dictionary in front of
+    its 32 KiB history buffer (libzultra.c:250-253, undefined behaviour); the library keeps the dictionary's last 32768 bytes as the history
+    and checksums the whole dictionary into the zlib header's DICTID (RFC 1950: the Adler-32 of the dictionary the caller gave)."""
+    if len(dic) <= 32768:
+        return checker.memory_compress(d, flags, bs, dic)
+    want = checker.memory_compress(d, flags, bs, dic[-32768:])
+    if flags == 1:
+        want = want[:2] + zlib.adler32(dic.tobytes()).to_bytes(4, "big") + want[6:]
+    return want
+
+
+def _stream_dict(gpu, d, flags, bs, dic, chunk):
+    s = gpu.stream(flags, bs)
+    assert s.set_dictionary(dic) == 0
+    out = bytearray()
+    pos, st = 0, 0
+    while True:
+        part = d[pos:pos + chunk]
+        pos += len(part)
+        st, b = s.compress(part, finalize=(pos >= len(d)), out_chunk=16384)
+        out += b
+        if pos >= len(d):
+            break
+    assert st == 1 and s.total_in == len(d)
+    s.end()
+    return bytes(out)
+
+
+@pytest.mark.parametrize("dsize", [1, 2, 3, 257, 32767, 32768, 40000, 70000])
+def test_preset_dictionaries_vs_oracle(gpu, checker, monkeypatch, dsize):
+    """A preset dictionary is the history of the first max-block only (libzultra.c:250-253,406-412). Dictionaries of 1 .. 32768 bytes and
+    above, raw / zlib / gzip framing, an input shorter than one max-block and one of five max-blocks (32 KiB), through zultra_memory_compress_dict
+    (one lane; through the stream API with ZULTRA_HIP_MEMORY_LANES=0; two device lanes with ZULTRA_HIP_DEVICES=0,0, whose first job takes its
+    history from the dictionary) and through zultra_stream_set_dictionary with the input in 16 KiB chunks and in one go: the checker's bytes.
+
+    Dictionaries of more than 32 KiB: the reference's behaviour is undefined (it copies the whole dictionary in front of its buffer). The
+    library's, pinned here: the last 32768 bytes are the history — raw and gzip streams equal the reference's with those bytes as the
+    dictionary — and a zlib header's DICTID is the Adler-32 of the whole dictionary, so zlib inflates the stream with the whole dictionary."""
+    bs = 32768
+    for n, seed in ((20000, 100 + dsize), (4 * bs + 3001, 200 + dsize)):
+        dic, d = _dict_case(dsize, n, seed)
+        for flags in (0, 1, 2):
+            want = _dict_want(checker, d, flags, bs, dic)
+            assert want is not None
+            got = {"memory": gpu.memory_compress(d, flags, bs, dic),
+                   "stream_16k": _stream_dict(gpu, d, flags, bs, dic, 16384),
+                   "stream_whole": _stream_dict(gpu, d, flags, bs, dic, len(d))}
+            monkeypatch.setenv("ZULTRA_HIP_MEMORY_LANES", "0")
+            got["memory_via_stream"] = gpu.memory_compress(d, flags, bs, dic)
+            monkeypatch.delenv("ZULTRA_HIP_MEMORY_LANES")
+            monkeypatch.setenv("ZULTRA_HIP_DEVICES", "0,0")
+            got["two_lanes"] = gpu.memory_compress(d, flags, bs, dic)
+            monkeypatch.delenv("ZULTRA_HIP_DEVICES")
+            for path, g in got.items():
+                assert g == want, (dsize, n, flags, path, None if g is None else len(g), len(want))
+            if flags != 2:   # (a gzip member carries no dictionary id: nothing outside can inflate it)
+                dec = zlib.decompressobj(15 if flags == 1 else -15, zdict=dic.tobytes())
+                assert dec.decompress(want) == d.tobytes() and dec.eof
+    # an empty input never finalises, dictionary or not (libzultra.c:275)
+    assert gpu.memory_compress(d[:0], 1, bs, dic) is None and checker.memory_compress(d[:0], 1, bs, dic[-32768:]) is None
+
+
+def test_set_dictionary_only_before_compression_starts(gpu, checker):
+    """zultra_stream_set_dictionary succeeds only while the stream's state is untouched (libzultra.c:177-190): once, before the first
+    compress call. A second call and a call after compression started fail with ZULTRA_ERROR_COMPRESSION; the first dictionary stays."""
+    dic, d = _dict_case(3000, 50000, 7)
+    s = gpu.stream(1, 40000)
+    assert s.set_dictionary(dic) == 0
+    assert s.set_dictionary(d[:100]) == -5
+    st, out = s.compress(d[:20000], False)
+    assert st == 0 and s.set_dictionary(d[:100]) == -5
+    st, out2 = s.compress(d[20000:], True)
+    s.end()
+    assert st == 1 and out + out2 == checker.memory_compress(d, 1, 40000, dic)
+
+
+@pytest.mark.parametrize("env,batch", [("ZULTRA_HIP_BATCH_BLOCKS", 2), ("ZULTRA_HIP_BATCH_BLOCKS", 3), ("ZULTRA_HIP_FLUSH_BYTES", 1)])
+def test_streaming_batches_that_end_at_their_edges(gpu, checker, monkeypatch, env, batch):
+    """The stream layer stages max-blocks until its staging area (ZULTRA_HIP_BATCH_BLOCKS max-blocks) is full or ZULTRA_HIP_FLUSH_BYTES of full
+    blocks wait: at a max-block size of 40000, inputs that fill one batch exactly, miss it by a byte or overrun it by one, and two batches and
+    a byte — fed in 16 KiB chunks and in one go, with and without a dictionary. The bytes are the reference's (which publishes every max-block)."""
+    bs = 40000
+    monkeypatch.setenv("ZULTRA_HIP_CACHE", "0")   # (the staging size is fixed when a stream's context is acquired)
+    gpu.L.zultra_release_cached_contexts()
+    monkeypatch.setenv(env, str(batch * bs) if env == "ZULTRA_HIP_FLUSH_BYTES" else str(batch))
+    base = _stretches(2 * batch * bs + 1, 300 + batch, [(bs - 15000, bs + 15000)])
+    dic = corpus.text_like_fast(5000, 301)
+    for i, n in enumerate((batch * bs - 1, batch * bs, batch * bs + 1, 2 * batch * bs + 1)):
+        d = base[:n]
+        flags = i % 3
+        for with_dict in (False, True):
+            want = checker.memory_compress(d, flags, bs, dic if with_dict else None)
+            for chunk in (16384, n):
+                s = gpu.stream(flags, bs)
+                if with_dict:
+                    assert s.set_dictionary(dic) == 0
+                out = bytearray()
+                pos, st = 0, 0
+                while pos < n:
+                    part = d[pos:pos + chunk]
+                    pos += len(part)
+                    st, b = s.compress(part, finalize=(pos >= n), out_chunk=50000)
+                    out += b
+                assert st == 1 and s.total_in == n
+                s.end()
+                assert bytes(out) == want, (env, batch, n, flags, with_dict, chunk)
+
+
+def test_files_mode_at_declared_sizes_that_are_not_powers_of_two(gpu, checker):
+    """Files contexts declared for 5000, 6143 and 777 bytes (the device rounds its slots up to 64): inputs that fill the declared size
+    exactly, miss it by a byte and anything smaller, each its own raw stream equal to the checker's; one byte more is refused. A declared
+    size of 8192 or more is refused at creation (the splitter may cut such inputs: the block interface takes them)."""
+    import zultra_amd
+    with pytest.raises(zultra_amd.ZultraError):
+        gpu.files_context(12289, 4)
+    for declared, seed in ((5000, 3), (6143, 4), (777, 5)):
+        rs = np.random.RandomState(seed)
+        sizes = [declared] * 9 + [declared - 1, 1, 2, 3] + [int(x) for x in rs.randint(1, declared + 1, size=40)]
+        makers = (corpus.json_like, corpus.text_like, corpus.noise, corpus.indented)
+        files = [makers[k % 4](n, 10 * seed + k) for k, n in enumerate(sizes)]
+        ctx = gpu.files_context(declared, len(files))
+        try:
+            fo = ctx.compress_files(np.concatenate(files), np.cumsum([0] + sizes[:-1]), sizes)
+            stream = ctx.stream_read(int(fo[-1]))
+            for k, f in enumerate(files):
+                assert stream[int(fo[k]):int(fo[k + 1])].tobytes() == checker.memory_compress(f, 0, 32768), (declared, k, sizes[k])
+            with pytest.raises(zultra_amd.ZultraError):
+                ctx.compress_files(np.concatenate([files[0], files[1]]), [0], [declared + 1])
+        finally:
+            ctx.close()
+
+
+def test_staggered_runs_at_an_odd_max_block_size(gpu, checker, monkeypatch):
+    """A batch of 131 max-blocks of 100003 bytes cut into three staggered runs (zh_plan_runs: run boundaries at block counts, not at
+    multiples of 4 MiB), with noise straddling both run boundaries: the bytes are the checker's, and the device did make three runs."""
+    bs, nb = 100003, 131
+    n = nb * bs - 7
+    cuts = [(nb // 3) * bs, (nb - nb // 3) * bs]
+    d = _stretches(n, 17, [(c - 70000, c + 70000) for c in cuts])
+    monkeypatch.setenv("ZULTRA_HIP_CACHE", "0")   # (the number of runs is fixed when a context is created)
+    gpu.L.zultra_release_cached_contexts()
+    monkeypatch.setenv("ZULTRA_HIP_STREAMS", "3")
+    assert gpu.memory_compress(d, 2, bs) == checker.memory_compress(d, 2, bs)
+    ctx = gpu.context(bs, nb)
+    try:
+        ctx.compress_blocks(d, [(b * bs - (32768 if b else 0), 32768 if b else 0, min(bs, n - b * bs)) for b in range(nb)])
+        assert ctx.stats()["runs"] == 3, ctx.stats()
+    finally:
+        ctx.close()

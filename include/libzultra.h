@@ -128,6 +128,15 @@ int zultra_set_devices(const int *pDevices, int nDevices);
  * two); with the environment variable ZULTRA_HIP_CACHE=0 none is ever kept and zultra_stream_end releases the device memory
  * itself. Returns the number of contexts destroyed. */
 int zultra_release_cached_contexts(void);
+/* Verification (default off; nEnable != 0 or the environment variable ZULTRA_HIP_VERIFY=1 turns it on): every batch the library stitches on a
+ * device is inflated there and compared with its input before its bytes are handed out (include/zultra_hip.h: zultra_hip_verify_device) —
+ * the stream API, zultra_memory_compress, zultra_memory_compress_dict, every shard of a call spread over several contexts. On a mismatch
+ * zultra_stream_compress returns ZULTRA_ERROR_COMPRESSION, the memory calls return (size_t)-1, and one line with the report goes to stderr.
+ * The check covers the deflate body, not the framing's header and footer. With ZULTRA_HIP_HOST_STITCH=1 the batch is stitched on the device
+ * as well, for the check, at the phase the host stitcher starts from. Off, the library launches nothing and reads nothing for it. */
+void zultra_set_verify(int nEnable);
+/* Input bytes verified that way in this process since the library was loaded: how a caller knows the check ran over everything. */
+unsigned long long zultra_verified_bytes(void);
 
 #ifdef __cplusplus
 }

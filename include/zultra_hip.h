@@ -199,6 +199,35 @@ int zultra_hip_stitch_with_batch(zultra_hip_ctx_t *ctx, int enable, uint32_t pha
 int zultra_hip_stitch_phase_table(zultra_hip_ctx_t *ctx, uint64_t *end_bits /* 8 */, uint32_t *failed_mask);   /* (rewrites the last stitch's items and report: stitch again before reading the stream) */
 const void *zultra_hip_stream_device(const zultra_hip_ctx_t *ctx);
 int zultra_hip_stream_read(zultra_hip_ctx_t *ctx, void *out, size_t offset, size_t nbytes);
+/* Counterpart of zultra_hip_stream_read: overwrite bytes of the stream buffer (diagnostics; what the verify tests corrupt a stream with). */
+int zultra_hip_stream_write(zultra_hip_ctx_t *ctx, const void *in, size_t offset, size_t nbytes);
+
+/*
+ * Verification: the device inflates the stream it has just assembled and compares it with the batch's input — one wave per
+ * sub-block, each from its own first header bit; a literal must equal the input byte, a match must copy what the input has, every sub-block's
+ * decode must end where the next one starts, BFINAL must sit on the stream's last block and nowhere else. Any content of the stream buffer
+ * gives a verdict.
+ */
+#define ZULTRA_HIP_VERIFY_OK 0          /* reasons: 1 header, 2 code lengths, 3 symbol, 4 distance, 5 literal differs, 6 match differs,
+                                           7 stored LEN/NLEN, 8 stored bytes differ, 9 size overrun, 10 end bit, 11 BFINAL, 12 stream end */
+typedef struct zultra_hip_verify_s {
+   uint32_t bad_subblocks;   /* sub-blocks that did not verify */
+   uint32_t first_bad;       /* stream-order index of the first, 0xFFFFFFFF if none */
+   uint32_t reason;          /* of first_bad */
+   uint32_t block;           /* its max-block */
+   uint64_t input_off;       /* offset inside that max-block where it went wrong */
+   uint64_t stream_bit;      /* bit of the stream buffer the decoder had reached */
+   uint64_t verified_bytes;  /* input bytes of the sub-blocks that verified */
+} zultra_hip_verify_t;
+
+/* Inflate-and-compare of the stream the last stitch left in the context's stream buffer (zultra_hip_stitch_device, the stitch armed with
+ * zultra_hip_stitch_with_batch, zultra_hip_compress_files / zultra_hip_stitch_files) against the batch's input. 0 = every sub-block
+ * verified, 1 = report->bad_subblocks > 0, -1 = HIP error or nothing stitched (a stitch that reported failure, a phase-table call since).
+ * The input is read where the batch's kernels read it: the context's own copy for data_on_device 0 and 2; for data_on_device 1 the CALLER'S
+ * device pointer, which must therefore stay valid and unchanged until this call returns. */
+int zultra_hip_verify_device(zultra_hip_ctx_t *ctx, zultra_hip_verify_t *report);
+/* Device time of the last zultra_hip_verify_device's kernel, milliseconds (HIP events on the context's stream). */
+float zultra_hip_last_verify_ms(const zultra_hip_ctx_t *ctx);
 
 /*
  * Many small independent inputs ("files", BASELINE.json configuration 5: 4 KiB records, each its own stream). A files

@@ -65,6 +65,12 @@ class BitState(C.Structure):
     _fields_ = [("acc", C.c_uint32), ("nacc", C.c_uint32)]
 
 
+class Verify(C.Structure):
+    # zultra_hip_verify_t
+    _fields_ = [("bad_subblocks", C.c_uint32), ("first_bad", C.c_uint32), ("reason", C.c_uint32), ("block", C.c_uint32),
+                ("input_off", C.c_uint64), ("stream_bit", C.c_uint64), ("verified_bytes", C.c_uint64)]
+
+
 EXPORTS = [
     # include/libzultra.h
     "zultra_stream_init", "zultra_stream_set_dictionary", "zultra_stream_compress", "zultra_stream_end",
@@ -81,6 +87,8 @@ EXPORTS = [
     "zultra_hip_create_files", "zultra_hip_compress_files", "zultra_hip_stitch_files", "zultra_hip_staging",
     "zultra_hip_block_adler32", "zultra_adler32_append", "zultra_hip_copy_bandwidth", "zultra_hip_last_stats",
     "zultra_hip_ctx_info", "zultra_hip_context_bytes", "zultra_hip_context_bytes_on", "zultra_release_cached_contexts", "zultra_hip_chain_trace", "zultra_hip_cut_tasks", "zultra_hip_stitch_with_batch",
+    # verification
+    "zultra_set_verify", "zultra_verified_bytes", "zultra_hip_verify_device", "zultra_hip_last_verify_ms", "zultra_hip_stream_write",
 ]
 
 
@@ -206,6 +214,16 @@ class Lib:
         f.argtypes = [C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32]
         f.restype = C.c_uint32
         return f(crc, a.ctypes.data, n.ctypes.data, len(a))
+
+    def set_verify(self, enable):
+        """zultra_set_verify: every batch the host API stitches is inflated on the device and compared with its input."""
+        self.L.zultra_set_verify.argtypes = [C.c_int]
+        self.L.zultra_set_verify.restype = None
+        self.L.zultra_set_verify(1 if enable else 0)
+
+    def verified_bytes(self):
+        self.L.zultra_verified_bytes.restype = C.c_ulonglong
+        return int(self.L.zultra_verified_bytes())
 
     def stream(self, flags, max_block=0, zalloc=None, zfree=None):
         return Stream(self, flags, max_block, zalloc, zfree)
@@ -431,6 +449,28 @@ class HipContext:
         self.lib.L.zultra_hip_stream_read.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t]
         if self.lib.L.zultra_hip_stream_read(self.h, out.ctypes.data, offset, nbytes) != 0:
             raise ZultraError("stream_read")
+        return out
+
+    def stream_write(self, data, offset=0):
+        """Overwrites stream bytes [offset, offset + len(data)) (zultra_hip_stream_write)."""
+        d = _as_u8(data)
+        self.lib.L.zultra_hip_stream_write.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t]
+        if self.lib.L.zultra_hip_stream_write(self.h, d.ctypes.data, offset, len(d)) != 0:
+            raise ZultraError("stream_write")
+
+    def verify(self):
+        """zultra_hip_verify_device over the last stitched batch -> dict of the report plus "rc" (0 verified, 1 mismatch) and "verify_ms"."""
+        L = self.lib.L
+        L.zultra_hip_verify_device.argtypes = [C.c_void_p, C.POINTER(Verify)]
+        L.zultra_hip_last_verify_ms.argtypes = [C.c_void_p]
+        L.zultra_hip_last_verify_ms.restype = C.c_float
+        r = Verify()
+        rc = L.zultra_hip_verify_device(self.h, C.byref(r))
+        if rc < 0:
+            raise ZultraError("zultra_hip_verify_device: " + L.zultra_hip_last_error(self.h).decode())
+        out = {k: int(getattr(r, k)) for k, _ in Verify._fields_}
+        out["rc"] = rc
+        out["verify_ms"] = float(L.zultra_hip_last_verify_ms(self.h))
         return out
 
     def block_adler32(self):

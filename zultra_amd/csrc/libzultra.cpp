@@ -9,6 +9,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <atomic>
 #include <condition_variable>
 #include <mutex>
 #include <new>
@@ -479,6 +480,33 @@ __attribute__((visibility("hidden"))) void zh_threaded_copy(uint8_t *dst, const 
    for (auto &t : th) t.join();
 }
 
+// ---- verification (libzultra.h: zultra_set_verify) ------------------------------------------------------------------------------------------
+static std::atomic<int> g_verify{-1};   // -1: not set by the caller, the environment decides
+static std::atomic<unsigned long long> g_verified_bytes{0};
+extern "C" void zultra_set_verify(int nEnable) { g_verify.store(nEnable ? 1 : 0); }
+extern "C" unsigned long long zultra_verified_bytes(void) { return g_verified_bytes.load(); }
+static bool zh_verify_on() {
+   const int v = g_verify.load();
+   if (v >= 0) return v != 0;
+   const char *e = getenv("ZULTRA_HIP_VERIFY");
+   return e && atoi(e) != 0;
+}
+// The batch the context has just stitched, inflated on its device and compared with its input. false: a mismatch (one line on stderr) or an error.
+static bool zh_verify_stitched(zultra_hip_ctx_t *c) {
+   zultra_hip_verify_t r;
+   const int rc = zultra_hip_verify_device(c, &r);
+   if (rc == 0) {
+      g_verified_bytes.fetch_add(r.verified_bytes);
+      return true;
+   }
+   if (rc == 1)
+      fprintf(stderr, "zultra: verification failed: %u sub-block(s) do not inflate to the input; first: sub-block %u, reason %u, max-block %u, input offset %llu, stream bit %llu\n",
+              r.bad_subblocks, r.first_bad, r.reason, r.block, (unsigned long long)r.input_off, (unsigned long long)r.stream_bit);
+   else
+      fprintf(stderr, "zultra: verification could not run: %s\n", zultra_hip_last_error(c));
+   return false;
+}
+
 static zultra_hip_ctx_t *ctx_acquire_on(int dev, uint32_t bs, uint32_t want_blocks) {
    std::lock_guard<std::mutex> lk(g_ctx_mutex);
    for (size_t i = 0; i < g_ctx_pool.size(); i++) {
@@ -722,6 +750,7 @@ static zultra_status_t compress_staged(zultra_stream_t *s, zultra_compressor_t *
       int rc = zultra_hip_stitch_device(c->hip, &c->bitstate, final_last ? (int)count - 1 : -1, &end_bit);
       if (rc == -2) return ZULTRA_ERROR_DST;
       if (rc != 0) return ZULTRA_ERROR_COMPRESSION;
+      if (zh_verify_on() && !zh_verify_stitched(c->hip)) return ZULTRA_ERROR_COMPRESSION;
       const size_t total = (size_t)((end_bit + 7) >> 3);
       if (total > c->out_cap) return ZULTRA_ERROR_DST;
       if (zultra_hip_stream_read(c->hip, c->out, 0, total) != 0) return ZULTRA_ERROR_COMPRESSION;
@@ -737,6 +766,14 @@ static zultra_status_t compress_staged(zultra_stream_t *s, zultra_compressor_t *
       }
    }
    else {
+      if (zh_verify_on()) {
+         // the host stitcher's bytes never reach the device: the same batch is stitched there too, from the same phase, and that stream is checked
+         zultra_hip_bitstate_t dev_state = c->bitstate;
+         uint64_t end_bit = 0;
+         const int rc = zultra_hip_stitch_device(c->hip, &dev_state, final_last ? (int)count - 1 : -1, &end_bit);
+         if (rc == -2) return ZULTRA_ERROR_DST;
+         if (rc != 0 || !zh_verify_stitched(c->hip)) return ZULTRA_ERROR_COMPRESSION;
+      }
       uint32_t cnt = 0;
       const zultra_hip_subblock_t *subs = zultra_hip_subblocks(c->hip, &cnt);
       size_t psize = 0;
@@ -1078,7 +1115,7 @@ static size_t memory_compress_lanes(const unsigned char *pIn, size_t nIn, unsign
          const int rc = zultra_hip_stitch_device(c, &bit, last ? (int)J.nblocks - 1 : -1, &end_bit);
          const size_t total = (size_t)((end_bit + 7) >> 3);
          uint8_t *stage = rc == 0 ? (uint8_t *)zultra_hip_staging(c, 1, total + 16) : NULL;
-         if (rc != 0 || !stage || zultra_hip_stream_read(c, stage, 0, total) != 0)
+         if (rc != 0 || !stage || (zh_verify_on() && !zh_verify_stitched(c)) || zultra_hip_stream_read(c, stage, 0, total) != 0)
             fail = true;
          else {
             stage[0] |= (uint8_t)pending;

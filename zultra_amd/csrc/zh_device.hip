@@ -35,6 +35,7 @@
 #include "zh_parse_lanes.h"
 #include "zh_split.h"
 #include "zh_stitch.h"
+#include "zh_inflate.h"
 
 #ifdef ZH_EMU
 #include <mutex>
@@ -203,6 +204,12 @@ struct zultra_hip_ctx_s {
    uint32_t *d_task_prefix, *h_task_prefix;   // files mode: exclusive prefix of the inputs' task counts, computed by the host from the sizes it was handed (zh_plan_files); B + 1 entries
    uint32_t *d_stream;        // stitched deflate bits of the last batch
    size_t stream_cap;         // bytes
+   // verification (zh_inflate.h, zultra_hip_verify_device): what is allocated on the first call, and whether the stream buffer holds a stitched batch
+   zh_verify_item_t *d_vitems;
+   zh_verify_report_t *d_vreport, *h_vreport;
+   hipEvent_t ev_verify[2];
+   int stream_stitched;       // 0: nothing to verify (no stitch yet, one that failed, a phase-table call since); 1: a stream; 2: one stream per max-block (files)
+   float verify_ms;
    uint32_t *d_crc, *d_crc_tables, *d_adler;
    uint32_t *h_adler;
    std::vector<uint32_t> adler;
@@ -569,6 +576,11 @@ extern "C" void zultra_hip_destroy(zultra_hip_ctx_t *c) {
    (void)hipFree(c->d_results_compact);
    (void)hipFree(c->d_items);
    (void)hipFree(c->d_stream);
+   (void)hipFree(c->d_vitems);
+   (void)hipFree(c->d_vreport);
+   if (c->h_vreport) (void)hipHostFree(c->h_vreport);
+   for (int i = 0; i < 2; i++)
+      if (c->ev_verify[i]) (void)hipEventDestroy(c->ev_verify[i]);
    (void)hipFree(c->d_crc);
    (void)hipFree(c->d_adler);
    if (c->h_adler) (void)hipHostFree(c->h_adler);
@@ -1349,6 +1361,7 @@ static int zh_run_files(zultra_hip_ctx_t *c, uint32_t nblocks) {
    c->adler.assign(c->h_adler, c->h_adler + 2 * (size_t)nblocks);
    c->nsubs = nblocks;
    c->files_stitch_rc = zh_stitch_verdict(c, false);
+   c->stream_stitched = c->files_stitch_rc == 0 ? 2 : 0;
    c->files_stitched = 1;   // (no stitch_ms of its own: inside a captured graph an event is a node, not a time stamp; the batch's encode_ms covers the assembly)
    (void)hipEventElapsedTime(&c->timing.h2d_ms, c->lane_ev[0][ZH_EV_START], c->ev_input);
    (void)hipEventElapsedTime(&c->timing.encode_ms, c->lane_ev[0][ZH_EV_INPUT], c->lane_ev[0][ZH_EV_READBACK]);   // the whole graph
@@ -1540,6 +1553,7 @@ static int zh_read_back(zultra_hip_ctx_t *c, const uint32_t *run_b0, int lanes, 
    c->nsubs = nsubs;
    if (stitch_now) {
       c->stitched_rc = zh_stitch_verdict(c, false);
+      c->stream_stitched = c->stitched_rc == 0 ? 1 : 0;
       c->stitched_phase = c->ab_phase;
       c->stitched_final = c->ab_final;
       c->stitched_valid = 1;
@@ -1593,6 +1607,7 @@ extern "C" int zultra_hip_compress_blocks(zultra_hip_ctx_t *c, const void *data,
    c->ab_armed = 0;
    c->stitched_valid = 0;
    c->files_stitched = 0;
+   c->stream_stitched = 0;
    c->nblocks = nblocks;
    c->nsubs = 0;
    c->blocks.assign((const zh_block_t *)blocks, (const zh_block_t *)blocks + nblocks);
@@ -1697,12 +1712,15 @@ static int zh_stitch_on_device(zultra_hip_ctx_t *c, uint32_t phase, int final_bl
    hipStream_t st = c->stream;
    c->stitched_valid = 0;   // (the items and the scan's report are rewritten)
    c->files_stitched = 0;
+   c->stream_stitched = 0;
    ZH_CHECK(c, hipEventRecord(c->ev_stitch[ZH_STITCH_EV_START], st));
    if (zh_enqueue_stitch(c, st, phase, final_block, files, scan_only, true) != 0) return -1;
    ZH_CHECK(c, hipStreamSynchronize(st));
    ZH_CHECK(c, hipGetLastError());
    if (!scan_only) (void)hipEventElapsedTime(&c->timing.stitch_ms, c->ev_stitch[ZH_STITCH_EV_START], c->ev_stitch[ZH_STITCH_EV_END]);
-   return zh_stitch_verdict(c, scan_only);
+   const int rc = zh_stitch_verdict(c, scan_only);
+   if (!scan_only && rc == 0) c->stream_stitched = files ? 2 : 1;
+   return rc;
 }
 
 // The next batch of max-blocks (zultra_hip_compress_blocks) is stitched at bit phase `phase` (final_block as for zultra_hip_stitch_device) BEHIND ITS LAST KERNEL,
@@ -1785,11 +1803,70 @@ extern "C" int zultra_hip_compress_files(zultra_hip_ctx_t *c, const void *data, 
 extern "C" const void *zultra_hip_stream_device(const zultra_hip_ctx_t *c) { return c ? c->d_stream : NULL; }
 
 extern "C" int zultra_hip_stream_read(zultra_hip_ctx_t *c, void *out, size_t offset, size_t nbytes) {
-   if (!c || offset + nbytes > c->stream_cap) return -1;
+   if (!c || nbytes > c->stream_cap || offset > c->stream_cap - nbytes) return -1;
    ZH_CHECK(c, hipSetDevice(c->device));
    ZH_CHECK(c, hipMemcpy(out, (const uint8_t *)c->d_stream + offset, nbytes, hipMemcpyDeviceToHost));
    return 0;
 }
+extern "C" int zultra_hip_stream_write(zultra_hip_ctx_t *c, const void *in, size_t offset, size_t nbytes) {
+   if (!c || !in || nbytes > c->stream_cap || offset > c->stream_cap - nbytes) return -1;
+   ZH_CHECK(c, hipSetDevice(c->device));
+   ZH_CHECK(c, hipMemcpy((uint8_t *)c->d_stream + offset, in, nbytes, hipMemcpyHostToDevice));
+   return 0;
+}
+
+// Inflate-and-compare of the stream the last stitch left in the stream buffer (zh_inflate.h): one wave per sub-block on the context's stream — the stitch
+// has been waited for, whichever stream it ran on —, the 16 bytes of the batch report read back, the first bad item's record only where there is one.
+// What it needs beyond the stitch's own buffers (24 bytes per sub-block, two events) is allocated by the first call: a context that is never asked
+// holds nothing for it.
+extern "C" int zultra_hip_verify_device(zultra_hip_ctx_t *c, zultra_hip_verify_t *report) {
+   ZH_EMU_SERIALIZE();
+   if (!c || !report) return -1;
+   memset(report, 0, sizeof(*report));
+   report->first_bad = 0xFFFFFFFFu;
+   if (!c->stream_stitched || c->nsubs == 0) {
+      snprintf(c->err, sizeof(c->err), "nothing to verify: the stream buffer holds no stitched batch");
+      return -1;
+   }
+   ZH_CHECK(c, hipSetDevice(c->device));
+   if (!c->d_vitems) {
+      if (zh_alloc(c, &c->d_vitems, (size_t)c->max_blocks * c->max_subs) || zh_alloc(c, &c->d_vreport, 1)) return -1;
+      ZH_CHECK(c, hipHostMalloc((void **)&c->h_vreport, sizeof(zh_verify_report_t), 0));
+      for (int i = 0; i < 2; i++) ZH_CHECK(c, hipEventCreate(&c->ev_verify[i]));
+   }
+   const int files = c->stream_stitched == 2;
+   hipStream_t st = c->stream;
+   ZH_CHECK(c, hipMemsetAsync(c->d_vreport, 0, sizeof(zh_verify_report_t), st));
+   ZH_CHECK(c, hipMemsetAsync(&c->d_vreport->first_bad, 0xff, sizeof(uint32_t), st));
+   ZH_CHECK(c, hipEventRecord(c->ev_verify[0], st));
+   const uint32_t grid = (uint32_t)zh_min64(c->nsubs, zh_max64(12ull * c->total_cus, 64));   // (one wave per workgroup, three to a SIMD — zh_inflate.h: a CU holds 12; more would only queue)
+   ZH_LAUNCH(zh_verify_subblocks, grid, ZH_VERIFY_THREADS, st, (const uint32_t *)c->d_stream, (uint64_t)c->stream_cap, (const zh_stitch_item_t *)c->d_items,
+             (const zh_subblock_t *)c->d_results_compact, (const zh_block_t *)c->d_blocks, c->nblocks, c->cur_data, (const zh_scan_out_t *)c->d_scan_out, (const uint64_t *)c->d_file_off, files,
+             c->d_vitems, c->d_vreport);
+   ZH_CHECK(c, hipEventRecord(c->ev_verify[1], st));
+   ZH_CHECK(c, hipMemcpyAsync(c->h_vreport, c->d_vreport, sizeof(zh_verify_report_t), hipMemcpyDeviceToHost, st));
+   ZH_CHECK(c, hipStreamSynchronize(st));
+   ZH_CHECK(c, hipGetLastError());
+   (void)hipEventElapsedTime(&c->verify_ms, c->ev_verify[0], c->ev_verify[1]);
+   const zh_verify_report_t r = *c->h_vreport;
+   report->bad_subblocks = r.bad;
+   report->verified_bytes = ((uint64_t)r.verified_hi << 32) | r.verified_lo;
+   if (r.bad == 0) return 0;
+   if (r.first_bad >= c->nsubs) {
+      snprintf(c->err, sizeof(c->err), "verification reports sub-block %u of %u", r.first_bad, c->nsubs);
+      return -1;
+   }
+   zh_verify_item_t item;
+   ZH_CHECK(c, hipMemcpy(&item, c->d_vitems + r.first_bad, sizeof(item), hipMemcpyDeviceToHost));
+   report->first_bad = r.first_bad;
+   report->reason = item.reason;
+   report->block = item.block;
+   report->input_off = item.input_off;
+   report->stream_bit = item.stream_bit;
+   return 1;
+}
+extern "C" float zultra_hip_last_verify_ms(const zultra_hip_ctx_t *c) { return c ? c->verify_ms : 0.f; }
+
 extern "C" void zultra_hip_last_timing(const zultra_hip_ctx_t *c, zultra_hip_timing_t *t) {
    if (c && t) *t = c->timing;
 }

@@ -6,7 +6,10 @@
  * so that the device sees batches of many max-blocks. The bytes written are those of the reference for the same flags and
  * block size.
  *
- *    zultra_amd_cli [-b <max block size>] [-f gzip|zlib|raw] [-k <chunk KiB>] [-d <device>] [-v] <infile> <outfile>
+ *    zultra_amd_cli [-b <max block size>] [-f gzip|zlib|raw] [-k <chunk KiB>] [-d <device>] [-c] [-v] <infile> <outfile>
+ *
+ * -c: every batch is inflated on the device and compared with its input before its bytes are written (zultra_set_verify); a mismatch ends the
+ *     run with a non-zero status. With -v the number of bytes checked is printed.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -24,7 +27,7 @@ static double now_s(void) {
 int main(int argc, char **argv) {
    unsigned flags = ZULTRA_FLAG_GZIP_FRAMING, block = 0;
    size_t chunk = (size_t)8 << 20;
-   int verbose = 0, i = 1;
+   int verbose = 0, verify = 0, i = 1;
    for (; i < argc && argv[i][0] == '-' && argv[i][1]; i++) {
       if (!strcmp(argv[i], "-b") && i + 1 < argc)
          block = (unsigned)strtoul(argv[++i], NULL, 0);
@@ -38,11 +41,15 @@ int main(int argc, char **argv) {
       }
       else if (!strcmp(argv[i], "-v"))
          verbose = 1;
+      else if (!strcmp(argv[i], "-c")) {
+         verify = 1;
+         zultra_set_verify(1);
+      }
       else
          break;
    }
    if (argc - i != 2 || chunk == 0) {
-      fprintf(stderr, "usage: %s [-b <max block size>] [-f gzip|zlib|raw] [-k <chunk KiB>] [-d <device>] [-v] <infile> <outfile>\n", argv[0]);
+      fprintf(stderr, "usage: %s [-b <max block size>] [-f gzip|zlib|raw] [-k <chunk KiB>] [-d <device>] [-c] [-v] <infile> <outfile>\n", argv[0]);
       return 100;
    }
    FILE *fin = fopen(argv[i], "rb");
@@ -89,6 +96,7 @@ int main(int argc, char **argv) {
    if (verbose && !rc)
       fprintf(stdout, "%llu -> %llu bytes (%.2f %%), %.1f MB/s\n", (unsigned long long)strm.total_in, (unsigned long long)strm.total_out,
               strm.total_in ? 100.0 * (double)strm.total_out / (double)strm.total_in : 0.0, dt > 0 ? (double)strm.total_in / dt / 1e6 : 0.0);
+   if (verbose && verify && !rc) fprintf(stdout, "verified %llu bytes on the device\n", zultra_verified_bytes());
    zultra_stream_end(&strm);
    zultra_release_cached_contexts();
    free(in);

@@ -137,6 +137,13 @@ int zultra_release_cached_contexts(void);
 void zultra_set_verify(int nEnable);
 /* Input bytes verified that way in this process since the library was loaded: how a caller knows the check ran over everything. */
 unsigned long long zultra_verified_bytes(void);
+/* Decompression (the reference has none: its tool links zlib for its own check). pIn is one complete stream in the framing nFlags names, as for
+ * compression: raw deflate (the stream must end at nIn), zlib (2-byte header with the CMF / FLG check, FDICT is rejected, Adler-32 checked) or gzip
+ * (RFC 1952 header with FEXTRA, FNAME, FCOMMENT and FHCRC skipped, CRC-32 and ISIZE checked). The deflate stream is inflated on the device
+ * (include/zultra_hip.h: zultra_hip_inflate_streams — one stream, so at the speed of one wave), the checksum is taken on the host. Returns the
+ * number of bytes written to pOut, or (size_t)-1: a bad header, a stream that does not decode, bytes behind its end, a checksum mismatch, more
+ * output than nMaxOut, no device. */
+size_t zultra_memory_decompress(const unsigned char *pIn, size_t nIn, unsigned char *pOut, size_t nMaxOut, const unsigned int nFlags);
 
 #ifdef __cplusplus
 }

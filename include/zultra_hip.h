@@ -230,6 +230,33 @@ int zultra_hip_verify_device(zultra_hip_ctx_t *ctx, zultra_hip_verify_t *report)
 float zultra_hip_last_verify_ms(const zultra_hip_ctx_t *ctx);
 
 /*
+ * Batched inflate: many independent raw deflate streams (RFC 1951) decoded on the device, one wave64 per stream. Item i is the
+ * complete stream at src + src_off (any byte address, any number of stored / fixed / dynamic blocks up to and including the block with BFINAL) and
+ * is written to dst + dst_off, at most dst_cap bytes. One stream runs at the speed of ONE wave — a serial chain of tokens —, so the call pays for
+ * batches of many streams (the records of a files batch); decoding one large stream in parallel is not what it does. Preset dictionaries are not
+ * supported: a match that reaches in front of the item's own output fails with reason 4.
+ *   reason   : 0 ok; as for verification where it fits — 1 header (BTYPE 3, HLIT / HDIST out of range), 2 code lengths, 3 symbol, 4 distance (no such
+ *              code, symbols 30 and 31, a distance that reaches in front of the item's output), 7 stored LEN/NLEN, 12 the stream ends before its
+ *              final block does (bytes behind src_size read as zero); and 13 = the output does not fit in dst_cap
+ *   blocks   : deflate blocks decoded
+ *   out_size : bytes written (on failure: before the failure); never more than dst_cap, and nothing outside the item's range is touched
+ *   src_used : bytes of the item consumed, up to and including the byte that holds the last bit of the final block
+ * With *_on_device == 1 the pointer is a device pointer valid on `device` and is used in place, nothing is copied: src = zultra_hip_stream_device(ctx)
+ * with the file_off array of zultra_hip_compress_files turned into items inflates a files batch without its bytes leaving the device. With
+ * *_on_device == 0 the call stages through device memory it allocates and frees itself (of a host dst only the out_size bytes of every item are
+ * written). No context is needed. kernel_ms (may be NULL): device time of the kernel, HIP events.
+ * Returns the number of items whose reason is not 0 (0: all of them decoded), or -1 for HIP errors and bad arguments: n == 0, an item range outside
+ * src_size or dst_size, destination ranges that overlap. Any bytes in src give a verdict per item and nothing else.
+ */
+#define ZULTRA_HIP_INFLATE_OK 0
+#define ZULTRA_HIP_INFLATE_DST_FULL 13
+typedef struct zultra_hip_inflate_item_s { uint64_t src_off, src_size, dst_off, dst_cap; } zultra_hip_inflate_item_t;
+typedef struct zultra_hip_inflate_result_s { uint32_t reason, blocks; uint64_t out_size, src_used; } zultra_hip_inflate_result_t;
+int zultra_hip_inflate_streams(int device, const void *src, size_t src_size, int src_on_device, void *dst, size_t dst_size, int dst_on_device,
+                               const zultra_hip_inflate_item_t *items, uint32_t n, zultra_hip_inflate_result_t *results /* host, n */,
+                               float *kernel_ms /* may be NULL */);
+
+/*
  * Many small independent inputs ("files", BASELINE.json configuration 5: 4 KiB records, each its own stream). A files
  * context takes inputs below 8192 bytes — the splitter never cuts those (blockdeflate.c:646), so a batch needs no host
  * decision and its whole kernel sequence is replayed from one captured hipGraph. zultra_hip_compress_files runs

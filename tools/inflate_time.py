@@ -1,0 +1,126 @@
+#!/usr/bin/env python3
+"""Times the batched inflate kernel (zh_inflate_streams, zultra_hip_inflate_streams) on a files batch of BASELINE.json configuration 5's shape:
+the batch is compressed on the device and inflated from the context's stream buffer into device memory, nothing leaves HBM. Next to it the
+verification kernel (zultra_hip_verify_device) on the same batch — the same decoder without an output path — and host zlib inflating the same
+streams on one core. One JSON line.
+
+    python tools/inflate_time.py [--files N] [--file-size BYTES] [--reps N] [--step-timeout SECONDS]
+
+The steps run in this order, every GPU step in a process of its own under its own time limit; a step that fails ends the run:
+    1. zultra_hip_inflate_streams from the device stream buffer (the output is read back once and compared with the input)
+    2. zultra_hip_verify_device on the same batch
+    3. host zlib, one core, over the same streams (this process: it touches no GPU)"""
+import argparse
+import json
+import os
+import subprocess
+import sys
+import tempfile
+import time
+import zlib
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+
+def batch(args):
+    import numpy as np
+
+    import corpus
+    import zultra_amd
+    L = zultra_amd.lib()
+    if L.device_count() < 1:
+        raise RuntimeError("no HIP device visible: nothing can be timed")
+    L.is_emulator = False
+    d = np.ascontiguousarray(corpus.json_files(0, args.files, args.file_size), dtype=np.uint8)
+    offs, sizes = np.arange(args.files, dtype=np.uint64) * args.file_size, np.full(args.files, args.file_size, dtype=np.uint32)
+    ctx = L.files_context(args.file_size, args.files)
+    file_off = ctx.compress_files(d, offs, sizes)
+    return L, ctx, d, file_off
+
+
+def child_inflate(args):
+    import numpy as np
+
+    import inflate_cases as I
+    import verify_cases as V
+    L, ctx, d, file_off = batch(args)
+    n, fs = args.files, args.file_size
+    items = np.stack([file_off[:-1], file_off[1:] - file_off[:-1], np.arange(n, dtype=np.uint64) * fs, np.full(n, fs, dtype=np.uint64)], axis=1)
+    dst = V.DeviceCopy(L, np.zeros(n * fs, dtype=np.uint8))
+    times, calls = [], []
+    for it in range(2 + args.reps):   # (two warm-up calls)
+        t0 = time.perf_counter()
+        rc, res, ms = L.inflate_streams(ctx.stream_ptr(), int(file_off[-1]), dst.ptr, n * fs, items)
+        calls.append(1e3 * (time.perf_counter() - t0))
+        assert rc == 0, (rc, res[res["reason"] != 0][:4])
+        if it >= 2:
+            times.append(ms)
+    assert I.device_read(L, dst, n * fs).tobytes() == d.tobytes(), "the inflated batch differs from the input"
+    np.savez(args.stream_file, stream=ctx.stream_read(int(file_off[-1])), file_off=file_off)
+    dst.free()
+    ctx.close()
+    print(json.dumps({"inflate_kernel_ms": {"min": min(times), "median": float(np.median(times)), "all": times},
+                      "inflate_call_ms": {"min": min(calls[2:]), "all": calls[2:]}, "stream_bytes": int(file_off[-1]), "blocks": int(res["blocks"].sum())}), flush=True)
+    return 0
+
+
+def child_verify(args):
+    import numpy as np
+    L, ctx, d, file_off = batch(args)
+    times = []
+    for it in range(2 + args.reps):
+        r = ctx.verify()
+        assert r["rc"] == 0 and r["verified_bytes"] == len(d), r
+        if it >= 2:
+            times.append(r["verify_ms"])
+    ctx.close()
+    print(json.dumps({"verify_kernel_ms": {"min": min(times), "median": float(np.median(times)), "all": times}}), flush=True)
+    return 0
+
+
+def gpu_step(name, args):
+    cmd = [sys.executable, os.path.abspath(__file__), "--child", name, "--files", str(args.files), "--file-size", str(args.file_size), "--reps", str(args.reps),
+           "--stream-file", args.stream_file]
+    r = subprocess.run(cmd, timeout=args.step_timeout, capture_output=True, text=True)
+    if r.returncode != 0:
+        sys.stderr.write(r.stdout + r.stderr)
+        sys.exit("step %s failed with status %d: nothing more is started" % (name, r.returncode))
+    return json.loads(r.stdout.strip().splitlines()[-1])
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--files", type=int, default=65536)
+    ap.add_argument("--file-size", type=int, default=4096)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--step-timeout", type=int, default=300, help="seconds every GPU step may take")
+    ap.add_argument("--child", choices=["inflate", "verify"], help="(internal) the process that opens the GPU")
+    ap.add_argument("--stream-file", default="", help="(internal) where the inflate step leaves the streams for host zlib")
+    args = ap.parse_args()
+    if args.child:
+        sys.exit(child_inflate(args) if args.child == "inflate" else child_verify(args))
+    import numpy as np
+    with tempfile.TemporaryDirectory() as tmp:
+        args.stream_file = os.path.join(tmp, "streams.npz")
+        out = {"files": args.files, "file_size": args.file_size, "input_bytes": args.files * args.file_size}
+        out.update(gpu_step("inflate", args))
+        out.update(gpu_step("verify", args))
+        z = np.load(args.stream_file)
+        stream, file_off = z["stream"].tobytes(), z["file_off"]
+    host = []
+    for _ in range(3):
+        t0 = time.perf_counter()
+        total = sum(len(zlib.decompress(stream[int(file_off[i]):int(file_off[i + 1])], -15)) for i in range(args.files))
+        host.append(1e3 * (time.perf_counter() - t0))
+    assert total == out["input_bytes"]
+    out["zlib_inflate_one_core_ms"] = {"min": min(host), "all": host}
+    out["inflate_over_verify"] = out["inflate_kernel_ms"]["median"] / out["verify_kernel_ms"]["median"]
+    out["zlib_over_inflate"] = min(host) / out["inflate_kernel_ms"]["median"]
+    out["inflate_GBps_of_output"] = out["input_bytes"] / out["inflate_kernel_ms"]["median"] / 1e6
+    print(json.dumps(out), flush=True)
+
+
+if __name__ == "__main__":
+    main()

@@ -71,6 +71,16 @@ class Verify(C.Structure):
                 ("input_off", C.c_uint64), ("stream_bit", C.c_uint64), ("verified_bytes", C.c_uint64)]
 
 
+class InflateItem(C.Structure):
+    # zultra_hip_inflate_item_t
+    _fields_ = [("src_off", C.c_uint64), ("src_size", C.c_uint64), ("dst_off", C.c_uint64), ("dst_cap", C.c_uint64)]
+
+
+class InflateResult(C.Structure):
+    # zultra_hip_inflate_result_t
+    _fields_ = [("reason", C.c_uint32), ("blocks", C.c_uint32), ("out_size", C.c_uint64), ("src_used", C.c_uint64)]
+
+
 EXPORTS = [
     # include/libzultra.h
     "zultra_stream_init", "zultra_stream_set_dictionary", "zultra_stream_compress", "zultra_stream_end",
@@ -89,6 +99,8 @@ EXPORTS = [
     "zultra_hip_ctx_info", "zultra_hip_context_bytes", "zultra_hip_context_bytes_on", "zultra_release_cached_contexts", "zultra_hip_chain_trace", "zultra_hip_cut_tasks", "zultra_hip_stitch_with_batch",
     # verification
     "zultra_set_verify", "zultra_verified_bytes", "zultra_hip_verify_device", "zultra_hip_last_verify_ms", "zultra_hip_stream_write",
+    # decompression
+    "zultra_memory_decompress", "zultra_hip_inflate_streams",
 ]
 
 
@@ -190,6 +202,33 @@ class Lib:
         data = _as_u8(data)
         r = self.L.zultra_memory_compress(data.ctypes.data, len(data), out.ctypes.data, len(out), flags, max_block)
         return None if r == _SIZE_MAX else int(r)
+
+    def memory_decompress(self, data, flags, max_out):
+        """zultra_memory_decompress -> the decompressed bytes, or None where the call returns (size_t)-1."""
+        data = _as_u8(data)
+        out = np.empty(max(max_out, 1), dtype=np.uint8)
+        f = self.L.zultra_memory_decompress
+        f.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint]
+        f.restype = C.c_size_t
+        r = f(data.ctypes.data, len(data), out.ctypes.data, max_out, flags)
+        if r == _SIZE_MAX:
+            return None
+        return out[:r].tobytes()
+
+    def inflate_streams(self, src, src_size, dst, dst_size, items, device=0):
+        """zultra_hip_inflate_streams. src / dst: a uint8 array (host memory, staged by the call) or an integer device pointer (used in place);
+        items: (src_off, src_size, dst_off, dst_cap) each. -> (rc, results, kernel_ms): rc = number of items that did not decode, -1 for bad
+        arguments and HIP errors; results = (reason, blocks, out_size, src_used) per item."""
+        arr = np.ascontiguousarray(items, dtype=np.uint64).reshape(-1, 4)
+        res = np.zeros(len(arr), dtype=[("reason", "<u4"), ("blocks", "<u4"), ("out_size", "<u8"), ("src_used", "<u8")])
+        src_dev, dst_dev = not isinstance(src, np.ndarray), not isinstance(dst, np.ndarray)
+        ms = C.c_float(0)
+        f = self.L.zultra_hip_inflate_streams
+        f.argtypes = [C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(C.c_float)]
+        f.restype = C.c_int
+        rc = f(device, int(src) if src_dev else src.ctypes.data, src_size, 1 if src_dev else 0, int(dst) if dst_dev else dst.ctypes.data, dst_size, 1 if dst_dev else 0,
+               arr.ctypes.data, len(arr), res.ctypes.data, C.byref(ms))
+        return rc, res, float(ms.value)
 
     def checksum(self, data, flags, start=None):
         data = _as_u8(data)

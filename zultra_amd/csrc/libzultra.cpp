@@ -1196,3 +1196,54 @@ extern "C" size_t zultra_memory_compress(const unsigned char *pIn, size_t nIn, u
                                          const unsigned int nFlags, unsigned int nMaxBlockSize) {
    return zultra_memory_compress_dict(pIn, nIn, pOut, nOutCap, nFlags, nMaxBlockSize, NULL, 0);
 }
+
+// ================================================================================================================
+// Decompression: the framing on the host, the deflate stream on the device (zultra_hip_inflate_streams)
+// ================================================================================================================
+
+extern "C" size_t zultra_memory_decompress(const unsigned char *pIn, size_t nIn, unsigned char *pOut, size_t nMaxOut, const unsigned int nFlags) {
+   if (!pIn || (!pOut && nMaxOut)) return (size_t)-1;
+   size_t head = 0, foot = 0;
+   if (nFlags & ZULTRA_FLAG_GZIP_FRAMING) {
+      // RFC 1952 2.3: ID1 ID2 CM FLG MTIME(4) XFL OS, then what FLG announces
+      if (nIn < 18 || pIn[0] != 0x1f || pIn[1] != 0x8b || pIn[2] != 8 || (pIn[3] & 0xe0)) return (size_t)-1;
+      const unsigned flg = pIn[3];
+      head = 10;
+      if (flg & 4) {   // FEXTRA: XLEN, then XLEN bytes
+         if (head + 2 > nIn) return (size_t)-1;
+         head += 2 + ((size_t)pIn[head] | ((size_t)pIn[head + 1] << 8));
+      }
+      for (unsigned bit = 8; bit <= 16; bit <<= 1)   // FNAME, FCOMMENT: zero-terminated
+         if (flg & bit) {
+            while (head < nIn && pIn[head]) head++;
+            head++;
+         }
+      if (flg & 2) head += 2;   // FHCRC
+      foot = 8;
+   }
+   else if (nFlags & ZULTRA_FLAG_ZLIB_FRAMING) {
+      // RFC 1950 2.2: CM = 8, CINFO <= 7, (CMF * 256 + FLG) % 31 == 0, no preset dictionary
+      if (nIn < 6 || (pIn[0] & 15) != 8 || (pIn[0] >> 4) > 7 || (((unsigned)pIn[0] << 8) | pIn[1]) % 31 || (pIn[1] & 0x20)) return (size_t)-1;
+      head = 2;
+      foot = 4;
+   }
+   if (head > nIn || foot > nIn - head || nIn - head - foot == 0) return (size_t)-1;
+   const size_t nBody = nIn - head - foot;
+   zultra_hip_inflate_item_t item = {0, nBody, 0, nMaxOut};
+   zultra_hip_inflate_result_t res;
+   unsigned char none = 0;
+   if (zultra_hip_inflate_streams(zh_pick_device(), pIn + head, nBody, 0, pOut ? pOut : &none, nMaxOut, 0, &item, 1, &res, NULL) != 0) return (size_t)-1;
+   if (res.src_used != nBody) return (size_t)-1;   // (bytes behind the final block)
+   const size_t nOut = (size_t)res.out_size;
+   if (foot) {
+      const unsigned char *f = pIn + head + nBody;
+      const zultra_frame_checksum_t sum = zultra_frame_update_checksum(zultra_frame_init_checksum(nFlags), pOut, nOut, nFlags);
+      if (nFlags & ZULTRA_FLAG_GZIP_FRAMING) {
+         const uint32_t crc = f[0] | (f[1] << 8) | (f[2] << 16) | ((uint32_t)f[3] << 24), isize = f[4] | (f[5] << 8) | (f[6] << 16) | ((uint32_t)f[7] << 24);
+         if (crc != sum || isize != (uint32_t)nOut) return (size_t)-1;
+      }
+      else if ((((uint32_t)f[0] << 24) | (f[1] << 16) | (f[2] << 8) | f[3]) != sum)
+         return (size_t)-1;
+   }
+   return nOut;
+}

@@ -22,6 +22,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <mutex>
 #include <vector>
 
@@ -36,6 +37,7 @@
 #include "zh_split.h"
 #include "zh_stitch.h"
 #include "zh_inflate.h"
+#include "zh_inflate_out.h"
 
 #ifdef ZH_EMU
 #include <mutex>
@@ -1866,6 +1868,90 @@ extern "C" int zultra_hip_verify_device(zultra_hip_ctx_t *c, zultra_hip_verify_t
    return 1;
 }
 extern "C" float zultra_hip_last_verify_ms(const zultra_hip_ctx_t *c) { return c ? c->verify_ms : 0.f; }
+
+// ---- batched inflate (zh_inflate_out.h) -------------------------------------------------------------------------------------------------------------------
+static_assert(sizeof(zultra_hip_inflate_item_t) == sizeof(zh_inflate_item_t) && sizeof(zultra_hip_inflate_result_t) == sizeof(zh_inflate_result_t), "ABI");
+
+// what a zultra_hip_inflate_streams call holds on the device: released when the call returns, however it returns
+struct zh_inflate_call_t {
+   void *d_src = NULL, *d_dst = NULL, *d_items = NULL, *d_results = NULL;
+   hipEvent_t ev[2] = {NULL, NULL};
+   ~zh_inflate_call_t() {
+      (void)hipFree(d_src);
+      (void)hipFree(d_dst);
+      (void)hipFree(d_items);
+      (void)hipFree(d_results);
+      for (int i = 0; i < 2; i++)
+         if (ev[i]) (void)hipEventDestroy(ev[i]);
+   }
+};
+#define ZH_TRY(call)                       \
+   do {                                    \
+      if ((call) != hipSuccess) return -1; \
+   } while (0)
+
+// Many raw deflate streams, one wave each. No context: the call owns its item and result buffers (and, for host pointers, the staging of the source and of
+// the output in device memory), on the null stream of `device`.
+extern "C" int zultra_hip_inflate_streams(int device, const void *src, size_t src_size, int src_on_device, void *dst, size_t dst_size, int dst_on_device,
+                                          const zultra_hip_inflate_item_t *items, uint32_t n, zultra_hip_inflate_result_t *results, float *kernel_ms) {
+   ZH_EMU_SERIALIZE();
+   if (kernel_ms) *kernel_ms = 0.f;
+   if (!src || !dst || !items || !results || n == 0 || device < 0) return -1;
+   // every item inside its buffer, no two destination ranges over the same byte (empty ranges take none)
+   std::vector<uint32_t> order;
+   order.reserve(n);
+   for (uint32_t k = 0; k < n; k++) {
+      const zultra_hip_inflate_item_t &it = items[k];
+      if (it.src_off > src_size || it.src_size > src_size - it.src_off || it.dst_off > dst_size || it.dst_cap > dst_size - it.dst_off) return -1;
+      if (it.dst_cap) order.push_back(k);
+   }
+   std::sort(order.begin(), order.end(), [items](uint32_t a, uint32_t b) { return items[a].dst_off < items[b].dst_off; });
+   for (size_t i = 1; i < order.size(); i++)
+      if (items[order[i - 1]].dst_off + items[order[i - 1]].dst_cap > items[order[i]].dst_off) return -1;
+   if (device >= zultra_hip_device_count()) return -1;
+   ZH_TRY(hipSetDevice(device));
+   zh_inflate_call_t C;
+   ZH_TRY(hipMalloc(&C.d_items, (size_t)n * sizeof(zh_inflate_item_t)));
+   ZH_TRY(hipMalloc(&C.d_results, (size_t)n * sizeof(zh_inflate_result_t)));
+   for (int i = 0; i < 2; i++) ZH_TRY(hipEventCreate(&C.ev[i]));
+   const uint8_t *s8 = (const uint8_t *)src;
+   uint8_t *d8 = (uint8_t *)dst;
+   if (!src_on_device) {
+      ZH_TRY(hipMalloc(&C.d_src, src_size ? src_size : 1));
+      ZH_TRY(hipMemcpy(C.d_src, src, src_size, hipMemcpyHostToDevice));
+      s8 = (const uint8_t *)C.d_src;
+   }
+   if (!dst_on_device) {
+      ZH_TRY(hipMalloc(&C.d_dst, dst_size ? dst_size : 1));
+      d8 = (uint8_t *)C.d_dst;
+   }
+   ZH_TRY(hipMemcpy(C.d_items, items, (size_t)n * sizeof(zh_inflate_item_t), hipMemcpyHostToDevice));
+   int cus = 0;
+   if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus <= 0) cus = 256;
+   uint32_t grid = (uint32_t)zh_min64(n, zh_max64(32ull * (uint32_t)cus, 64));   // (one wave per workgroup; a CU holds fewer at a time — zh_inflate_out.h —, the rest queue and even out streams of unequal length)
+   const uint32_t grid_cap = (uint32_t)max(0, zh_env("ZULTRA_HIP_GRID_CAP", 0));   // tests: fewer waves than streams, every wave strides
+   if (grid_cap) grid = max(1u, min(grid, grid_cap));
+   ZH_TRY(hipEventRecord(C.ev[0], 0));
+   ZH_LAUNCH(zh_inflate_streams, grid, ZH_INFLATE_THREADS, 0, s8, (uint64_t)src_size, d8, (uint64_t)dst_size, (const zh_inflate_item_t *)C.d_items, n, (zh_inflate_result_t *)C.d_results);
+   ZH_TRY(hipEventRecord(C.ev[1], 0));
+   ZH_TRY(hipMemcpy(results, C.d_results, (size_t)n * sizeof(zh_inflate_result_t), hipMemcpyDeviceToHost));
+   ZH_TRY(hipDeviceSynchronize());
+   ZH_TRY(hipGetLastError());
+   if (kernel_ms) (void)hipEventElapsedTime(kernel_ms, C.ev[0], C.ev[1]);
+   int bad = 0;
+   for (uint32_t k = 0; k < n; k++) {
+      if (results[k].reason != 0) bad++;
+      if (results[k].out_size > items[k].dst_cap) return -1;   // (the kernel checks every store: never)
+   }
+   if (!dst_on_device && !order.empty()) {
+      // the bytes written, and nothing between the items' ranges: the span they cover comes back in one copy, the ranges are taken out of it
+      const uint64_t lo = items[order.front()].dst_off, hi = items[order.back()].dst_off + items[order.back()].dst_cap;
+      std::vector<uint8_t> span((size_t)(hi - lo));
+      ZH_TRY(hipMemcpy(span.data(), d8 + lo, (size_t)(hi - lo), hipMemcpyDeviceToHost));
+      for (uint32_t k : order) memcpy((uint8_t *)dst + items[k].dst_off, span.data() + (items[k].dst_off - lo), (size_t)results[k].out_size);
+   }
+   return bad;
+}
 
 extern "C" void zultra_hip_last_timing(const zultra_hip_ctx_t *c, zultra_hip_timing_t *t) {
    if (c && t) *t = c->timing;

@@ -7,9 +7,12 @@
  * block size.
  *
  *    zultra_amd_cli [-b <max block size>] [-f gzip|zlib|raw] [-k <chunk KiB>] [-d <device>] [-c] [-v] <infile> <outfile>
+ *    zultra_amd_cli -x [-f gzip|zlib|raw] [-d <device>] [-v] <infile> <outfile>
  *
  * -c: every batch is inflated on the device and compared with its input before its bytes are written (zultra_set_verify); a mismatch ends the
  *     run with a non-zero status. With -v the number of bytes checked is printed.
+ * -x: extract — <infile> is one stream in the framing -f names, inflated on the device (zultra_memory_decompress: header, checksum and the end of
+ *     the stream are checked); a stream that does not decode ends the run with a non-zero status and an empty <outfile>.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -24,10 +27,53 @@ static double now_s(void) {
    return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec;
 }
 
+/* -x: the whole file through zultra_memory_decompress. The output size is not known in advance (gzip's ISIZE is a hint, modulo 2^32): the buffer
+ * grows until the call succeeds or the bound of the format is passed (a deflate stream expands at most 1032 : 1). */
+static int extract(FILE *fin, FILE *fout, unsigned flags, int verbose) {
+   size_t n = 0, cap = (size_t)1 << 20;
+   unsigned char *in = (unsigned char *)malloc(cap);
+   for (size_t got; in && (got = fread(in + n, 1, cap - n, fin)) > 0;) {
+      n += got;
+      if (n == cap) in = (unsigned char *)realloc(in, cap *= 2);
+   }
+   if (!in) {
+      fprintf(stderr, "out of memory\n");
+      return 100;
+   }
+   const size_t bound = n * 1032 + 1024;
+   size_t room = n * 4 + 4096, size = (size_t)-1;
+   if ((flags & ZULTRA_FLAG_GZIP_FRAMING) && n >= 18) room = (size_t)in[n - 4] | ((size_t)in[n - 3] << 8) | ((size_t)in[n - 2] << 16) | ((size_t)in[n - 1] << 24);
+   const double t0 = now_s();
+   unsigned char *out = NULL;
+   for (;;) {
+      if (room > bound) room = bound;
+      free(out);
+      out = (unsigned char *)malloc(room ? room : 1);
+      if (!out) break;
+      size = zultra_memory_decompress(in, n, out, room, flags);
+      if (size != (size_t)-1 || room == bound) break;
+      room = room < 4096 ? 8192 : room * 2;
+   }
+   const double dt = now_s() - t0;
+   int rc = 0;
+   if (size == (size_t)-1) {
+      fprintf(stderr, "decompression error (a damaged stream, another framing than -f names, or no HIP device: this library has no CPU path)\n");
+      rc = 100;
+   }
+   else if (size && fwrite(out, 1, size, fout) != size) {
+      fprintf(stderr, "write error\n");
+      rc = 100;
+   }
+   if (verbose && !rc) fprintf(stdout, "%llu -> %llu bytes, %.1f MB/s\n", (unsigned long long)n, (unsigned long long)size, dt > 0 ? (double)size / dt / 1e6 : 0.0);
+   free(in);
+   free(out);
+   return rc;
+}
+
 int main(int argc, char **argv) {
    unsigned flags = ZULTRA_FLAG_GZIP_FRAMING, block = 0;
    size_t chunk = (size_t)8 << 20;
-   int verbose = 0, verify = 0, i = 1;
+   int verbose = 0, verify = 0, do_extract = 0, i = 1;
    for (; i < argc && argv[i][0] == '-' && argv[i][1]; i++) {
       if (!strcmp(argv[i], "-b") && i + 1 < argc)
          block = (unsigned)strtoul(argv[++i], NULL, 0);
@@ -41,6 +87,8 @@ int main(int argc, char **argv) {
       }
       else if (!strcmp(argv[i], "-v"))
          verbose = 1;
+      else if (!strcmp(argv[i], "-x"))
+         do_extract = 1;
       else if (!strcmp(argv[i], "-c")) {
          verify = 1;
          zultra_set_verify(1);
@@ -49,7 +97,8 @@ int main(int argc, char **argv) {
          break;
    }
    if (argc - i != 2 || chunk == 0) {
-      fprintf(stderr, "usage: %s [-b <max block size>] [-f gzip|zlib|raw] [-k <chunk KiB>] [-d <device>] [-c] [-v] <infile> <outfile>\n", argv[0]);
+      fprintf(stderr, "usage: %s [-b <max block size>] [-f gzip|zlib|raw] [-k <chunk KiB>] [-d <device>] [-c] [-v] <infile> <outfile>\n"
+                      "       %s -x [-f gzip|zlib|raw] [-d <device>] [-v] <infile> <outfile>\n", argv[0], argv[0]);
       return 100;
    }
    FILE *fin = fopen(argv[i], "rb");
@@ -62,6 +111,12 @@ int main(int argc, char **argv) {
       fprintf(stderr, "error opening '%s' for writing\n", argv[i + 1]);
       fclose(fin);
       return 100;
+   }
+   if (do_extract) {
+      const int xrc = extract(fin, fout, flags, verbose);
+      fclose(fin);
+      fclose(fout);
+      return xrc;
    }
    unsigned char *in = (unsigned char *)malloc(chunk), *out = (unsigned char *)malloc(chunk);
    zultra_stream_t strm;

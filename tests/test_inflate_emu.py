@@ -1,6 +1,7 @@
 """CPU (no GPU needed): zultra_hip_inflate_streams — the batched inflate kernel of zultra_amd/csrc/zh_inflate_out.h — and zultra_memory_decompress
 in the lock-step emulator build of the product's sources, against Python's zlib: foreign streams, hand-written token streams, the library's own
-streams device to device, bounds, corrupted streams, the host API. tests/test_inflate_gpu.py runs the same cases (tests/inflate_cases.py), larger,
+streams device to device, bounds, corrupted streams, the host API, dynamic-Huffman headers written by hand (cut at every byte, every bit flipped), seeded token streams, buffers
+that start inside a dword, stored-block edges. tests/test_inflate_gpu.py runs the same cases (tests/inflate_cases.py), larger,
 on the MI355X."""
 import ctypes
 import os
@@ -74,6 +75,35 @@ def test_truncated_streams_end_with_reason_12(emu):
 
 def test_host_api(emu):
     I.check_host_api(emu, 9000)
+
+
+def test_hand_written_dynamic_headers(emu):
+    assert I.check_dynamic_good(emu) >= 13
+
+
+def test_hand_written_bad_dynamic_headers(emu):
+    assert I.check_dynamic_bad(emu) >= 20
+
+
+def test_dynamic_headers_cut_at_every_byte(emu):
+    assert I.check_dynamic_cuts(emu) >= 1000
+
+
+def test_dynamic_headers_with_every_bit_flipped(emu):
+    n, benign = I.check_dynamic_flips(emu)
+    assert n >= 900 and benign > 0
+
+
+def test_token_stream_fuzz(emu):
+    I.check_token_fuzz(emu, 20261018, 64, 300)
+
+
+def test_unaligned_source_and_destination_pointers(emu):
+    I.check_unaligned(emu)
+
+
+def test_stored_block_edges(emu):
+    I.check_stored_edges(emu)
 
 
 def test_no_device_means_loud_failure():

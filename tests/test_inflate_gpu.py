@@ -76,6 +76,38 @@ def test_host_api(gpu):
     I.check_host_api(gpu, 100000)
 
 
+def test_hand_written_dynamic_headers(gpu):
+    assert I.check_dynamic_good(gpu) >= 13
+
+
+def test_hand_written_bad_dynamic_headers(gpu):
+    assert I.check_dynamic_bad(gpu) >= 20
+
+
+def test_dynamic_headers_cut_at_every_byte(gpu):
+    assert I.check_dynamic_cuts(gpu) >= 1000
+
+
+def test_dynamic_headers_with_every_bit_flipped(gpu):
+    n, benign = I.check_dynamic_flips(gpu)
+    assert n >= 900 and benign > 0
+
+
+def test_token_stream_fuzz(gpu, tmp_path):
+    """512 items of about 600 tokens in flight: 128 generated streams, each four times (generating 512 takes Python ten seconds)."""
+    import zultra_amd
+    made = I.check_token_fuzz(gpu, 20261018, 128, 600, copies=4)
+    I.check_token_fuzz_strided(zultra_amd.LIB_PATH, False, made, 4, tmp_path)
+
+
+def test_unaligned_source_and_destination_pointers(gpu):
+    I.check_unaligned(gpu)
+
+
+def test_stored_block_edges(gpu):
+    I.check_stored_edges(gpu)
+
+
 def test_cli_extracts(gpu, tmp_path):
     import zultra_amd
     cli = os.path.join(os.path.dirname(zultra_amd.LIB_PATH), "zultra_amd_cli")

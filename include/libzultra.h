@@ -144,6 +144,14 @@ unsigned long long zultra_verified_bytes(void);
  * number of bytes written to pOut, or (size_t)-1: a bad header, a stream that does not decode, bytes behind its end, a checksum mismatch, more
  * output than nMaxOut, no device. */
 size_t zultra_memory_decompress(const unsigned char *pIn, size_t nIn, unsigned char *pOut, size_t nMaxOut, const unsigned int nFlags);
+/* ... of a stream compressed against a preset dictionary (zultra_memory_compress_dict, zultra_stream_set_dictionary, zlib's deflateSetDictionary).
+ * Raw deflate and gzip: the dictionary is the history of the stream, as it was on the way in. zlib: a header with FDICT must carry the Adler-32 of
+ * the WHOLE dictionary as its DICTID (what zultra_frame_encode_header writes, also for dictionaries above 32 KiB), else (size_t)-1 — a wrong
+ * dictionary, or FDICT and no dictionary given; a header without FDICT ignores the dictionary, as zlib does. In every framing the last
+ * min(nDictSize, 32768) bytes are what matches can reach (include/zultra_hip.h: zultra_hip_inflate_streams_dict). pDict == NULL or nDictSize <= 0:
+ * no dictionary. Everything else as zultra_memory_decompress, which keeps rejecting FDICT. */
+size_t zultra_memory_decompress_dict(const unsigned char *pIn, size_t nIn, unsigned char *pOut, size_t nMaxOut, const unsigned int nFlags,
+                                     const void *pDict, int nDictSize);
 
 #ifdef __cplusplus
 }

@@ -233,8 +233,8 @@ float zultra_hip_last_verify_ms(const zultra_hip_ctx_t *ctx);
  * Batched inflate: many independent raw deflate streams (RFC 1951) decoded on the device, one wave64 per stream. Item i is the
  * complete stream at src + src_off (any byte address, any number of stored / fixed / dynamic blocks up to and including the block with BFINAL) and
  * is written to dst + dst_off, at most dst_cap bytes. One stream runs at the speed of ONE wave — a serial chain of tokens —, so the call pays for
- * batches of many streams (the records of a files batch); decoding one large stream in parallel is not what it does. Preset dictionaries are not
- * supported: a match that reaches in front of the item's own output fails with reason 4.
+ * batches of many streams (the records of a files batch); decoding one large stream in parallel is not what it does. Without a preset dictionary
+ * (zultra_hip_inflate_streams_dict below) a match that reaches in front of the item's own output fails with reason 4.
  *   reason   : 0 ok; as for verification where it fits — 1 header (BTYPE 3, HLIT / HDIST out of range), 2 code lengths, 3 symbol, 4 distance (no such
  *              code, symbols 30 and 31, a distance that reaches in front of the item's output), 7 stored LEN/NLEN, 12 the stream ends before its
  *              final block does (bytes behind src_size read as zero); and 13 = the output does not fit in dst_cap
@@ -255,6 +255,16 @@ typedef struct zultra_hip_inflate_result_s { uint32_t reason, blocks; uint64_t o
 int zultra_hip_inflate_streams(int device, const void *src, size_t src_size, int src_on_device, void *dst, size_t dst_size, int dst_on_device,
                                const zultra_hip_inflate_item_t *items, uint32_t n, zultra_hip_inflate_result_t *results /* host, n */,
                                float *kernel_ms /* may be NULL */);
+/* The same with ONE preset dictionary for every item of the call (records compressed against a shared dictionary: zultra_memory_compress_dict,
+ * zlib's deflateSetDictionary): the last min(dict_size, 32768) bytes of dict, at any byte address, lie in front of every item's output as history,
+ * which is what zlib's inflateSetDictionary keeps. Reason 4 is then a distance above 32768 or above out_size-so-far + that history length (zlib's
+ * "invalid distance too far back"). The history is only read. dict_on_device == 0: staged through device memory the call owns, like src; == 1: used
+ * in place, and a dictionary that overlaps an item's destination range (both on the device) is refused with -1, as is dict == NULL with
+ * dict_size > 0. dict_size == 0 (dict may be NULL) is zultra_hip_inflate_streams. Items, results, reasons and the return value are the same. */
+int zultra_hip_inflate_streams_dict(int device, const void *src, size_t src_size, int src_on_device, void *dst, size_t dst_size, int dst_on_device,
+                                    const void *dict, size_t dict_size, int dict_on_device,
+                                    const zultra_hip_inflate_item_t *items, uint32_t n, zultra_hip_inflate_result_t *results /* host, n */,
+                                    float *kernel_ms /* may be NULL */);
 
 /*
  * Many small independent inputs ("files", BASELINE.json configuration 5: 4 KiB records, each its own stream). A files

@@ -2,14 +2,20 @@
 """Times the batched inflate kernel (zh_inflate_streams, zultra_hip_inflate_streams) on a files batch of BASELINE.json configuration 5's shape:
 the batch is compressed on the device and inflated from the context's stream buffer into device memory, nothing leaves HBM. Next to it the
 verification kernel (zultra_hip_verify_device) on the same batch — the same decoder without an output path — and host zlib inflating the same
-streams on one core. One JSON line.
+streams on one core. Then the dictionary leg: the same records compressed by host zlib against one preset dictionary (zdict: the library's files
+mode has none) and inflated by zh_inflate_streams_dict (zultra_hip_inflate_streams_dict), next to the plain kernel on the same records compressed
+by host zlib without a dictionary, and host zlib with zdict on one core. One JSON line.
 
-    python tools/inflate_time.py [--files N] [--file-size BYTES] [--reps N] [--step-timeout SECONDS]
+    python tools/inflate_time.py [--files N] [--file-size BYTES] [--reps N] [--dict-size BYTES] [--step-timeout SECONDS] [--lib PATH]
 
 The steps run in this order, every GPU step in a process of its own under its own time limit; a step that fails ends the run:
     1. zultra_hip_inflate_streams from the device stream buffer (the output is read back once and compared with the input)
     2. zultra_hip_verify_device on the same batch
-    3. host zlib, one core, over the same streams (this process: it touches no GPU)"""
+    3. host zlib, one core, over the same streams (this process: it touches no GPU)
+    4. zultra_hip_inflate_streams_dict over the zdict streams, then zultra_hip_inflate_streams over the streams without a dictionary, device to
+       device (both outputs are read back once and compared with the records)
+    5. host zlib with zdict, one core, over the streams of step 4 (this process), every output compared with its record
+--lib: another build of the library (an A/B of the plain kernel against an older build); steps 4 and 5 are left out where it has no dictionary kernel."""
 import argparse
 import json
 import os
@@ -24,12 +30,19 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 
+def library(args):
+    import zultra_amd
+    if not args.lib:
+        return zultra_amd.lib()
+    from zultra_amd._ffi import Lib
+    return Lib(args.lib, allow_missing=("zultra_memory_decompress_dict", "zultra_hip_inflate_streams_dict"))
+
+
 def batch(args):
     import numpy as np
 
     import corpus
-    import zultra_amd
-    L = zultra_amd.lib()
+    L = library(args)
     if L.device_count() < 1:
         raise RuntimeError("no HIP device visible: nothing can be timed")
     L.is_emulator = False
@@ -80,9 +93,72 @@ def child_verify(args):
     return 0
 
 
+def records_and_dictionary(args):
+    """The records of configuration 5's generator and a dictionary of further records of it (so that every record finds its keys there)."""
+    import numpy as np
+
+    import corpus
+    d = np.ascontiguousarray(corpus.json_files(0, args.files, args.file_size), dtype=np.uint8)
+    more = (args.dict_size + args.file_size - 1) // args.file_size
+    dictionary = np.ascontiguousarray(corpus.json_files(args.files, more, args.file_size), dtype=np.uint8)[-args.dict_size:]
+    return d, dictionary.tobytes()
+
+
+def zlib_records(d, n, fs, dictionary):
+    """Every record as a raw deflate stream of host zlib (level 6), against the dictionary or without one -> (streams back to back, offsets[n + 1])."""
+    import numpy as np
+    raw = d.tobytes()
+    base = zlib.compressobj(6, zlib.DEFLATED, -15, 9, zlib.Z_DEFAULT_STRATEGY, zdict=dictionary) if dictionary else zlib.compressobj(6, zlib.DEFLATED, -15, 9)
+    parts = []
+    for i in range(n):
+        c = base.copy()
+        parts.append(c.compress(raw[i * fs: (i + 1) * fs]) + c.flush())
+    off = np.zeros(n + 1, dtype=np.uint64)
+    off[1:] = np.cumsum([len(p) for p in parts])
+    return np.frombuffer(b"".join(parts), dtype=np.uint8).copy(), off
+
+
+def child_dict(args):
+    import numpy as np
+
+    import inflate_cases as I
+    import verify_cases as V
+    L = library(args)
+    if L.device_count() < 1:
+        raise RuntimeError("no HIP device visible: nothing can be timed")
+    L.is_emulator = False
+    n, fs = args.files, args.file_size
+    d, dictionary = records_and_dictionary(args)
+    out = {"dict_size": len(dictionary)}
+    hist = V.DeviceCopy(L, np.frombuffer(dictionary, dtype=np.uint8).copy())
+    for leg, zdict in (("dict", dictionary), ("nodict", None)):
+        stream, off = zlib_records(d, n, fs, zdict)
+        items = np.stack([off[:-1], off[1:] - off[:-1], np.arange(n, dtype=np.uint64) * fs, np.full(n, fs, dtype=np.uint64)], axis=1)
+        src, dst = V.DeviceCopy(L, stream), V.DeviceCopy(L, np.zeros(n * fs, dtype=np.uint8))
+        times = []
+        for it in range(2 + args.reps):   # (two warm-up calls)
+            if zdict:
+                rc, res, ms = L.inflate_streams_dict(src.ptr, len(stream), dst.ptr, n * fs, hist.ptr, len(dictionary), items)
+            else:
+                rc, res, ms = L.inflate_streams(src.ptr, len(stream), dst.ptr, n * fs, items)
+            assert rc == 0, (leg, rc, res[res["reason"] != 0][:4])
+            if it >= 2:
+                times.append(ms)
+        assert I.device_read(L, dst, n * fs).tobytes() == d.tobytes(), "the inflated batch differs from the records (%s)" % leg
+        src.free()
+        dst.free()
+        out["zlib_%s_stream_bytes" % leg] = int(off[-1])
+        out["%s_inflate_kernel_ms" % leg] = {"min": min(times), "median": float(np.median(times)), "all": times}
+        if zdict:
+            np.savez(args.stream_file, stream=stream, file_off=off)
+    hist.free()
+    print(json.dumps(out), flush=True)
+    return 0
+
+
 def gpu_step(name, args):
     cmd = [sys.executable, os.path.abspath(__file__), "--child", name, "--files", str(args.files), "--file-size", str(args.file_size), "--reps", str(args.reps),
-           "--stream-file", args.stream_file]
+           "--dict-size", str(args.dict_size), "--stream-file", args.stream_file] + (["--lib", args.lib] if args.lib else [])
     r = subprocess.run(cmd, timeout=args.step_timeout, capture_output=True, text=True)
     if r.returncode != 0:
         sys.stderr.write(r.stdout + r.stderr)
@@ -96,11 +172,13 @@ def main():
     ap.add_argument("--file-size", type=int, default=4096)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--step-timeout", type=int, default=300, help="seconds every GPU step may take")
-    ap.add_argument("--child", choices=["inflate", "verify"], help="(internal) the process that opens the GPU")
+    ap.add_argument("--dict-size", type=int, default=32768, help="bytes of the dictionary leg's preset dictionary")
+    ap.add_argument("--lib", default="", help="another build of libzultra_amd.so to time instead of the tree's")
+    ap.add_argument("--child", choices=["inflate", "verify", "dict"], help="(internal) the process that opens the GPU")
     ap.add_argument("--stream-file", default="", help="(internal) where the inflate step leaves the streams for host zlib")
     args = ap.parse_args()
     if args.child:
-        sys.exit(child_inflate(args) if args.child == "inflate" else child_verify(args))
+        sys.exit({"inflate": child_inflate, "verify": child_verify, "dict": child_dict}[args.child](args))
     import numpy as np
     with tempfile.TemporaryDirectory() as tmp:
         args.stream_file = os.path.join(tmp, "streams.npz")
@@ -109,6 +187,11 @@ def main():
         out.update(gpu_step("verify", args))
         z = np.load(args.stream_file)
         stream, file_off = z["stream"].tobytes(), z["file_off"]
+        with_dict = not args.lib or hasattr(library(args).L, "zultra_hip_inflate_streams_dict")   # (loading the library opens no device)
+        if with_dict:
+            out.update(gpu_step("dict", args))
+            z = np.load(args.stream_file)
+            dstream, dict_off = z["stream"].tobytes(), z["file_off"]
     host = []
     for _ in range(3):
         t0 = time.perf_counter()
@@ -119,6 +202,19 @@ def main():
     out["inflate_over_verify"] = out["inflate_kernel_ms"]["median"] / out["verify_kernel_ms"]["median"]
     out["zlib_over_inflate"] = min(host) / out["inflate_kernel_ms"]["median"]
     out["inflate_GBps_of_output"] = out["input_bytes"] / out["inflate_kernel_ms"]["median"] / 1e6
+    if with_dict:
+        d, dictionary = records_and_dictionary(args)
+        raw, fs, host = d.tobytes(), args.file_size, []
+        for rep in range(3):
+            t0 = time.perf_counter()
+            outs = [zlib.decompressobj(-15, zdict=dictionary).decompress(dstream[int(dict_off[i]):int(dict_off[i + 1])]) for i in range(args.files)]
+            host.append(1e3 * (time.perf_counter() - t0))
+            if rep == 0:
+                assert all(o == raw[i * fs: (i + 1) * fs] for i, o in enumerate(outs)), "host zlib with zdict differs from the records"
+        out["zlib_zdict_inflate_one_core_ms"] = {"min": min(host), "all": host}
+        out["dict_over_nodict"] = out["dict_inflate_kernel_ms"]["median"] / out["nodict_inflate_kernel_ms"]["median"]
+        out["zlib_zdict_over_dict_inflate"] = min(host) / out["dict_inflate_kernel_ms"]["median"]
+        out["dict_inflate_GBps_of_output"] = out["input_bytes"] / out["dict_inflate_kernel_ms"]["median"] / 1e6
     print(json.dumps(out), flush=True)
 
 

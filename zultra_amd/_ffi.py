@@ -100,7 +100,7 @@ EXPORTS = [
     # verification
     "zultra_set_verify", "zultra_verified_bytes", "zultra_hip_verify_device", "zultra_hip_last_verify_ms", "zultra_hip_stream_write",
     # decompression
-    "zultra_memory_decompress", "zultra_hip_inflate_streams",
+    "zultra_memory_decompress", "zultra_hip_inflate_streams", "zultra_memory_decompress_dict", "zultra_hip_inflate_streams_dict",
 ]
 
 
@@ -228,6 +228,35 @@ class Lib:
         f.restype = C.c_int
         rc = f(device, int(src) if src_dev else src.ctypes.data, src_size, 1 if src_dev else 0, int(dst) if dst_dev else dst.ctypes.data, dst_size, 1 if dst_dev else 0,
                arr.ctypes.data, len(arr), res.ctypes.data, C.byref(ms))
+        return rc, res, float(ms.value)
+
+    def memory_decompress_dict(self, data, flags, max_out, dictionary):
+        """zultra_memory_decompress_dict -> the decompressed bytes, or None where the call returns (size_t)-1. dictionary: bytes / uint8 array, or
+        None (no dictionary)."""
+        data = _as_u8(data)
+        out = np.empty(max(max_out, 1), dtype=np.uint8)
+        d = None if dictionary is None else _as_u8(dictionary)
+        f = self.L.zultra_memory_decompress_dict
+        f.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint, C.c_void_p, C.c_int]
+        f.restype = C.c_size_t
+        r = f(data.ctypes.data, len(data), out.ctypes.data, max_out, flags, None if d is None or not len(d) else d.ctypes.data, 0 if d is None else len(d))
+        if r == _SIZE_MAX:
+            return None
+        return out[:r].tobytes()
+
+    def inflate_streams_dict(self, src, src_size, dst, dst_size, dictionary, dict_size, items, device=0):
+        """zultra_hip_inflate_streams_dict: inflate_streams with one preset dictionary for all items. dictionary: a uint8 array (host memory, staged
+        by the call), an integer device pointer (used in place) or None; dict_size bytes of it."""
+        arr = np.ascontiguousarray(items, dtype=np.uint64).reshape(-1, 4)
+        res = np.zeros(len(arr), dtype=[("reason", "<u4"), ("blocks", "<u4"), ("out_size", "<u8"), ("src_used", "<u8")])
+        src_dev, dst_dev = not isinstance(src, np.ndarray), not isinstance(dst, np.ndarray)
+        dict_dev = dictionary is not None and not isinstance(dictionary, np.ndarray)
+        ms = C.c_float(0)
+        f = self.L.zultra_hip_inflate_streams_dict
+        f.argtypes = [C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(C.c_float)]
+        f.restype = C.c_int
+        rc = f(device, int(src) if src_dev else src.ctypes.data, src_size, 1 if src_dev else 0, int(dst) if dst_dev else dst.ctypes.data, dst_size, 1 if dst_dev else 0,
+               None if dictionary is None else int(dictionary) if dict_dev else dictionary.ctypes.data, dict_size, 1 if dict_dev else 0, arr.ctypes.data, len(arr), res.ctypes.data, C.byref(ms))
         return rc, res, float(ms.value)
 
     def checksum(self, data, flags, start=None):

@@ -1201,8 +1201,13 @@ extern "C" size_t zultra_memory_compress(const unsigned char *pIn, size_t nIn, u
 // Decompression: the framing on the host, the deflate stream on the device (zultra_hip_inflate_streams)
 // ================================================================================================================
 
-extern "C" size_t zultra_memory_decompress(const unsigned char *pIn, size_t nIn, unsigned char *pOut, size_t nMaxOut, const unsigned int nFlags) {
+// with_dict: zultra_memory_decompress_dict (a zlib stream may carry FDICT, and pDict — NULL for none — is the history of the deflate stream)
+static size_t memory_decompress(const unsigned char *pIn, size_t nIn, unsigned char *pOut, size_t nMaxOut, const unsigned int nFlags, bool with_dict, const void *pDict, int nDictSize) {
    if (!pIn || (!pOut && nMaxOut)) return (size_t)-1;
+   if (!pDict || nDictSize <= 0) {
+      pDict = NULL;
+      nDictSize = 0;
+   }
    size_t head = 0, foot = 0;
    if (nFlags & ZULTRA_FLAG_GZIP_FRAMING) {
       // RFC 1952 2.3: ID1 ID2 CM FLG MTIME(4) XFL OS, then what FLG announces
@@ -1222,17 +1227,28 @@ extern "C" size_t zultra_memory_decompress(const unsigned char *pIn, size_t nIn,
       foot = 8;
    }
    else if (nFlags & ZULTRA_FLAG_ZLIB_FRAMING) {
-      // RFC 1950 2.2: CM = 8, CINFO <= 7, (CMF * 256 + FLG) % 31 == 0, no preset dictionary
-      if (nIn < 6 || (pIn[0] & 15) != 8 || (pIn[0] >> 4) > 7 || (((unsigned)pIn[0] << 8) | pIn[1]) % 31 || (pIn[1] & 0x20)) return (size_t)-1;
+      // RFC 1950 2.2: CM = 8, CINFO <= 7, (CMF * 256 + FLG) % 31 == 0; FDICT only where a dictionary may be given
+      if (nIn < 6 || (pIn[0] & 15) != 8 || (pIn[0] >> 4) > 7 || (((unsigned)pIn[0] << 8) | pIn[1]) % 31 || ((pIn[1] & 0x20) && !with_dict)) return (size_t)-1;
       head = 2;
       foot = 4;
+      if (pIn[1] & 0x20) {
+         // DICTID: the Adler-32 of the whole dictionary, of which the last 32768 bytes are the history (zultra_frame_encode_header writes the same)
+         if (!pDict) return (size_t)-1;
+         const uint32_t id = ((uint32_t)pIn[2] << 24) | (pIn[3] << 16) | (pIn[4] << 8) | pIn[5];
+         if (id != adler32_update(1, (const uint8_t *)pDict, (size_t)nDictSize)) return (size_t)-1;
+         head = 6;
+      }
+      else
+         nDictSize = 0;   // (no FDICT: the dictionary is not looked at, as in zlib)
    }
    if (head > nIn || foot > nIn - head || nIn - head - foot == 0) return (size_t)-1;
    const size_t nBody = nIn - head - foot;
    zultra_hip_inflate_item_t item = {0, nBody, 0, nMaxOut};
    zultra_hip_inflate_result_t res;
    unsigned char none = 0;
-   if (zultra_hip_inflate_streams(zh_pick_device(), pIn + head, nBody, 0, pOut ? pOut : &none, nMaxOut, 0, &item, 1, &res, NULL) != 0) return (size_t)-1;
+   if ((nDictSize ? zultra_hip_inflate_streams_dict(zh_pick_device(), pIn + head, nBody, 0, pOut ? pOut : &none, nMaxOut, 0, pDict, (size_t)nDictSize, 0, &item, 1, &res, NULL)
+                  : zultra_hip_inflate_streams(zh_pick_device(), pIn + head, nBody, 0, pOut ? pOut : &none, nMaxOut, 0, &item, 1, &res, NULL)) != 0)
+      return (size_t)-1;
    if (res.src_used != nBody) return (size_t)-1;   // (bytes behind the final block)
    const size_t nOut = (size_t)res.out_size;
    if (foot) {
@@ -1246,4 +1262,12 @@ extern "C" size_t zultra_memory_decompress(const unsigned char *pIn, size_t nIn,
          return (size_t)-1;
    }
    return nOut;
+}
+
+extern "C" size_t zultra_memory_decompress(const unsigned char *pIn, size_t nIn, unsigned char *pOut, size_t nMaxOut, const unsigned int nFlags) {
+   return memory_decompress(pIn, nIn, pOut, nMaxOut, nFlags, false, NULL, 0);
+}
+
+extern "C" size_t zultra_memory_decompress_dict(const unsigned char *pIn, size_t nIn, unsigned char *pOut, size_t nMaxOut, const unsigned int nFlags, const void *pDict, int nDictSize) {
+   return memory_decompress(pIn, nIn, pOut, nMaxOut, nFlags, true, pDict, nDictSize);
 }

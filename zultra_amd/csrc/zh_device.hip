@@ -1874,13 +1874,14 @@ static_assert(sizeof(zultra_hip_inflate_item_t) == sizeof(zh_inflate_item_t) && 
 
 // what a zultra_hip_inflate_streams call holds on the device: released when the call returns, however it returns
 struct zh_inflate_call_t {
-   void *d_src = NULL, *d_dst = NULL, *d_items = NULL, *d_results = NULL;
+   void *d_src = NULL, *d_dst = NULL, *d_items = NULL, *d_results = NULL, *d_hist = NULL;
    hipEvent_t ev[2] = {NULL, NULL};
    ~zh_inflate_call_t() {
       (void)hipFree(d_src);
       (void)hipFree(d_dst);
       (void)hipFree(d_items);
       (void)hipFree(d_results);
+      (void)hipFree(d_hist);
       for (int i = 0; i < 2; i++)
          if (ev[i]) (void)hipEventDestroy(ev[i]);
    }
@@ -1890,10 +1891,11 @@ struct zh_inflate_call_t {
       if ((call) != hipSuccess) return -1; \
    } while (0)
 
-// Many raw deflate streams, one wave each. No context: the call owns its item and result buffers (and, for host pointers, the staging of the source and of
-// the output in device memory), on the null stream of `device`.
-extern "C" int zultra_hip_inflate_streams(int device, const void *src, size_t src_size, int src_on_device, void *dst, size_t dst_size, int dst_on_device,
-                                          const zultra_hip_inflate_item_t *items, uint32_t n, zultra_hip_inflate_result_t *results, float *kernel_ms) {
+// Many raw deflate streams, one wave each. No context: the call owns its item and result buffers (and, for host pointers, the staging of the source, of
+// the output and of the history in device memory), on the null stream of `device`. hist_len == 0: zh_inflate_streams; else the last hist_len bytes of the
+// dictionary (`hist`, at most 32768) lie in front of every item's output, zh_inflate_streams_dict.
+static int zh_inflate_streams_call(int device, const void *src, size_t src_size, int src_on_device, void *dst, size_t dst_size, int dst_on_device, const uint8_t *hist, uint32_t hist_len,
+                                   int hist_on_device, const zultra_hip_inflate_item_t *items, uint32_t n, zultra_hip_inflate_result_t *results, float *kernel_ms) {
    ZH_EMU_SERIALIZE();
    if (kernel_ms) *kernel_ms = 0.f;
    if (!src || !dst || !items || !results || n == 0 || device < 0) return -1;
@@ -1908,6 +1910,13 @@ extern "C" int zultra_hip_inflate_streams(int device, const void *src, size_t sr
    std::sort(order.begin(), order.end(), [items](uint32_t a, uint32_t b) { return items[a].dst_off < items[b].dst_off; });
    for (size_t i = 1; i < order.size(); i++)
       if (items[order[i - 1]].dst_off + items[order[i - 1]].dst_cap > items[order[i]].dst_off) return -1;
+   if (hist_len && hist_on_device && dst_on_device) {   // the history is read while the output is written: none of it inside a destination range
+      const uintptr_t h_lo = (uintptr_t)hist, h_hi = h_lo + hist_len;
+      for (uint32_t k : order) {
+         const uintptr_t d_lo = (uintptr_t)dst + items[k].dst_off;
+         if (d_lo < h_hi && h_lo < d_lo + items[k].dst_cap) return -1;
+      }
+   }
    if (device >= zultra_hip_device_count()) return -1;
    ZH_TRY(hipSetDevice(device));
    zh_inflate_call_t C;
@@ -1925,6 +1934,11 @@ extern "C" int zultra_hip_inflate_streams(int device, const void *src, size_t sr
       ZH_TRY(hipMalloc(&C.d_dst, dst_size ? dst_size : 1));
       d8 = (uint8_t *)C.d_dst;
    }
+   if (hist_len && !hist_on_device) {
+      ZH_TRY(hipMalloc(&C.d_hist, hist_len));
+      ZH_TRY(hipMemcpy(C.d_hist, hist, hist_len, hipMemcpyHostToDevice));
+      hist = (const uint8_t *)C.d_hist;
+   }
    ZH_TRY(hipMemcpy(C.d_items, items, (size_t)n * sizeof(zh_inflate_item_t), hipMemcpyHostToDevice));
    int cus = 0;
    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus <= 0) cus = 256;
@@ -1932,7 +1946,11 @@ extern "C" int zultra_hip_inflate_streams(int device, const void *src, size_t sr
    const uint32_t grid_cap = (uint32_t)max(0, zh_env("ZULTRA_HIP_GRID_CAP", 0));   // tests: fewer waves than streams, every wave strides
    if (grid_cap) grid = max(1u, min(grid, grid_cap));
    ZH_TRY(hipEventRecord(C.ev[0], 0));
-   ZH_LAUNCH(zh_inflate_streams, grid, ZH_INFLATE_THREADS, 0, s8, (uint64_t)src_size, d8, (uint64_t)dst_size, (const zh_inflate_item_t *)C.d_items, n, (zh_inflate_result_t *)C.d_results);
+   if (hist_len)
+      ZH_LAUNCH(zh_inflate_streams_dict, grid, ZH_INFLATE_THREADS, 0, s8, (uint64_t)src_size, d8, (uint64_t)dst_size, hist + hist_len, hist_len, (const zh_inflate_item_t *)C.d_items, n,
+                (zh_inflate_result_t *)C.d_results);
+   else
+      ZH_LAUNCH(zh_inflate_streams, grid, ZH_INFLATE_THREADS, 0, s8, (uint64_t)src_size, d8, (uint64_t)dst_size, (const zh_inflate_item_t *)C.d_items, n, (zh_inflate_result_t *)C.d_results);
    ZH_TRY(hipEventRecord(C.ev[1], 0));
    ZH_TRY(hipMemcpy(results, C.d_results, (size_t)n * sizeof(zh_inflate_result_t), hipMemcpyDeviceToHost));
    ZH_TRY(hipDeviceSynchronize());
@@ -1951,6 +1969,21 @@ extern "C" int zultra_hip_inflate_streams(int device, const void *src, size_t sr
       for (uint32_t k : order) memcpy((uint8_t *)dst + items[k].dst_off, span.data() + (items[k].dst_off - lo), (size_t)results[k].out_size);
    }
    return bad;
+}
+
+extern "C" int zultra_hip_inflate_streams(int device, const void *src, size_t src_size, int src_on_device, void *dst, size_t dst_size, int dst_on_device,
+                                          const zultra_hip_inflate_item_t *items, uint32_t n, zultra_hip_inflate_result_t *results, float *kernel_ms) {
+   return zh_inflate_streams_call(device, src, src_size, src_on_device, dst, dst_size, dst_on_device, NULL, 0, 0, items, n, results, kernel_ms);
+}
+
+// ... with one preset dictionary for all items: its last min(dict_size, 32768) bytes are the history (zlib's inflateSetDictionary keeps the same).
+extern "C" int zultra_hip_inflate_streams_dict(int device, const void *src, size_t src_size, int src_on_device, void *dst, size_t dst_size, int dst_on_device, const void *dict, size_t dict_size,
+                                               int dict_on_device, const zultra_hip_inflate_item_t *items, uint32_t n, zultra_hip_inflate_result_t *results, float *kernel_ms) {
+   if (kernel_ms) *kernel_ms = 0.f;
+   if (!dict && dict_size) return -1;
+   const uint32_t hist_len = (uint32_t)zh_min64(dict_size, ZH_MAX_DIST);
+   return zh_inflate_streams_call(device, src, src_size, src_on_device, dst, dst_size, dst_on_device, dict ? (const uint8_t *)dict + (dict_size - hist_len) : NULL, hist_len, dict_on_device, items, n,
+                                  results, kernel_ms);
 }
 
 extern "C" void zultra_hip_last_timing(const zultra_hip_ctx_t *c, zultra_hip_timing_t *t) {

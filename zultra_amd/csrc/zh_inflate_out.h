@@ -12,6 +12,11 @@
 //              far matches of a text run without them;
 //   stored     a 64-lane byte copy from the stream, four loads in flight.
 //
+// The dictionary form (zh_inflate_one<true>, zh_inflate_streams_dict) puts up to 32768 bytes of read-only history in front of every item's output:
+// a source index below zero is taken from hist_end[index] instead of out[index], lane by lane, so one match may read both and may wrap while it
+// still starts in the history. Nobody stores to the history during the launch: those loads need no release / acquire and no drain, and `synced` is
+// compared, in signed arithmetic, with the end of the part of the source that lies in the output. <false> is the decoder without any of this.
+//
 // A stream may start at any byte address: the bit reader's base is that address aligned down to a dword and the first bit 8 * (address & 3). No
 // byte outside the caller's source buffer is loaded (the two edge dwords of the buffer are put together from bytes), and bytes behind the ITEM's
 // own end read as zero: a decode that wants them ends with ZH_V_STREAM_END.
@@ -141,8 +146,10 @@ __device__ __forceinline__ uint32_t zh_i_dynamic_lens(zh_v_lds_t &S, zh_v_bits_t
 }
 
 // One stream: bytes [it_lo, it_hi) from the reader's base -> out[0 .. cap). Returns the reason (wave-uniform).
-__device__ __forceinline__ uint32_t zh_inflate_one(zh_v_lds_t &S, const uint32_t *base, const zh_i_src_t s, uint64_t it_lo, uint8_t *out, uint64_t cap, uint32_t *pblocks, uint64_t *pout,
-                                                   uint64_t *pused) {
+// DICT: hist_end[-hist_len .. 0) is what lies in front of out[0] for the matches (hist_len <= ZH_MAX_DIST); without it the two are not looked at.
+template <bool DICT>
+__device__ __forceinline__ uint32_t zh_inflate_one(zh_v_lds_t &S, const uint32_t *base, const zh_i_src_t s, uint64_t it_lo, uint8_t *out, uint64_t cap, const uint8_t *hist_end, uint32_t hist_len,
+                                                   uint32_t *pblocks, uint64_t *pout, uint64_t *pused) {
    const uint32_t lane = zh_lane();
    const uint64_t end_bit = s.it_hi * 8u;
    zh_v_bits_t b;
@@ -256,20 +263,35 @@ __device__ __forceinline__ uint32_t zh_inflate_one(zh_v_lds_t &S, const uint32_t
                reason = ZH_V_STREAM_END;
             else if (sym >= 286)
                reason = ZH_V_SYMBOL;
-            else if (ds < 0 || ds >= 30 || dist > ZH_MAX_DIST || dist > p)   // (dist > p: it reaches in front of the item's output)
+            else if (ds < 0 || ds >= 30 || dist > ZH_MAX_DIST || dist > (DICT ? p + hist_len : p))   // (it reaches in front of the item's output, or of the history)
                reason = ZH_V_DISTANCE;
             else if (len > cap - p)
                reason = ZH_I_DST_FULL;
             if (reason != ZH_V_OK) break;
             zh_i_flush(out, lit_group, lit_val, lit_set);
-            const uint64_t from = p - dist;
-            if (from + (dist < len ? dist : len) > synced) {   // the source reaches into bytes stored since the last release / acquire
-               zh_wave_sync();
-               zh_stores_done();   // (for a workgroup of one wave the compiler folds the fences into nothing: the drain is asked for by name)
-               synced = p;
-            }
             const bool wraps = dist < len;
-            for (uint32_t l = lane; l < len; l += 64u) out[p + l] = out[from + (wraps ? l % dist : l)];   // (len <= 258: five rounds at most)
+            if (DICT) {
+               // the source is [from, from + min(dist, len)), from >= -hist_len: what of it lies below zero is history, which nobody stores to
+               const int64_t from = (int64_t)p - (int64_t)dist;
+               if (from + (int64_t)(wraps ? dist : len) > (int64_t)synced) {   // its part in the output reaches into bytes stored since the last release / acquire
+                  zh_wave_sync();
+                  zh_stores_done();
+                  synced = p;
+               }
+               for (uint32_t l = lane; l < len; l += 64u) {
+                  const int64_t i = from + (int64_t)(wraps ? l % dist : l);
+                  out[p + l] = i < 0 ? hist_end[i] : out[i];
+               }
+            }
+            else {
+               const uint64_t from = p - dist;
+               if (from + (wraps ? dist : len) > synced) {   // the source reaches into bytes stored since the last release / acquire
+                  zh_wave_sync();
+                  zh_stores_done();   // (for a workgroup of one wave the compiler folds the fences into nothing: the drain is asked for by name)
+                  synced = p;
+               }
+               for (uint32_t l = lane; l < len; l += 64u) out[p + l] = out[from + (wraps ? l % dist : l)];   // (len <= 258: five rounds at most)
+            }
             p += len;
          }
          if (reason != ZH_V_OK) break;
@@ -293,9 +315,9 @@ __device__ __forceinline__ uint32_t zh_inflate_one(zh_v_lds_t &S, const uint32_t
 // (149 VGPRs as the compiler allots them: three waves to a SIMD, twelve streams to a CU. Held to 128 with amdgpu_waves_per_eu(4) the kernel spills 8 bytes
 // to scratch memory, which no kernel here does.)
 #define ZH_INFLATE_THREADS 64
-__global__ void __launch_bounds__(ZH_INFLATE_THREADS)
-zh_inflate_streams(const uint8_t *src, uint64_t src_size, uint8_t *dst, uint64_t dst_size, const zh_inflate_item_t *__restrict__ items, uint32_t n, zh_inflate_result_t *__restrict__ results) {
-   __shared__ zh_v_lds_t S;
+template <bool DICT>
+__device__ __forceinline__ void zh_inflate_items(zh_v_lds_t &S, const uint8_t *src, uint64_t src_size, uint8_t *dst, uint64_t dst_size, const uint8_t *hist_end, uint32_t hist_len,
+                                                 const zh_inflate_item_t *__restrict__ items, uint32_t n, zh_inflate_result_t *__restrict__ results) {
    const uint64_t lead = (uint64_t)((uintptr_t)src & 3u);
    const uint32_t *base = (const uint32_t *)(src - lead);
    for (uint32_t k = blockIdx.x; k < n; k += gridDim.x) {
@@ -311,10 +333,22 @@ zh_inflate_streams(const uint8_t *src, uint64_t src_size, uint8_t *dst, uint64_t
          s.buf_lo = lead;
          s.buf_hi = lead + src_size;
          s.it_hi = lead + it.src_off + it.src_size;
-         r.reason = zh_inflate_one(S, base, s, lead + it.src_off, dst + it.dst_off, it.dst_cap, &r.blocks, &r.out_size, &r.src_used);
+         r.reason = zh_inflate_one<DICT>(S, base, s, lead + it.src_off, dst + it.dst_off, it.dst_cap, hist_end, hist_len, &r.blocks, &r.out_size, &r.src_used);
       }
       if (zh_lane() == 0) results[k] = r;
       zh_sync();   // (the tables in LDS are the next stream's)
    }
+}
+__global__ void __launch_bounds__(ZH_INFLATE_THREADS)
+zh_inflate_streams(const uint8_t *src, uint64_t src_size, uint8_t *dst, uint64_t dst_size, const zh_inflate_item_t *__restrict__ items, uint32_t n, zh_inflate_result_t *__restrict__ results) {
+   __shared__ zh_v_lds_t S;
+   zh_inflate_items<false>(S, src, src_size, dst, dst_size, NULL, 0, items, n, results);
+}
+// ... with one preset dictionary for every item: hist_end is the byte behind its last one (any byte address), hist_len <= 32768 of them are history.
+__global__ void __launch_bounds__(ZH_INFLATE_THREADS)
+zh_inflate_streams_dict(const uint8_t *src, uint64_t src_size, uint8_t *dst, uint64_t dst_size, const uint8_t *hist_end, uint32_t hist_len, const zh_inflate_item_t *__restrict__ items, uint32_t n,
+                        zh_inflate_result_t *__restrict__ results) {
+   __shared__ zh_v_lds_t S;
+   zh_inflate_items<true>(S, src, src_size, dst, dst_size, hist_end, hist_len < ZH_MAX_DIST ? hist_len : ZH_MAX_DIST, items, n, results);
 }
 #endif

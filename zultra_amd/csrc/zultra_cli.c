@@ -6,9 +6,12 @@
  * so that the device sees batches of many max-blocks. The bytes written are those of the reference for the same flags and
  * block size.
  *
- *    zultra_amd_cli [-b <max block size>] [-f gzip|zlib|raw] [-k <chunk KiB>] [-d <device>] [-c] [-v] <infile> <outfile>
- *    zultra_amd_cli -x [-f gzip|zlib|raw] [-d <device>] [-v] <infile> <outfile>
+ *    zultra_amd_cli [-b <max block size>] [-f gzip|zlib|raw] [-k <chunk KiB>] [-d <device>] [-D <dictionary>] [-c] [-v] <infile> <outfile>
+ *    zultra_amd_cli -x [-f gzip|zlib|raw] [-d <device>] [-D <dictionary>] [-v] <infile> <outfile>
  *
+ * -D: a preset dictionary, loaded as the reference's tool loads it (zultra_dictionary_load: the last 32 KiB of the file; tool/zultra.c -D). Compressing,
+ *     it is set before the first zultra_stream_compress (zultra_stream_set_dictionary: the history of the first max-block; a zlib header gets FDICT and
+ *     the DICTID); with -x the stream is inflated against it (zultra_memory_decompress_dict: a zlib stream's DICTID must be this dictionary's).
  * -c: every batch is inflated on the device and compared with its input before its bytes are written (zultra_set_verify); a mismatch ends the
  *     run with a non-zero status. With -v the number of bytes checked is printed.
  * -x: extract — <infile> is one stream in the framing -f names, inflated on the device (zultra_memory_decompress: header, checksum and the end of
@@ -29,7 +32,7 @@ static double now_s(void) {
 
 /* -x: the whole file through zultra_memory_decompress. The output size is not known in advance (gzip's ISIZE is a hint, modulo 2^32): the buffer
  * grows until the call succeeds or the bound of the format is passed (a deflate stream expands at most 1032 : 1). */
-static int extract(FILE *fin, FILE *fout, unsigned flags, int verbose) {
+static int extract(FILE *fin, FILE *fout, unsigned flags, int verbose, const void *dict, int dict_size) {
    size_t n = 0, cap = (size_t)1 << 20;
    unsigned char *in = (unsigned char *)malloc(cap);
    for (size_t got; in && (got = fread(in + n, 1, cap - n, fin)) > 0;) {
@@ -50,14 +53,14 @@ static int extract(FILE *fin, FILE *fout, unsigned flags, int verbose) {
       free(out);
       out = (unsigned char *)malloc(room ? room : 1);
       if (!out) break;
-      size = zultra_memory_decompress(in, n, out, room, flags);
+      size = dict ? zultra_memory_decompress_dict(in, n, out, room, flags, dict, dict_size) : zultra_memory_decompress(in, n, out, room, flags);
       if (size != (size_t)-1 || room == bound) break;
       room = room < 4096 ? 8192 : room * 2;
    }
    const double dt = now_s() - t0;
    int rc = 0;
    if (size == (size_t)-1) {
-      fprintf(stderr, "decompression error (a damaged stream, another framing than -f names, or no HIP device: this library has no CPU path)\n");
+      fprintf(stderr, "decompression error (a damaged stream, another framing than -f names, another dictionary than -D names or none, or no HIP device: this library has no CPU path)\n");
       rc = 100;
    }
    else if (size && fwrite(out, 1, size, fout) != size) {
@@ -74,6 +77,7 @@ int main(int argc, char **argv) {
    unsigned flags = ZULTRA_FLAG_GZIP_FRAMING, block = 0;
    size_t chunk = (size_t)8 << 20;
    int verbose = 0, verify = 0, do_extract = 0, i = 1;
+   const char *dict_name = NULL;
    for (; i < argc && argv[i][0] == '-' && argv[i][1]; i++) {
       if (!strcmp(argv[i], "-b") && i + 1 < argc)
          block = (unsigned)strtoul(argv[++i], NULL, 0);
@@ -85,6 +89,8 @@ int main(int argc, char **argv) {
          const char *f = argv[++i];
          flags = !strcmp(f, "gzip") ? ZULTRA_FLAG_GZIP_FRAMING : !strcmp(f, "zlib") ? ZULTRA_FLAG_ZLIB_FRAMING : ZULTRA_FLAG_DEFLATE_FRAMING;
       }
+      else if (!strcmp(argv[i], "-D") && i + 1 < argc)
+         dict_name = argv[++i];
       else if (!strcmp(argv[i], "-v"))
          verbose = 1;
       else if (!strcmp(argv[i], "-x"))
@@ -97,8 +103,15 @@ int main(int argc, char **argv) {
          break;
    }
    if (argc - i != 2 || chunk == 0) {
-      fprintf(stderr, "usage: %s [-b <max block size>] [-f gzip|zlib|raw] [-k <chunk KiB>] [-d <device>] [-c] [-v] <infile> <outfile>\n"
-                      "       %s -x [-f gzip|zlib|raw] [-d <device>] [-v] <infile> <outfile>\n", argv[0], argv[0]);
+      fprintf(stderr, "usage: %s [-b <max block size>] [-f gzip|zlib|raw] [-k <chunk KiB>] [-d <device>] [-D <dictionary>] [-c] [-v] <infile> <outfile>\n"
+                      "       %s -x [-f gzip|zlib|raw] [-d <device>] [-D <dictionary>] [-v] <infile> <outfile>\n", argv[0], argv[0]);
+      return 100;
+   }
+   void *dict = NULL;
+   int dict_size = 0;
+   if (dict_name && (zultra_dictionary_load(dict_name, &dict, &dict_size) != ZULTRA_OK || dict_size <= 0)) {
+      fprintf(stderr, "error loading dictionary '%s'\n", dict_name);
+      zultra_dictionary_free(&dict);
       return 100;
    }
    FILE *fin = fopen(argv[i], "rb");
@@ -113,9 +126,10 @@ int main(int argc, char **argv) {
       return 100;
    }
    if (do_extract) {
-      const int xrc = extract(fin, fout, flags, verbose);
+      const int xrc = extract(fin, fout, flags, verbose, dict, dict_size);
       fclose(fin);
       fclose(fout);
+      zultra_dictionary_free(&dict);
       return xrc;
    }
    unsigned char *in = (unsigned char *)malloc(chunk), *out = (unsigned char *)malloc(chunk);
@@ -123,6 +137,10 @@ int main(int argc, char **argv) {
    memset(&strm, 0, sizeof(strm));
    if (!in || !out || zultra_stream_init(&strm, flags, block) != ZULTRA_OK) {
       fprintf(stderr, "error initializing compressor (no HIP device? this library has no CPU path)\n");
+      return 100;
+   }
+   if (dict && zultra_stream_set_dictionary(&strm, dict, dict_size) != ZULTRA_OK) {
+      fprintf(stderr, "error setting the dictionary\n");
       return 100;
    }
    const double t0 = now_s();
@@ -154,6 +172,7 @@ int main(int argc, char **argv) {
    if (verbose && verify && !rc) fprintf(stdout, "verified %llu bytes on the device\n", zultra_verified_bytes());
    zultra_stream_end(&strm);
    zultra_release_cached_contexts();
+   zultra_dictionary_free(&dict);
    free(in);
    free(out);
    fclose(fin);

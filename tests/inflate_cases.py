@@ -692,7 +692,7 @@ SMALL_LIT = _lens_of([(ord("a"), 2), (ord("b"), 2), (256, 2), (257, 2)], 258)   
 
 
 def _ladder(name, dist_order, far):
-    """The 15-bit literal z, the 15-bit length symbol 285 and a 15-bit distance code; every code of more than 9 / 8 bits takes zh_v_sym's walk."""
+    """The 15-bit literal z, the 15-bit length symbol 285 and a 15-bit distance code; every code of more than 9 / 8 bits takes zh_d_sym's walk."""
     w = DynWriter()
     dist_lens = ladder_lens(dist_order, max(dist_order) + 1)
     w.begin_dynamic(True, ladder_lens(LADDER_LIT, 286), dist_lens)

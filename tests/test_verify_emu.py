@@ -1,4 +1,4 @@
-"""CPU (no GPU needed): zultra_hip_verify_device — the inflate-and-compare kernel of zultra_amd/csrc/zh_inflate.h — in the lock-step emulator
+"""CPU (no GPU needed): zultra_hip_verify_device — the inflate-and-compare kernel of zultra_amd/csrc/zh_verify.h — in the lock-step emulator
 build of the product's sources: clean streams verify, corrupted streams get host zlib's verdict and the right sub-block, and the host API
 verifies every batch when asked. tests/test_verify_gpu.py runs the same cases, larger, on the MI355X."""
 import os
@@ -104,6 +104,13 @@ def test_targeted_flips_get_zlibs_verdict(emu):
     """BFINAL of a middle and of the last sub-block, both BTYPE bits, HLIT / HDIST / HCLEN, a stored LEN and NLEN bit, a stored byte, the last valid bit."""
     n, _ = V.check_flips(emu, "text_noise_text", lambda: V.text_noise_text(2000, 2000), 2000, 32768, 4, False, seed=7, targeted=True)
     assert n >= 4 + 11
+
+
+def test_flip_reports_are_the_recorded_ones(emu):
+    """reason, sub-block, input offset and stream bit of every report for the fixed flips of verify_cases.flip_reports (the end of the data and the
+    last sub-block's header among them) are those of tests/golden/verify_flip_reports.json, recorded before the decoder was shared with the inflate
+    kernels."""
+    V.check_flip_reports(emu)
 
 
 def test_host_api_verifies_every_batch(emu, monkeypatch):

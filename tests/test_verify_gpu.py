@@ -1,4 +1,4 @@
-"""GPU (MI355X): zultra_hip_verify_device — the inflate-and-compare kernel of zultra_amd/csrc/zh_inflate.h — in the product library: clean streams
+"""GPU (MI355X): zultra_hip_verify_device — the inflate-and-compare kernel of zultra_amd/csrc/zh_verify.h — in the product library: clean streams
 verify, corrupted streams get host zlib's verdict and the right sub-block, the host API and the command-line tool verify every batch when asked.
 The cases are those of tests/test_verify_emu.py at full size (tests/verify_cases.py)."""
 import os
@@ -99,6 +99,13 @@ def test_targeted_flips_get_zlibs_verdict(gpu):
     """BFINAL of a middle and of the last sub-block, both BTYPE bits, HLIT / HDIST / HCLEN, a stored LEN and NLEN bit, a stored byte, the last valid bit."""
     n, _ = V.check_flips(gpu, "text_noise_text", lambda: V.text_noise_text(65536, 32768), 32768, 32768, 20, False, seed=7, targeted=True)
     assert n >= 20 + 11
+
+
+def test_flip_reports_are_the_recorded_ones(gpu):
+    """reason, sub-block, input offset and stream bit of every report for the fixed flips of verify_cases.flip_reports (the end of the data and the
+    last sub-block's header among them) are those of tests/golden/verify_flip_reports.json, recorded before the decoder was shared with the inflate
+    kernels."""
+    V.check_flip_reports(gpu)
 
 
 def _uneven_stream(lib, d, flags, bs):

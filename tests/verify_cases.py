@@ -1,14 +1,22 @@
 """Shared by tests/test_verify_emu.py (CPU emulator build) and tests/test_verify_gpu.py (product library on the MI355X): the inputs, the
 batch builder and the checks of zultra_hip_verify_device. Both files run the same generators; the emulator takes smaller windows."""
 import ctypes as C
+import json
+import os
+import sys
 import zlib
 
 import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+if __name__ == "__main__":   # (the recorder at the end of the file: no conftest has set the path up)
+    sys.path[:0] = [os.path.dirname(HERE), os.path.join(HERE, "emu")]
 
 import corpus
 from zultra_amd._ffi import Block
 
 HISTORY = 32768
+FLIP_REPORTS = os.path.join(HERE, "golden", "verify_flip_reports.json")
 
 
 def many_splits(stretch):
@@ -300,3 +308,96 @@ def check_files(lib, nrecords):
         assert ctx.verify()["rc"] == 0
     finally:
         ctx.close()
+
+
+def _flip_rows(ctx, subs, starts, end_bit, seed):
+    """The fixed list of single-bit flips of flip_reports over the stitched stream in `ctx`, one verify call each:
+    [[bit, rc, reason, first_bad, block, input_off, stream_bit]] and the clean stream's CRC-32."""
+    nbytes = (end_bit + 7) // 8
+    clean = ctx.stream_read(nbytes).copy()
+    assert ctx.verify()["rc"] == 0
+    assert nbytes > 8 and starts[-1] + 24 <= end_bit
+    bits = sorted(targeted_bits(subs, starts, end_bit).values())
+    bits += [int(b) for b in np.random.RandomState(seed).randint(0, end_bit, size=200)]
+    bits += range(8 * (nbytes - 8), 8 * nbytes)      # the end of the data (the pad bits of the last byte included) ...
+    bits += range(starts[-1], starts[-1] + 24)       # ... and the last sub-block's header: where the order of the decoder's verdicts shows
+    rows = []
+    for bit in bits:
+        at = bit >> 3
+        ctx.stream_write(clean[at: at + 1] ^ np.uint8(1 << (bit & 7)), at)
+        r = ctx.verify()
+        ctx.stream_write(clean[at: at + 1], at)
+        rows.append([bit] + [r[k] for k in ("rc", "reason", "first_bad", "block", "input_off", "stream_bit")])
+    assert ctx.verify()["rc"] == 0   # (the buffer is restored)
+    return {"end_bit": end_bit, "crc32": zlib.crc32(clean.tobytes()), "rows": rows}
+
+
+def flip_reports(lib):
+    """The whole report of zultra_hip_verify_device — not only its verdict — for a fixed, seeded list of single-bit flips of two small streams: the one
+    of test_targeted_flips_get_zlibs_verdict in the emulator's size (dynamic and stored sub-blocks) and a files batch of two 4 KiB records and inputs
+    of 1, 2 and 8191 bytes. -> {stream name: {"end_bit", "crc32" of the clean stream, "rows"}}; tests/golden/verify_flip_reports.json holds what the
+    decoder said before zh_deflate_dec.h was shared between the verify and the inflate kernels."""
+    out = {}
+    data = np.ascontiguousarray(text_noise_text(2000, 2000), dtype=np.uint8)
+    blocks = stream_blocks(len(data), 2000)
+    ctx = lib.context(32768, len(blocks))
+    try:
+        compress(lib, ctx, data, blocks, 0)
+        end_bit, _ = ctx.stitch_device(len(blocks) - 1, 0)
+        subs, _, cnt = ctx.subblocks()
+        starts, planned_end = plan(subs, 32768, 0)
+        assert planned_end == end_bit and cnt >= 3
+        assert {"hlit", "stored_len"} <= set(targeted_bits(subs, starts, end_bit))
+        out["targeted"] = _flip_rows(ctx, subs, starts, end_bit, 20260117)
+    finally:
+        ctx.close()
+    sizes = [4096, 4096, 1, 2, 8191]
+    data = np.concatenate([corpus.json_like(4096, 10), corpus.json_like(4096, 11), corpus.text_like(1, 2), corpus.text_like(2, 3), corpus.json_like(8191, 4)])
+    offsets = np.concatenate([[0], np.cumsum(sizes)[:-1]]).astype(np.uint64)
+    ctx = lib.files_context(8191, len(sizes))
+    try:
+        file_off = ctx.compress_files(data, offsets, sizes)
+        subs, _, cnt = ctx.subblocks()
+        starts = []
+        for f in range(len(sizes)):   # every file is a stream of its own, from a byte boundary
+            s, end = plan([sb for sb in subs if sb.block == f], 8191, 0)
+            starts += [8 * int(file_off[f]) + b for b in s]
+            assert int(file_off[f]) + (end + 7) // 8 == int(file_off[f + 1])
+        assert len(starts) == cnt
+        out["files"] = _flip_rows(ctx, subs, starts, 8 * int(file_off[-1]), 20260118)
+    finally:
+        ctx.close()
+    return out
+
+
+def check_flip_reports(lib):
+    """The build under test gives the recorded reports, field for field."""
+    with open(FLIP_REPORTS) as f:
+        want = json.load(f)["streams"]
+    got = flip_reports(lib)
+    assert sorted(got) == sorted(want)
+    for name in sorted(want):
+        assert (got[name]["end_bit"], got[name]["crc32"]) == (want[name]["end_bit"], want[name]["crc32"]), "%s: the compressor's stream is another one" % name
+        assert len(got[name]["rows"]) == len(want[name]["rows"])
+        for g, w in zip(got[name]["rows"], want[name]["rows"]):
+            assert g == w, "%s: bit, rc, reason, first_bad, block, input_off, stream_bit: got %s, recorded %s" % (name, g, w)
+
+
+if __name__ == "__main__":
+    # python tests/verify_cases.py --record PATH [SOURCE]: the reports of this tree's emulator build, written as the golden file. SOURCE says which
+    # commit the tree is (the file is recorded from the commit BEFORE a change to the decoder, never from the code under test).
+    assert len(sys.argv) in (3, 4) and sys.argv[1] == "--record", "usage: verify_cases.py --record PATH [SOURCE]"
+    import build_emu
+    from zultra_amd._ffi import Lib
+    emu = Lib(build_emu.build())
+    emu.is_emulator = True
+    streams = flip_reports(emu)
+    with open(sys.argv[2], "w") as f:
+        f.write('{"recorded_from": %s,\n "row": ["bit", "rc", "reason", "first_bad", "block", "input_off", "stream_bit"],\n "streams": {\n' % json.dumps(sys.argv[3] if len(sys.argv) == 4 else "unnamed tree"))
+        for i, name in enumerate(sorted(streams)):
+            s = streams[name]
+            f.write('  %s: {"end_bit": %d, "crc32": %d, "rows": [\n' % (json.dumps(name), s["end_bit"], s["crc32"]))
+            f.write(",\n".join("   " + json.dumps(r) for r in s["rows"]))
+            f.write("]}%s\n" % ("," if i + 1 < len(streams) else ""))
+        f.write(" }}\n")
+    print("%s: %s" % (sys.argv[2], ", ".join("%s %d rows" % (k, len(v["rows"])) for k, v in sorted(streams.items()))))

@@ -2,10 +2,11 @@
 """Times the verification kernel (zh_verify_subblocks, zultra_hip_verify_device) on a benchmark configuration's batch, next to the batch's own
 step time from the same context and to host zlib inflating the same stream on one core — the check the reference tool offers. One JSON line.
 
-    python tools/verify_time.py [--config 1|2|3|4|5] [--size BYTES] [--reps N]
+    python tools/verify_time.py [--config 1|2|3|4|5] [--size BYTES] [--reps N] [--lib PATH]
 
 Configurations 2-4 are one stream of max-blocks (4: 256 MiB of its GiB unless --size says otherwise), 1 is the one small file as one max-block, 5 one
 batch of 65 536 inputs of 4 KiB in files mode. The exit status is 1 when the kernel is not faster than host zlib's inflate — the acceptance of the check.
+--lib: another build of the library (an A/B of the kernel against an older build, as in tools/inflate_time.py); the line then names it as "lib".
 
 The process that is started touches no GPU: like bench.py it hands the work to a child process, and only the child opens the device."""
 import argparse
@@ -53,7 +54,11 @@ def child(args):
     d = np.ascontiguousarray(d, dtype=np.uint8)
     nb = (len(d) + bs - 1) // bs
     blocks = [(b * bs - (32768 if b else 0), 32768 if b else 0, min(bs, len(d) - b * bs)) for b in range(nb)]
-    L = zultra_amd.lib()
+    if args.lib:
+        from zultra_amd._ffi import Lib
+        L = Lib(args.lib, allow_missing=("zultra_memory_decompress_dict", "zultra_hip_inflate_streams_dict"))
+    else:
+        L = zultra_amd.lib()
     if L.device_count() < 1:
         raise RuntimeError("no HIP device visible: nothing can be timed")
     hip = None
@@ -107,7 +112,7 @@ def child(args):
         "zlib_inflate_one_core_ms": {"min": min(inflate), "all": inflate},
         "verify_over_step": float(np.median(verifies)) / float(np.median(steps)),
         "verify_below_zlib_inflate": below,
-        "csrc_digest": zultra_amd.csrc_digest(),
+        "csrc_digest": zultra_amd.csrc_digest(), "lib": args.lib or "this tree",
     }), flush=True)
     return 0 if below and rep["rc"] == 0 else 1
 
@@ -117,6 +122,7 @@ def main():
     ap.add_argument("--config", type=int, default=2, choices=[1, 2, 3, 4, 5])
     ap.add_argument("--size", type=int, default=0, help="bytes (default: the configuration's own; configuration 4: 256 MiB)")
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--lib", default="", help="another build of libzultra_amd.so to time instead of the tree's")
     ap.add_argument("--child", action="store_true", help="(internal) the process that opens the GPU")
     args = ap.parse_args()
     if args.child:

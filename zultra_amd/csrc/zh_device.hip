@@ -36,7 +36,7 @@
 #include "zh_parse_lanes.h"
 #include "zh_split.h"
 #include "zh_stitch.h"
-#include "zh_inflate.h"
+#include "zh_verify.h"
 #include "zh_inflate_out.h"
 
 #ifdef ZH_EMU
@@ -206,7 +206,7 @@ struct zultra_hip_ctx_s {
    uint32_t *d_task_prefix, *h_task_prefix;   // files mode: exclusive prefix of the inputs' task counts, computed by the host from the sizes it was handed (zh_plan_files); B + 1 entries
    uint32_t *d_stream;        // stitched deflate bits of the last batch
    size_t stream_cap;         // bytes
-   // verification (zh_inflate.h, zultra_hip_verify_device): what is allocated on the first call, and whether the stream buffer holds a stitched batch
+   // verification (zh_verify.h, zultra_hip_verify_device): what is allocated on the first call, and whether the stream buffer holds a stitched batch
    zh_verify_item_t *d_vitems;
    zh_verify_report_t *d_vreport, *h_vreport;
    hipEvent_t ev_verify[2];
@@ -1817,7 +1817,7 @@ extern "C" int zultra_hip_stream_write(zultra_hip_ctx_t *c, const void *in, size
    return 0;
 }
 
-// Inflate-and-compare of the stream the last stitch left in the stream buffer (zh_inflate.h): one wave per sub-block on the context's stream — the stitch
+// Inflate-and-compare of the stream the last stitch left in the stream buffer (zh_verify.h): one wave per sub-block on the context's stream — the stitch
 // has been waited for, whichever stream it ran on —, the 16 bytes of the batch report read back, the first bad item's record only where there is one.
 // What it needs beyond the stitch's own buffers (24 bytes per sub-block, two events) is allocated by the first call: a context that is never asked
 // holds nothing for it.
@@ -1841,7 +1841,7 @@ extern "C" int zultra_hip_verify_device(zultra_hip_ctx_t *c, zultra_hip_verify_t
    ZH_CHECK(c, hipMemsetAsync(c->d_vreport, 0, sizeof(zh_verify_report_t), st));
    ZH_CHECK(c, hipMemsetAsync(&c->d_vreport->first_bad, 0xff, sizeof(uint32_t), st));
    ZH_CHECK(c, hipEventRecord(c->ev_verify[0], st));
-   const uint32_t grid = (uint32_t)zh_min64(c->nsubs, zh_max64(12ull * c->total_cus, 64));   // (one wave per workgroup, three to a SIMD — zh_inflate.h: a CU holds 12; more would only queue)
+   const uint32_t grid = (uint32_t)zh_min64(c->nsubs, zh_max64(12ull * c->total_cus, 64));   // (one wave per workgroup, three to a SIMD — zh_verify.h: a CU holds 12; more would only queue)
    ZH_LAUNCH(zh_verify_subblocks, grid, ZH_VERIFY_THREADS, st, (const uint32_t *)c->d_stream, (uint64_t)c->stream_cap, (const zh_stitch_item_t *)c->d_items,
              (const zh_subblock_t *)c->d_results_compact, (const zh_block_t *)c->d_blocks, c->nblocks, c->cur_data, (const zh_scan_out_t *)c->d_scan_out, (const uint64_t *)c->d_file_off, files,
              c->d_vitems, c->d_vreport);

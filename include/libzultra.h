@@ -152,6 +152,14 @@ size_t zultra_memory_decompress(const unsigned char *pIn, size_t nIn, unsigned c
  * no dictionary. Everything else as zultra_memory_decompress, which keeps rejecting FDICT. */
 size_t zultra_memory_decompress_dict(const unsigned char *pIn, size_t nIn, unsigned char *pOut, size_t nMaxOut, const unsigned int nFlags,
                                      const void *pDict, int nDictSize);
+/* n members of ONE framing in one call (include/zultra_hip.h: zultra_hip_inflate_members — headers, inflate, checksums and trailers on the device),
+ * each complete in pIn at pInOff[i] .. + pInSize[i], decoded to pOut + pOutOff[i] (at most pOutCap[i] bytes; the ranges must not overlap);
+ * pOutSize[i] = bytes written or (size_t)-1. Returns the number of members that failed, (size_t)-1 for bad arguments or no device. A member must
+ * fill its range of pIn exactly (bytes behind its trailer fail it). Two differences from calling zultra_memory_decompress_dict member by member: a
+ * gzip header's FHCRC is checked, and with a dictionary a zlib member WITHOUT FDICT fails (put such members into a call without one). */
+size_t zultra_memory_decompress_batch(const unsigned char *pIn, size_t nIn, const size_t *pInOff, const size_t *pInSize, unsigned char *pOut, size_t nMaxOut,
+                                      const size_t *pOutOff, const size_t *pOutCap, size_t *pOutSize, size_t n, const unsigned int nFlags,
+                                      const void *pDict, int nDictSize);
 
 #ifdef __cplusplus
 }

@@ -267,6 +267,43 @@ int zultra_hip_inflate_streams_dict(int device, const void *src, size_t src_size
                                     float *kernel_ms /* may be NULL */);
 
 /*
+ * Batched inflate of gzip (RFC 1952) and zlib (RFC 1950) MEMBERS with the checks on the device: item i holds one member — header,
+ * deflate stream, trailer — at src + src_off; its bytes are decoded to dst + dst_off and their CRC-32 / Adler-32 is taken there and compared with the
+ * trailer. Nothing but the results crosses to the host. Three launches on one stream, one synchronisation: zh_frame_heads parses the headers and
+ * writes the items of the inflate kernel, zh_inflate_streams[_dict] decodes, zh_check_members sums the output and reads the trailers.
+ *   framing  : 0 (raw: exactly zultra_hip_inflate_streams[_dict]'s results, head_size = check = 0), ZULTRA_FLAG_ZLIB_FRAMING or ZULTRA_FLAG_GZIP_FRAMING
+ *              (libzultra.h) for ALL items of the call; both bits, or any other bit, is -1
+ *   reason   : in this order — 14 the header (gzip: magic, CM, a reserved FLG bit, FHCRC; zlib: CM, CINFO > 7, the CMF/FLG check, FDICT / DICTID; a
+ *              header that does not end inside the item); 1..13 the inflate kernel's own reason, out_size as it left it; 12 also where the
+ *              trailer does not fit in the item (the member is cut off); 15 the checksum of the output differs from the trailer's; 16 gzip's ISIZE
+ *              differs from out_size mod 2^32
+ *   src_used : header + deflate stream + trailer. Bytes of the item behind the member's trailer are NOT an error: compare src_used with src_size, or
+ *              walk a concatenation of gzip members call by call
+ *   head_size: bytes of header; check: the checksum COMPUTED over the output, whenever the stream decoded (0 for raw)
+ * gzip: FEXTRA, FNAME and FCOMMENT are skipped, and FHCRC is CHECKED — the low 16 bits of the CRC-32 of the header bytes in front of it, as zlib's
+ * inflate does. This is stricter than zultra_memory_decompress, which skips the two bytes.
+ * zlib: a header with FDICT must carry the Adler-32 of the WHOLE dictionary as its DICTID (the library's convention, libzultra.h); FDICT without a
+ * dictionary, or another DICTID, is 14. And where the call HAS a dictionary a zlib item WITHOUT FDICT is 14 as well — unlike
+ * zultra_memory_decompress_dict, which ignores the dictionary for such a stream: the dictionary kernel has one history length per launch, and
+ * decoding the item with the history visible would accept "distance too far back" streams that zlib rejects. Such items belong in a call without a
+ * dictionary. Raw and gzip items take the dictionary as history, as in zultra_hip_inflate_streams_dict.
+ * Items, argument checks, the *_on_device meanings, the dictionary rules and the return value (items with reason != 0; -1 for bad arguments and HIP
+ * errors) are those of zultra_hip_inflate_streams_dict. kernel_ms (may be NULL): device time of the three launches — frame, inflate, check.
+ */
+#define ZULTRA_HIP_INFLATE_BAD_FRAME 14
+#define ZULTRA_HIP_INFLATE_BAD_CHECK 15
+#define ZULTRA_HIP_INFLATE_BAD_ISIZE 16
+typedef struct zultra_hip_member_result_s {
+   uint32_t reason, blocks;
+   uint64_t out_size, src_used;
+   uint32_t head_size, check;
+} zultra_hip_member_result_t;
+int zultra_hip_inflate_members(int device, const void *src, size_t src_size, int src_on_device, void *dst, size_t dst_size, int dst_on_device,
+                               const void *dict, size_t dict_size, int dict_on_device, unsigned int framing,
+                               const zultra_hip_inflate_item_t *items, uint32_t n, zultra_hip_member_result_t *results /* host, n */,
+                               float *kernel_ms /* [3], may be NULL */);
+
+/*
  * Many small independent inputs ("files", BASELINE.json configuration 5: 4 KiB records, each its own stream). A files
  * context takes inputs below 8192 bytes — the splitter never cuts those (blockdeflate.c:646), so a batch needs no host
  * decision and its whole kernel sequence is replayed from one captured hipGraph. zultra_hip_compress_files runs

@@ -4,7 +4,10 @@ the batch is compressed on the device and inflated from the context's stream buf
 verification kernel (zultra_hip_verify_device) on the same batch — the same decoder without an output path — and host zlib inflating the same
 streams on one core. Then the dictionary leg: the same records compressed by host zlib against one preset dictionary (zdict: the library's files
 mode has none) and inflated by zh_inflate_streams_dict (zultra_hip_inflate_streams_dict), next to the plain kernel on the same records compressed
-by host zlib without a dictionary, and host zlib with zdict on one core. One JSON line.
+by host zlib without a dictionary, and host zlib with zdict on one core. Then the members leg: the library's own raw streams of the first batch with
+gzip framing put around them on the host, and as a second variant with zlib framing, inflated and CHECKED device to device by
+zultra_hip_inflate_members (zh_frame_heads, the inflate kernel, zh_check_members: three kernel times), next to zultra_hip_inflate_streams on the
+bare streams and host zlib.crc32 / zlib.adler32 over the output on one core, all in one process. One JSON line.
 
     python tools/inflate_time.py [--files N] [--file-size BYTES] [--reps N] [--dict-size BYTES] [--step-timeout SECONDS] [--lib PATH]
 
@@ -15,8 +18,12 @@ The steps run in this order, every GPU step in a process of its own under its ow
     4. zultra_hip_inflate_streams_dict over the zdict streams, then zultra_hip_inflate_streams over the streams without a dictionary, device to
        device (both outputs are read back once and compared with the records)
     5. host zlib with zdict, one core, over the streams of step 4 (this process), every output compared with its record
---lib: another build of the library (an A/B of the plain kernel against an older build); steps 4 and 5 are left out where it has no dictionary kernel."""
+    6. zultra_hip_inflate_members over the gzip members, then over the zlib members, device to device; zultra_hip_inflate_streams over the bare
+       streams; zlib.crc32 and zlib.adler32 over the output on one core (the outputs are read back once and compared with the input)
+--lib: another build of the library (an A/B of the plain kernel against an older build); steps 4 and 5 are left out where it has no dictionary kernel,
+step 6 where it has no members call."""
 import argparse
+import ctypes as C
 import json
 import os
 import subprocess
@@ -35,7 +42,7 @@ def library(args):
     if not args.lib:
         return zultra_amd.lib()
     from zultra_amd._ffi import Lib
-    return Lib(args.lib, allow_missing=("zultra_memory_decompress_dict", "zultra_hip_inflate_streams_dict"))
+    return Lib(args.lib, allow_missing=("zultra_memory_decompress_dict", "zultra_hip_inflate_streams_dict", "zultra_memory_decompress_batch", "zultra_hip_inflate_members"))
 
 
 def batch(args):
@@ -156,6 +163,65 @@ def child_dict(args):
     return 0
 
 
+def child_members(args):
+    import numpy as np
+
+    import inflate_cases as I
+    import verify_cases as V
+    L, ctx, d, file_off = batch(args)
+    n, fs = args.files, args.file_size
+    raw = d.tobytes()
+    stream = ctx.stream_read(int(file_off[-1])).tobytes()
+    bare = np.stack([file_off[:-1], file_off[1:] - file_off[:-1], np.arange(n, dtype=np.uint64) * fs, np.full(n, fs, dtype=np.uint64)], axis=1)
+    dst = V.DeviceCopy(L, np.zeros(n * fs, dtype=np.uint8))
+    out, times = {}, []
+    for it in range(2 + args.reps):   # (two warm-up calls)
+        rc, res, ms = L.inflate_streams(ctx.stream_ptr(), int(file_off[-1]), dst.ptr, n * fs, bare)
+        assert rc == 0, (rc, res[res["reason"] != 0][:4])
+        if it >= 2:
+            times.append(ms)
+    out["bare_inflate_kernel_ms"] = {"min": min(times), "median": float(np.median(times)), "all": times}
+    ctx.close()
+    for leg, framing, head in (("gzip", 2, b"\x1f\x8b\x08\x00\x00\x00\x00\x00\x00\x03"), ("zlib", 1, b"\x78\x9c")):
+        parts, sums = [], []
+        for i in range(n):
+            rec = raw[i * fs: (i + 1) * fs]
+            sums.append(zlib.crc32(rec) if framing == 2 else zlib.adler32(rec))
+            foot = sums[-1].to_bytes(4, "little") + fs.to_bytes(4, "little") if framing == 2 else sums[-1].to_bytes(4, "big")
+            parts.append(head + stream[int(file_off[i]): int(file_off[i + 1])] + foot)
+        off = np.zeros(n + 1, dtype=np.uint64)
+        off[1:] = np.cumsum([len(p) for p in parts])
+        members = np.frombuffer(b"".join(parts), dtype=np.uint8).copy()
+        items = np.stack([off[:-1], off[1:] - off[:-1], np.arange(n, dtype=np.uint64) * fs, np.full(n, fs, dtype=np.uint64)], axis=1)
+        src = V.DeviceCopy(L, members)
+        assert V._Hip.lib().hipMemset(C.c_void_p(dst.ptr), 0, C.c_size_t(n * fs)) == 0
+        times = []
+        for it in range(2 + args.reps):
+            rc, res, ms = L.inflate_members(src.ptr, len(members), dst.ptr, n * fs, None, 0, framing, items)
+            assert rc == 0, (leg, rc, res[res["reason"] != 0][:4])
+            if it >= 2:
+                times.append(ms)
+        assert (res["check"] == np.array(sums, dtype=np.uint32)).all() and (res["src_used"] == items[:, 1]).all(), leg
+        assert I.device_read(L, dst, n * fs).tobytes() == raw, "the inflated batch differs from the input (%s)" % leg
+        src.free()
+        med = [float(np.median([t[k] for t in times])) for k in range(3)]
+        out["%s_members_kernel_ms" % leg] = {"frame": med[0], "inflate": med[1], "check": med[2], "all": times}
+        host = []
+        for _ in range(3):
+            t0 = time.perf_counter()
+            f = zlib.crc32 if framing == 2 else zlib.adler32
+            got = [f(raw[i * fs: (i + 1) * fs]) for i in range(n)]
+            host.append(1e3 * (time.perf_counter() - t0))
+        assert got == sums
+        out["%s_host_checksum_one_core_ms" % leg] = {"min": min(host), "all": host}
+        out["%s_frame_and_check_over_inflate" % leg] = (med[0] + med[2]) / med[1]
+        out["%s_frame_and_check_over_bare_inflate" % leg] = (med[0] + med[2]) / out["bare_inflate_kernel_ms"]["median"]
+        out["%s_host_checksum_over_frame_and_check" % leg] = min(host) / (med[0] + med[2])
+    dst.free()
+    print(json.dumps(out), flush=True)
+    return 0
+
+
 def gpu_step(name, args):
     cmd = [sys.executable, os.path.abspath(__file__), "--child", name, "--files", str(args.files), "--file-size", str(args.file_size), "--reps", str(args.reps),
            "--dict-size", str(args.dict_size), "--stream-file", args.stream_file] + (["--lib", args.lib] if args.lib else [])
@@ -174,11 +240,11 @@ def main():
     ap.add_argument("--step-timeout", type=int, default=300, help="seconds every GPU step may take")
     ap.add_argument("--dict-size", type=int, default=32768, help="bytes of the dictionary leg's preset dictionary")
     ap.add_argument("--lib", default="", help="another build of libzultra_amd.so to time instead of the tree's")
-    ap.add_argument("--child", choices=["inflate", "verify", "dict"], help="(internal) the process that opens the GPU")
+    ap.add_argument("--child", choices=["inflate", "verify", "dict", "members"], help="(internal) the process that opens the GPU")
     ap.add_argument("--stream-file", default="", help="(internal) where the inflate step leaves the streams for host zlib")
     args = ap.parse_args()
     if args.child:
-        sys.exit({"inflate": child_inflate, "verify": child_verify, "dict": child_dict}[args.child](args))
+        sys.exit({"inflate": child_inflate, "verify": child_verify, "dict": child_dict, "members": child_members}[args.child](args))
     import numpy as np
     with tempfile.TemporaryDirectory() as tmp:
         args.stream_file = os.path.join(tmp, "streams.npz")
@@ -192,6 +258,9 @@ def main():
             out.update(gpu_step("dict", args))
             z = np.load(args.stream_file)
             dstream, dict_off = z["stream"].tobytes(), z["file_off"]
+        with_members = not args.lib or hasattr(library(args).L, "zultra_hip_inflate_members")
+        if with_members:
+            out.update(gpu_step("members", args))
     host = []
     for _ in range(3):
         t0 = time.perf_counter()

@@ -81,6 +81,14 @@ class InflateResult(C.Structure):
     _fields_ = [("reason", C.c_uint32), ("blocks", C.c_uint32), ("out_size", C.c_uint64), ("src_used", C.c_uint64)]
 
 
+class MemberResult(C.Structure):
+    # zultra_hip_member_result_t
+    _fields_ = [("reason", C.c_uint32), ("blocks", C.c_uint32), ("out_size", C.c_uint64), ("src_used", C.c_uint64), ("head_size", C.c_uint32), ("check", C.c_uint32)]
+
+
+MEMBER_RESULT_DTYPE = [("reason", "<u4"), ("blocks", "<u4"), ("out_size", "<u8"), ("src_used", "<u8"), ("head_size", "<u4"), ("check", "<u4")]
+
+
 EXPORTS = [
     # include/libzultra.h
     "zultra_stream_init", "zultra_stream_set_dictionary", "zultra_stream_compress", "zultra_stream_end",
@@ -101,6 +109,7 @@ EXPORTS = [
     "zultra_set_verify", "zultra_verified_bytes", "zultra_hip_verify_device", "zultra_hip_last_verify_ms", "zultra_hip_stream_write",
     # decompression
     "zultra_memory_decompress", "zultra_hip_inflate_streams", "zultra_memory_decompress_dict", "zultra_hip_inflate_streams_dict",
+    "zultra_memory_decompress_batch", "zultra_hip_inflate_members",
 ]
 
 
@@ -258,6 +267,46 @@ class Lib:
         rc = f(device, int(src) if src_dev else src.ctypes.data, src_size, 1 if src_dev else 0, int(dst) if dst_dev else dst.ctypes.data, dst_size, 1 if dst_dev else 0,
                None if dictionary is None else int(dictionary) if dict_dev else dictionary.ctypes.data, dict_size, 1 if dict_dev else 0, arr.ctypes.data, len(arr), res.ctypes.data, C.byref(ms))
         return rc, res, float(ms.value)
+
+    def inflate_members(self, src, src_size, dst, dst_size, dictionary, dict_size, framing, items, device=0):
+        """zultra_hip_inflate_members: inflate_streams_dict over gzip (framing FLAG_GZIP) or zlib (FLAG_ZLIB) members, or raw streams (0), with the
+        headers, checksums and trailers checked on the device. -> (rc, results, kernel_ms): results = (reason, blocks, out_size, src_used,
+        head_size, check) per item (MemberResult's layout); kernel_ms = the device time of the three launches (frame, inflate, check)."""
+        arr = np.ascontiguousarray(items, dtype=np.uint64).reshape(-1, 4)
+        res = np.zeros(len(arr), dtype=MEMBER_RESULT_DTYPE)
+        assert res.itemsize == C.sizeof(MemberResult)
+        src_dev, dst_dev = not isinstance(src, np.ndarray), not isinstance(dst, np.ndarray)
+        dict_dev = dictionary is not None and not isinstance(dictionary, np.ndarray)
+        ms = (C.c_float * 3)()
+        f = self.L.zultra_hip_inflate_members
+        f.argtypes = [C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_uint, C.c_void_p, C.c_uint32, C.c_void_p,
+                      C.POINTER(C.c_float)]
+        f.restype = C.c_int
+        rc = f(device, int(src) if src_dev else src.ctypes.data, src_size, 1 if src_dev else 0, int(dst) if dst_dev else dst.ctypes.data, dst_size, 1 if dst_dev else 0,
+               None if dictionary is None else int(dictionary) if dict_dev else dictionary.ctypes.data, dict_size, 1 if dict_dev else 0, framing, arr.ctypes.data, len(arr),
+               res.ctypes.data, ms)
+        return rc, res, [float(v) for v in ms]
+
+    def memory_decompress_batch(self, data, members, flags, out_caps, dictionary=None):
+        """zultra_memory_decompress_batch over the members [(offset, size)] of `data`, member i with out_caps[i] bytes of room (the outputs lie back
+        to back). -> (rc, [bytes, or None for a member that failed]); rc = members that failed, -1 where the call returns (size_t)-1."""
+        data = _as_u8(data)
+        n = len(members)
+        in_off = np.array([m[0] for m in members], dtype=np.uintp)
+        in_size = np.array([m[1] for m in members], dtype=np.uintp)
+        caps = np.array(out_caps, dtype=np.uintp)
+        out_off = (np.cumsum(caps) - caps).astype(np.uintp)
+        out_size = np.zeros(max(n, 1), dtype=np.uintp)
+        out = np.empty(max(int(caps.sum()), 1), dtype=np.uint8)
+        d = None if dictionary is None else _as_u8(dictionary)
+        f = self.L.zultra_memory_decompress_batch
+        f.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint, C.c_void_p, C.c_int]
+        f.restype = C.c_size_t
+        r = f(data.ctypes.data, len(data), in_off.ctypes.data, in_size.ctypes.data, out.ctypes.data, int(caps.sum()), out_off.ctypes.data, caps.ctypes.data, out_size.ctypes.data, n, flags,
+              None if d is None or not len(d) else d.ctypes.data, 0 if d is None else len(d))
+        if r == _SIZE_MAX:
+            return -1, []
+        return int(r), [None if int(out_size[i]) == _SIZE_MAX else out[int(out_off[i]): int(out_off[i]) + int(out_size[i])].tobytes() for i in range(n)]
 
     def checksum(self, data, flags, start=None):
         data = _as_u8(data)

@@ -1271,3 +1271,29 @@ extern "C" size_t zultra_memory_decompress(const unsigned char *pIn, size_t nIn,
 extern "C" size_t zultra_memory_decompress_dict(const unsigned char *pIn, size_t nIn, unsigned char *pOut, size_t nMaxOut, const unsigned int nFlags, const void *pDict, int nDictSize) {
    return memory_decompress(pIn, nIn, pOut, nMaxOut, nFlags, true, pDict, nDictSize);
 }
+
+// Many members of one framing: all of it on the device (zultra_hip_inflate_members), from and to host memory
+extern "C" size_t zultra_memory_decompress_batch(const unsigned char *pIn, size_t nIn, const size_t *pInOff, const size_t *pInSize, unsigned char *pOut, size_t nMaxOut,
+                                                 const size_t *pOutOff, const size_t *pOutCap, size_t *pOutSize, size_t n, const unsigned int nFlags, const void *pDict, int nDictSize) {
+   const unsigned int framing = nFlags & (ZULTRA_FLAG_ZLIB_FRAMING | ZULTRA_FLAG_GZIP_FRAMING);
+   if (!pIn || (!pOut && nMaxOut) || !pInOff || !pInSize || !pOutOff || !pOutCap || !pOutSize || n == 0 || n > 0xFFFFFFFFull ||
+       framing == (ZULTRA_FLAG_ZLIB_FRAMING | ZULTRA_FLAG_GZIP_FRAMING))
+      return (size_t)-1;
+   if (!pDict || nDictSize <= 0) {
+      pDict = NULL;
+      nDictSize = 0;
+   }
+   std::vector<zultra_hip_inflate_item_t> items(n);
+   std::vector<zultra_hip_member_result_t> res(n);
+   for (size_t i = 0; i < n; i++) items[i] = {pInOff[i], pInSize[i], pOutOff[i], pOutCap[i]};
+   unsigned char none = 0;
+   if (zultra_hip_inflate_members(zh_pick_device(), pIn, nIn, 0, pOut ? pOut : &none, nMaxOut, 0, pDict, (size_t)nDictSize, 0, framing, items.data(), (uint32_t)n, res.data(), NULL) < 0)
+      return (size_t)-1;
+   size_t failed = 0;
+   for (size_t i = 0; i < n; i++) {
+      const bool ok = res[i].reason == 0 && res[i].src_used == pInSize[i];   // (bytes behind the trailer)
+      pOutSize[i] = ok ? (size_t)res[i].out_size : (size_t)-1;
+      failed += !ok;
+   }
+   return failed;
+}

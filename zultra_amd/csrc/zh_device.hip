@@ -38,6 +38,7 @@
 #include "zh_stitch.h"
 #include "zh_verify.h"
 #include "zh_inflate_out.h"
+#include "zh_inflate_check.h"
 
 #ifdef ZH_EMU
 #include <mutex>
@@ -1869,20 +1870,21 @@ extern "C" int zultra_hip_verify_device(zultra_hip_ctx_t *c, zultra_hip_verify_t
 }
 extern "C" float zultra_hip_last_verify_ms(const zultra_hip_ctx_t *c) { return c ? c->verify_ms : 0.f; }
 
-// ---- batched inflate (zh_inflate_out.h) -------------------------------------------------------------------------------------------------------------------
+// ---- batched inflate (zh_inflate_out.h, zh_inflate_check.h) -------------------------------------------------------------------------------------------
 static_assert(sizeof(zultra_hip_inflate_item_t) == sizeof(zh_inflate_item_t) && sizeof(zultra_hip_inflate_result_t) == sizeof(zh_inflate_result_t), "ABI");
+static_assert(sizeof(zultra_hip_member_result_t) == sizeof(zh_member_result_t), "ABI");
 
-// what a zultra_hip_inflate_streams call holds on the device: released when the call returns, however it returns
+// what a zultra_hip_inflate_streams / zultra_hip_inflate_members call holds on the device: released when the call returns, however it returns
 struct zh_inflate_call_t {
    void *d_src = NULL, *d_dst = NULL, *d_items = NULL, *d_results = NULL, *d_hist = NULL;
-   hipEvent_t ev[2] = {NULL, NULL};
+   void *d_inner = NULL, *d_members = NULL, *d_idx = NULL, *d_tables = NULL, *d_dict = NULL, *d_dictjob = NULL;   // (members only)
+   hipEvent_t ev[4] = {NULL, NULL, NULL, NULL};
+   std::vector<uint32_t> order;   // the items with room, by dst_off
+   const uint8_t *s8 = NULL, *hist = NULL;
+   uint8_t *d8 = NULL;
    ~zh_inflate_call_t() {
-      (void)hipFree(d_src);
-      (void)hipFree(d_dst);
-      (void)hipFree(d_items);
-      (void)hipFree(d_results);
-      (void)hipFree(d_hist);
-      for (int i = 0; i < 2; i++)
+      for (void *p : {d_src, d_dst, d_items, d_results, d_hist, d_inner, d_members, d_idx, d_tables, d_dict, d_dictjob}) (void)hipFree(p);
+      for (int i = 0; i < 4; i++)
          if (ev[i]) (void)hipEventDestroy(ev[i]);
    }
 };
@@ -1891,16 +1893,13 @@ struct zh_inflate_call_t {
       if ((call) != hipSuccess) return -1; \
    } while (0)
 
-// Many raw deflate streams, one wave each. No context: the call owns its item and result buffers (and, for host pointers, the staging of the source, of
-// the output and of the history in device memory), on the null stream of `device`. hist_len == 0: zh_inflate_streams; else the last hist_len bytes of the
-// dictionary (`hist`, at most 32768) lie in front of every item's output, zh_inflate_streams_dict.
-static int zh_inflate_streams_call(int device, const void *src, size_t src_size, int src_on_device, void *dst, size_t dst_size, int dst_on_device, const uint8_t *hist, uint32_t hist_len,
-                                   int hist_on_device, const zultra_hip_inflate_item_t *items, uint32_t n, zultra_hip_inflate_result_t *results, float *kernel_ms) {
-   ZH_EMU_SERIALIZE();
-   if (kernel_ms) *kernel_ms = 0.f;
+// The steps of a call, each 0 or -1. No context: the call owns its item and result buffers (and, for host pointers, the staging of the source, of the output
+// and of the history in device memory), on the null stream of `device`.
+// 1. the arguments: every item inside its buffer, no two destination ranges over the same byte (empty ranges take none), no device history inside one
+static int zh_inflate_args(zh_inflate_call_t &C, int device, const void *src, size_t src_size, void *dst, size_t dst_size, int dst_on_device, const uint8_t *hist, uint32_t hist_len,
+                           int hist_on_device, const zultra_hip_inflate_item_t *items, uint32_t n, const void *results) {
    if (!src || !dst || !items || !results || n == 0 || device < 0) return -1;
-   // every item inside its buffer, no two destination ranges over the same byte (empty ranges take none)
-   std::vector<uint32_t> order;
+   std::vector<uint32_t> &order = C.order;
    order.reserve(n);
    for (uint32_t k = 0; k < n; k++) {
       const zultra_hip_inflate_item_t &it = items[k];
@@ -1918,57 +1917,83 @@ static int zh_inflate_streams_call(int device, const void *src, size_t src_size,
       }
    }
    if (device >= zultra_hip_device_count()) return -1;
+   return 0;
+}
+// 2. the device, the call's buffers, the staging of host pointers, the items uploaded
+static int zh_inflate_stage(zh_inflate_call_t &C, int device, const void *src, size_t src_size, int src_on_device, void *dst, size_t dst_size, int dst_on_device, const uint8_t *hist,
+                            uint32_t hist_len, int hist_on_device, const zultra_hip_inflate_item_t *items, uint32_t n, int nevents) {
    ZH_TRY(hipSetDevice(device));
-   zh_inflate_call_t C;
    ZH_TRY(hipMalloc(&C.d_items, (size_t)n * sizeof(zh_inflate_item_t)));
    ZH_TRY(hipMalloc(&C.d_results, (size_t)n * sizeof(zh_inflate_result_t)));
-   for (int i = 0; i < 2; i++) ZH_TRY(hipEventCreate(&C.ev[i]));
-   const uint8_t *s8 = (const uint8_t *)src;
-   uint8_t *d8 = (uint8_t *)dst;
+   for (int i = 0; i < nevents; i++) ZH_TRY(hipEventCreate(&C.ev[i]));
+   C.s8 = (const uint8_t *)src;
+   C.d8 = (uint8_t *)dst;
+   C.hist = hist;
    if (!src_on_device) {
       ZH_TRY(hipMalloc(&C.d_src, src_size ? src_size : 1));
       ZH_TRY(hipMemcpy(C.d_src, src, src_size, hipMemcpyHostToDevice));
-      s8 = (const uint8_t *)C.d_src;
+      C.s8 = (const uint8_t *)C.d_src;
    }
    if (!dst_on_device) {
       ZH_TRY(hipMalloc(&C.d_dst, dst_size ? dst_size : 1));
-      d8 = (uint8_t *)C.d_dst;
+      C.d8 = (uint8_t *)C.d_dst;
    }
    if (hist_len && !hist_on_device) {
       ZH_TRY(hipMalloc(&C.d_hist, hist_len));
       ZH_TRY(hipMemcpy(C.d_hist, hist, hist_len, hipMemcpyHostToDevice));
-      hist = (const uint8_t *)C.d_hist;
+      C.hist = (const uint8_t *)C.d_hist;
    }
    ZH_TRY(hipMemcpy(C.d_items, items, (size_t)n * sizeof(zh_inflate_item_t), hipMemcpyHostToDevice));
+   return 0;
+}
+// 3. the inflate kernel over n items that lie in device memory. hist_len == 0: zh_inflate_streams; else the last hist_len bytes of the dictionary
+// (C.hist, at most 32768) lie in front of every item's output, zh_inflate_streams_dict.
+static int zh_inflate_launch(const zh_inflate_call_t &C, int device, size_t src_size, size_t dst_size, uint32_t hist_len, const zh_inflate_item_t *d_items, uint32_t n) {
    int cus = 0;
    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus <= 0) cus = 256;
    uint32_t grid = (uint32_t)zh_min64(n, zh_max64(32ull * (uint32_t)cus, 64));   // (one wave per workgroup; a CU holds fewer at a time — zh_inflate_out.h —, the rest queue and even out streams of unequal length)
    const uint32_t grid_cap = (uint32_t)max(0, zh_env("ZULTRA_HIP_GRID_CAP", 0));   // tests: fewer waves than streams, every wave strides
    if (grid_cap) grid = max(1u, min(grid, grid_cap));
-   ZH_TRY(hipEventRecord(C.ev[0], 0));
    if (hist_len)
-      ZH_LAUNCH(zh_inflate_streams_dict, grid, ZH_INFLATE_THREADS, 0, s8, (uint64_t)src_size, d8, (uint64_t)dst_size, hist + hist_len, hist_len, (const zh_inflate_item_t *)C.d_items, n,
-                (zh_inflate_result_t *)C.d_results);
+      ZH_LAUNCH(zh_inflate_streams_dict, grid, ZH_INFLATE_THREADS, 0, C.s8, (uint64_t)src_size, C.d8, (uint64_t)dst_size, C.hist + hist_len, hist_len, d_items, n, (zh_inflate_result_t *)C.d_results);
    else
-      ZH_LAUNCH(zh_inflate_streams, grid, ZH_INFLATE_THREADS, 0, s8, (uint64_t)src_size, d8, (uint64_t)dst_size, (const zh_inflate_item_t *)C.d_items, n, (zh_inflate_result_t *)C.d_results);
-   ZH_TRY(hipEventRecord(C.ev[1], 0));
-   ZH_TRY(hipMemcpy(results, C.d_results, (size_t)n * sizeof(zh_inflate_result_t), hipMemcpyDeviceToHost));
-   ZH_TRY(hipDeviceSynchronize());
-   ZH_TRY(hipGetLastError());
-   if (kernel_ms) (void)hipEventElapsedTime(kernel_ms, C.ev[0], C.ev[1]);
+      ZH_LAUNCH(zh_inflate_streams, grid, ZH_INFLATE_THREADS, 0, C.s8, (uint64_t)src_size, C.d8, (uint64_t)dst_size, d_items, n, (zh_inflate_result_t *)C.d_results);
+   return 0;
+}
+// 4. the count of failed items; and of a host dst the bytes written, and nothing between the items' ranges: the span they cover comes back in one copy, the
+// ranges are taken out of it. R: zultra_hip_inflate_result_t or zultra_hip_member_result_t.
+template <typename R>
+static int zh_inflate_collect(const zh_inflate_call_t &C, void *dst, int dst_on_device, const zultra_hip_inflate_item_t *items, uint32_t n, const R *results) {
    int bad = 0;
    for (uint32_t k = 0; k < n; k++) {
       if (results[k].reason != 0) bad++;
       if (results[k].out_size > items[k].dst_cap) return -1;   // (the kernel checks every store: never)
    }
-   if (!dst_on_device && !order.empty()) {
-      // the bytes written, and nothing between the items' ranges: the span they cover comes back in one copy, the ranges are taken out of it
-      const uint64_t lo = items[order.front()].dst_off, hi = items[order.back()].dst_off + items[order.back()].dst_cap;
+   if (!dst_on_device && !C.order.empty()) {
+      const uint64_t lo = items[C.order.front()].dst_off, hi = items[C.order.back()].dst_off + items[C.order.back()].dst_cap;
       std::vector<uint8_t> span((size_t)(hi - lo));
-      ZH_TRY(hipMemcpy(span.data(), d8 + lo, (size_t)(hi - lo), hipMemcpyDeviceToHost));
-      for (uint32_t k : order) memcpy((uint8_t *)dst + items[k].dst_off, span.data() + (items[k].dst_off - lo), (size_t)results[k].out_size);
+      ZH_TRY(hipMemcpy(span.data(), C.d8 + lo, (size_t)(hi - lo), hipMemcpyDeviceToHost));
+      for (uint32_t k : C.order) memcpy((uint8_t *)dst + items[k].dst_off, span.data() + (items[k].dst_off - lo), (size_t)results[k].out_size);
    }
    return bad;
+}
+
+// Many raw deflate streams, one wave each.
+static int zh_inflate_streams_call(int device, const void *src, size_t src_size, int src_on_device, void *dst, size_t dst_size, int dst_on_device, const uint8_t *hist, uint32_t hist_len,
+                                   int hist_on_device, const zultra_hip_inflate_item_t *items, uint32_t n, zultra_hip_inflate_result_t *results, float *kernel_ms) {
+   ZH_EMU_SERIALIZE();
+   if (kernel_ms) *kernel_ms = 0.f;
+   zh_inflate_call_t C;
+   if (zh_inflate_args(C, device, src, src_size, dst, dst_size, dst_on_device, hist, hist_len, hist_on_device, items, n, results)) return -1;
+   if (zh_inflate_stage(C, device, src, src_size, src_on_device, dst, dst_size, dst_on_device, hist, hist_len, hist_on_device, items, n, 2)) return -1;
+   ZH_TRY(hipEventRecord(C.ev[0], 0));
+   if (zh_inflate_launch(C, device, src_size, dst_size, hist_len, (const zh_inflate_item_t *)C.d_items, n)) return -1;
+   ZH_TRY(hipEventRecord(C.ev[1], 0));
+   ZH_TRY(hipMemcpy(results, C.d_results, (size_t)n * sizeof(zh_inflate_result_t), hipMemcpyDeviceToHost));
+   ZH_TRY(hipDeviceSynchronize());
+   ZH_TRY(hipGetLastError());
+   if (kernel_ms) (void)hipEventElapsedTime(kernel_ms, C.ev[0], C.ev[1]);
+   return zh_inflate_collect(C, dst, dst_on_device, items, n, results);
 }
 
 extern "C" int zultra_hip_inflate_streams(int device, const void *src, size_t src_size, int src_on_device, void *dst, size_t dst_size, int dst_on_device,
@@ -1984,6 +2009,144 @@ extern "C" int zultra_hip_inflate_streams_dict(int device, const void *src, size
    const uint32_t hist_len = (uint32_t)zh_min64(dict_size, ZH_MAX_DIST);
    return zh_inflate_streams_call(device, src, src_size, src_on_device, dst, dst_size, dst_on_device, dict ? (const uint8_t *)dict + (dict_size - hist_len) : NULL, hist_len, dict_on_device, items, n,
                                   results, kernel_ms);
+}
+
+// Adler-32 of a host buffer (the DICTID of a host dictionary)
+static uint32_t zh_adler32_host(const uint8_t *p, size_t n) {
+   uint32_t a = 1, b = 0;
+   while (n) {
+      const size_t run = n < 5552 ? n : 5552;   // (the longest run whose sums stay below 2^32)
+      for (size_t i = 0; i < run; i++) {
+         a += p[i];
+         b += a;
+      }
+      a %= ZH_CK_ADLER_MOD;
+      b %= ZH_CK_ADLER_MOD;
+      p += run;
+      n -= run;
+   }
+   return (b << 16) | a;
+}
+
+// zh_check_members' tables: the CRC-32 byte table, "append ZH_CK_SLICE zero bytes" and "append 64 * ZH_CK_SLICE zero bytes", the operators one table per state byte
+static const std::vector<uint32_t> &zh_ck_tables() {
+   static const std::vector<uint32_t> tables = [] {
+      std::vector<uint32_t> t(ZH_CK_TABLE_WORDS);
+      for (uint32_t i = 0; i < 256; i++) {
+         uint32_t v = i;
+         for (int k = 0; k < 8; k++) v = (v >> 1) ^ ((v & 1) ? 0xEDB88320u : 0);
+         t[i] = v;
+      }
+      for (int b = 0; b < 4; b++)
+         for (uint32_t i = 0; i < 256; i++) {
+            uint32_t v = i << (8 * b);
+            for (uint32_t k = 0; k < ZH_CK_SLICE; k++) v = (v >> 8) ^ t[v & 0xff];
+            t[256 + 256 * b + i] = v;
+         }
+      for (int b = 0; b < 4; b++)
+         for (uint32_t i = 0; i < 256; i++) {
+            uint32_t v = i << (8 * b);
+            for (int k = 0; k < 64; k++) v = t[256 + (v & 0xff)] ^ t[512 + ((v >> 8) & 0xff)] ^ t[768 + ((v >> 16) & 0xff)] ^ t[1024 + (v >> 24)];
+            t[1280 + 256 * b + i] = v;
+         }
+      return t;
+   }();
+   return tables;
+}
+
+// zh_check_members over n items: idx = those of at most ZH_CK_SMALL_MAX bytes of room first (spg threads each), then the others
+template <uint32_t FRAMING>
+static int zh_check_launch(const uint8_t *src, const uint8_t *dst, uint64_t dst_size, const zh_inflate_item_t *d_items, const zh_inflate_result_t *d_inner, zh_member_result_t *d_members,
+                           const uint32_t *d_idx, uint32_t nsmall, uint32_t nlarge, uint32_t spg, const uint32_t *d_tables) {
+   uint32_t small_blocks, large_blocks = nlarge;
+   if (FRAMING == ZH_M_RAW) {
+      small_blocks = (uint32_t)zh_min64(((uint64_t)nsmall + nlarge + ZH_CK_THREADS - 1) / ZH_CK_THREADS, 4096);
+      large_blocks = 0;
+   }
+   else
+      small_blocks = (nsmall + ZH_CK_THREADS / spg - 1) / (ZH_CK_THREADS / spg);
+   const uint32_t grid_cap = (uint32_t)max(0, zh_env("ZULTRA_HIP_GRID_CAP", 0));   // tests: fewer workgroups than groups and items, every one strides
+   if (grid_cap) {
+      small_blocks = min(small_blocks, max(1u, grid_cap / 2));
+      large_blocks = min(large_blocks, max(1u, grid_cap - grid_cap / 2));
+   }
+   ZH_LAUNCH(zh_check_members<FRAMING>, small_blocks + large_blocks, ZH_CK_THREADS, 0, src, dst, dst_size, d_items, d_inner, d_members, d_idx, nsmall, nlarge, spg, small_blocks, d_tables);
+   return 0;
+}
+
+// Many gzip / zlib members (or raw streams): headers, inflate, checksums and trailers in three launches on the null stream, one synchronisation at the end.
+extern "C" int zultra_hip_inflate_members(int device, const void *src, size_t src_size, int src_on_device, void *dst, size_t dst_size, int dst_on_device, const void *dict, size_t dict_size,
+                                          int dict_on_device, unsigned int framing, const zultra_hip_inflate_item_t *items, uint32_t n, zultra_hip_member_result_t *results, float *kernel_ms) {
+   ZH_EMU_SERIALIZE();
+   if (kernel_ms) kernel_ms[0] = kernel_ms[1] = kernel_ms[2] = 0.f;
+   if ((!dict && dict_size) || (framing != ZH_M_RAW && framing != ZH_M_ZLIB && framing != ZH_M_GZIP)) return -1;
+   const uint32_t hist_len = (uint32_t)zh_min64(dict_size, ZH_MAX_DIST);
+   const uint8_t *hist = dict ? (const uint8_t *)dict + (dict_size - hist_len) : NULL;
+   zh_inflate_call_t C;
+   if (zh_inflate_args(C, device, src, src_size, dst, dst_size, dst_on_device, hist, hist_len, dict_on_device, items, n, results)) return -1;
+   if (zh_inflate_stage(C, device, src, src_size, src_on_device, dst, dst_size, dst_on_device, hist, hist_len, dict_on_device, items, n, 4)) return -1;
+   ZH_TRY(hipMalloc(&C.d_inner, (size_t)n * sizeof(zh_inflate_item_t)));
+   ZH_TRY(hipMalloc(&C.d_members, (size_t)n * sizeof(zh_member_result_t)));
+   // the checksum kernel's two forms: by the room an item has (what it will have written is known on the device only)
+   std::vector<uint32_t> idx(n);
+   uint32_t nsmall = 0, nlarge = 0, spg = 1;
+   for (uint32_t k = 0; k < n; k++)
+      if (items[k].dst_cap <= ZH_CK_SMALL_MAX) {
+         idx[nsmall++] = k;
+         while ((uint64_t)spg * ZH_CK_SLICE < items[k].dst_cap) spg *= 2;
+      }
+   for (uint32_t k = 0; k < n; k++)
+      if (items[k].dst_cap > ZH_CK_SMALL_MAX) idx[nsmall + nlarge++] = k;
+   ZH_TRY(hipMalloc(&C.d_idx, (size_t)n * sizeof(uint32_t)));
+   ZH_TRY(hipMemcpy(C.d_idx, idx.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice));
+   if (framing == ZH_M_GZIP) {
+      ZH_TRY(hipMalloc(&C.d_tables, ZH_CK_TABLE_WORDS * sizeof(uint32_t)));
+      ZH_TRY(hipMemcpy(C.d_tables, zh_ck_tables().data(), ZH_CK_TABLE_WORDS * sizeof(uint32_t), hipMemcpyHostToDevice));
+   }
+   // DICTID (zlib): the Adler-32 of the WHOLE dictionary, once per call — the host's sum of a host dictionary; of a device dictionary the checksum kernel's, as
+   // a batch of one item whose "output" is the dictionary (no trailer behind it: its reason is not looked at, its `check` is)
+   struct {
+      zh_inflate_item_t item;
+      zh_inflate_result_t inner;
+      zh_member_result_t member;
+      uint32_t idx;
+   } job = {};
+   ZH_TRY(hipMalloc(&C.d_dictjob, sizeof(job)));
+   uint8_t *const dj = (uint8_t *)C.d_dictjob;
+   zh_member_result_t *const d_dictsum = (zh_member_result_t *)(dj + offsetof(decltype(job), member));
+   const bool need_id = framing == ZH_M_ZLIB && dict_size != 0;
+   if (need_id) {
+      job.item.dst_cap = job.inner.out_size = dict_size;
+      if (!dict_on_device) job.member.check = zh_adler32_host((const uint8_t *)dict, dict_size);
+      ZH_TRY(hipMemcpy(dj, &job, sizeof(job), hipMemcpyHostToDevice));
+      if (dict_on_device) {
+         const bool small = dict_size <= ZH_CK_SMALL_MAX;
+         if (zh_check_launch<ZH_M_ZLIB>((const uint8_t *)dict, (const uint8_t *)dict, dict_size, (const zh_inflate_item_t *)(dj + offsetof(decltype(job), item)),
+                                        (const zh_inflate_result_t *)(dj + offsetof(decltype(job), inner)), d_dictsum, (const uint32_t *)(dj + offsetof(decltype(job), idx)), small ? 1 : 0,
+                                        small ? 0 : 1, ZH_CK_SMALL_MAX / ZH_CK_SLICE, NULL))
+            return -1;
+      }
+   }
+   ZH_TRY(hipEventRecord(C.ev[0], 0));
+   ZH_LAUNCH(zh_frame_heads, (uint32_t)zh_min64(((uint64_t)n + ZH_FRAME_THREADS - 1) / ZH_FRAME_THREADS, 4096), ZH_FRAME_THREADS, 0, C.s8, (uint64_t)src_size, (const zh_inflate_item_t *)C.d_items, n,
+             (uint32_t)framing, dict_size ? 1u : 0u, (const zh_member_result_t *)d_dictsum, (zh_inflate_item_t *)C.d_inner, (zh_member_result_t *)C.d_members);
+   ZH_TRY(hipEventRecord(C.ev[1], 0));
+   if (zh_inflate_launch(C, device, src_size, dst_size, hist_len, (const zh_inflate_item_t *)C.d_inner, n)) return -1;
+   ZH_TRY(hipEventRecord(C.ev[2], 0));
+   const zh_inflate_item_t *d_items = (const zh_inflate_item_t *)C.d_items;
+   const zh_inflate_result_t *d_inner_res = (const zh_inflate_result_t *)C.d_results;
+   zh_member_result_t *d_members = (zh_member_result_t *)C.d_members;
+   if ((framing == ZH_M_GZIP   ? zh_check_launch<ZH_M_GZIP>(C.s8, C.d8, dst_size, d_items, d_inner_res, d_members, (const uint32_t *)C.d_idx, nsmall, nlarge, spg, (const uint32_t *)C.d_tables)
+        : framing == ZH_M_ZLIB ? zh_check_launch<ZH_M_ZLIB>(C.s8, C.d8, dst_size, d_items, d_inner_res, d_members, (const uint32_t *)C.d_idx, nsmall, nlarge, spg, NULL)
+                               : zh_check_launch<ZH_M_RAW>(C.s8, C.d8, dst_size, d_items, d_inner_res, d_members, (const uint32_t *)C.d_idx, nsmall, nlarge, spg, NULL)))
+      return -1;
+   ZH_TRY(hipEventRecord(C.ev[3], 0));
+   ZH_TRY(hipMemcpy(results, C.d_members, (size_t)n * sizeof(zh_member_result_t), hipMemcpyDeviceToHost));
+   ZH_TRY(hipDeviceSynchronize());
+   ZH_TRY(hipGetLastError());
+   if (kernel_ms)
+      for (int i = 0; i < 3; i++) (void)hipEventElapsedTime(kernel_ms + i, C.ev[i], C.ev[i + 1]);
+   return zh_inflate_collect(C, dst, dst_on_device, items, n, results);
 }
 
 extern "C" void zultra_hip_last_timing(const zultra_hip_ctx_t *c, zultra_hip_timing_t *t) {

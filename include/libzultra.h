@@ -161,6 +161,15 @@ size_t zultra_memory_decompress_batch(const unsigned char *pIn, size_t nIn, cons
                                       const size_t *pOutOff, const size_t *pOutCap, size_t *pOutSize, size_t n, const unsigned int nFlags,
                                       const void *pDict, int nDictSize);
 
+/* gzip(1) over a whole file: pIn is any number of gzip members back to back — what bgzip, pigz -i or `cat a.gz b.gz` write — and pOut receives the
+ * concatenation of their outputs. The source is uploaded once. Runs of BGZF members (a `BC` extra subfield with the member's size: include/zultra_hip.h,
+ * zultra_hip_inflate_file) are found and inflated on the device in one batch each; a member without that hint is decoded on its own, at the speed of
+ * one wave, and the walk goes on behind it. *pnMembers (may be NULL) = the members decoded. Returns the bytes written, or (size_t)-1: a member that
+ * failed (header, stream, CRC-32, ISIZE), bytes behind the last member that are no member (trailing garbage, trailing zeros, a member cut off), more
+ * output than nMaxOut, an empty input, no device. A gzip header's FHCRC is checked, as in zultra_memory_decompress_batch (zultra_memory_decompress
+ * skips the two bytes). No dictionary. */
+size_t zultra_memory_decompress_members(const unsigned char *pIn, size_t nIn, unsigned char *pOut, size_t nMaxOut, size_t *pnMembers /* may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -304,6 +304,37 @@ int zultra_hip_inflate_members(int device, const void *src, size_t src_size, int
                                float *kernel_ms /* [3], may be NULL */);
 
 /*
+ * A whole BGZF / multi-member gzip FILE: the device finds the members itself, so the caller names no offsets. A HINTED member starts at p when
+ * src_size - p >= 12, src[p..p+3) = 1f 8b 08, FEXTRA is set, XLEN fits in the source, the extra field's subfields reach one with SI1 'B', SI2 'C', SLEN 2 (a
+ * subfield that runs past XLEN ends the walk), and L = le16(its data) + 1 has L >= 12 + XLEN + 8 and p + L <= src_size: the member is src[p .. p + L), its
+ * ISIZE the last four of those bytes. The index is the chain of hinted members from p = 0: item i = {p_i, L_i, the sum of the ISIZEs before it, ISIZE_i}. It
+ * checks nothing else of a member: that is zultra_hip_inflate_members' business, with its reasons 1..16.
+ *   stop           : why the chain ended at src_used — 0 the end of the source; 1 magic and CM = 8 but no hint (a gzip member the index cannot size); 2 a hint
+ *                    whose L is too short or reaches past the source; 3 anything else (fewer than 12 bytes, no magic); and 4 = more members than `cap` /
+ *                    `results_cap`, or more output than dst_size: nothing was written, members / out_size say how much room the file needs
+ *   tiles, tiles_rewalked : diagnostics — the source is indexed in tiles of ZULTRA_HIP_INDEX_TILE bytes (environment, any value >= 32; default 256 KiB), each
+ *                    from a guessed entry; tiles the chain entered, and those of them whose guess was not the chain's entry and were walked again
+ * zultra_hip_index_members: the index alone. items (host, cap entries) may be NULL with cap 0 to learn members and out_size. Returns 0; -1 for bad arguments
+ * (src NULL, src_size 0, a bad device, items NULL with cap > 0), HIP errors, and stop 4 (res filled, no item written). kernel_ms (may be NULL): the index kernels.
+ * zultra_hip_inflate_file: index, headers, inflate and checks of the indexed members, gzip framing, no dictionary; the items never leave the device except for
+ * one read of 32 bytes per member. The per-member results are those of zultra_hip_inflate_members(..., ZULTRA_FLAG_GZIP_FRAMING, the index's items, ...), field
+ * for field: a member whose ISIZE lies is 13 (too low) or 16 (too high). results (host, results_cap entries) may be NULL. Returns the number of indexed
+ * members whose reason is not 0; -1 for bad arguments (src / dst / res NULL, src_size 0, a bad device), HIP errors and stop 4 (res filled). A stop of 1..3 is
+ * no error of this call: the indexed prefix is decoded and res->src_used says where the rest begins. *_on_device as for zultra_hip_inflate_streams (of a host
+ * dst only the out_size bytes of every member are written). kernel_ms (may be NULL): four — index, frame, inflate, check.
+ */
+typedef struct zultra_hip_index_result_s {
+   uint32_t members, stop;          /* stop kinds 0..3 above; 4 = more members than `cap` / more output than dst_size (nothing decoded) */
+   uint64_t out_size, src_used;     /* sum of ISIZE of the indexed members; the stop position */
+   uint32_t tiles, tiles_rewalked;  /* diagnostics: tiles the chain entered, and those whose guess was not the chain's entry */
+} zultra_hip_index_result_t;
+int zultra_hip_index_members(int device, const void *src, size_t src_size, int src_on_device,
+                             zultra_hip_inflate_item_t *items, uint32_t cap, zultra_hip_index_result_t *res, float *kernel_ms /* may be NULL */);
+int zultra_hip_inflate_file(int device, const void *src, size_t src_size, int src_on_device, void *dst, size_t dst_size, int dst_on_device,
+                            zultra_hip_index_result_t *res, zultra_hip_member_result_t *results /* host, results_cap; may be NULL */, uint32_t results_cap,
+                            float *kernel_ms /* [4]: index, frame, inflate, check; may be NULL */);
+
+/*
  * Many small independent inputs ("files", BASELINE.json configuration 5: 4 KiB records, each its own stream). A files
  * context takes inputs below 8192 bytes — the splitter never cuts those (blockdeflate.c:646), so a batch needs no host
  * decision and its whole kernel sequence is replayed from one captured hipGraph. zultra_hip_compress_files runs

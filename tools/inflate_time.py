@@ -7,7 +7,11 @@ mode has none) and inflated by zh_inflate_streams_dict (zultra_hip_inflate_strea
 by host zlib without a dictionary, and host zlib with zdict on one core. Then the members leg: the library's own raw streams of the first batch with
 gzip framing put around them on the host, and as a second variant with zlib framing, inflated and CHECKED device to device by
 zultra_hip_inflate_members (zh_frame_heads, the inflate kernel, zh_check_members: three kernel times), next to zultra_hip_inflate_streams on the
-bare streams and host zlib.crc32 / zlib.adler32 over the output on one core, all in one process. One JSON line.
+bare streams and host zlib.crc32 / zlib.adler32 over the output on one core, all in one process. Then the file leg: the first --bgzf-bytes of the
+corpus as ONE BGZF file built on the host (payloads of 65 280 bytes, host zlib level 6), indexed, inflated and checked device to device by
+zultra_hip_inflate_file (four kernel times: index, frame, inflate, check) with ZULTRA_HIP_INDEX_TILE swept over 64 KiB .. 4 MiB, next to the route
+without the index in the same process: a host walk of BSIZE over a host copy of the file, then zultra_hip_inflate_members over those items. One JSON
+line.
 
     python tools/inflate_time.py [--files N] [--file-size BYTES] [--reps N] [--dict-size BYTES] [--step-timeout SECONDS] [--lib PATH]
 
@@ -20,8 +24,10 @@ The steps run in this order, every GPU step in a process of its own under its ow
     5. host zlib with zdict, one core, over the streams of step 4 (this process), every output compared with its record
     6. zultra_hip_inflate_members over the gzip members, then over the zlib members, device to device; zultra_hip_inflate_streams over the bare
        streams; zlib.crc32 and zlib.adler32 over the output on one core (the outputs are read back once and compared with the input)
+    7. zultra_hip_inflate_file over the BGZF file per tile size, then the host walk and zultra_hip_inflate_members (the output is read back once
+       and compared with the input)
 --lib: another build of the library (an A/B of the plain kernel against an older build); steps 4 and 5 are left out where it has no dictionary kernel,
-step 6 where it has no members call."""
+step 6 where it has no members call, step 7 where it has no file call."""
 import argparse
 import ctypes as C
 import json
@@ -42,7 +48,8 @@ def library(args):
     if not args.lib:
         return zultra_amd.lib()
     from zultra_amd._ffi import Lib
-    return Lib(args.lib, allow_missing=("zultra_memory_decompress_dict", "zultra_hip_inflate_streams_dict", "zultra_memory_decompress_batch", "zultra_hip_inflate_members"))
+    return Lib(args.lib, allow_missing=("zultra_memory_decompress_dict", "zultra_hip_inflate_streams_dict", "zultra_memory_decompress_batch", "zultra_hip_inflate_members",
+                                        "zultra_hip_index_members", "zultra_hip_inflate_file", "zultra_memory_decompress_members"))
 
 
 def batch(args):
@@ -222,9 +229,68 @@ def child_members(args):
     return 0
 
 
+FILE_TILES = [64 << 10, 128 << 10, 256 << 10, 512 << 10, 1 << 20, 2 << 20, 4 << 20]
+
+
+def child_file(args):
+    import numpy as np
+
+    import corpus
+    import inflate_cases as I
+    import inflate_file_cases as F
+    import verify_cases as V
+    L = library(args)
+    if L.device_count() < 1:
+        raise RuntimeError("no HIP device visible: nothing can be timed")
+    L.is_emulator = False
+    nrec = (args.bgzf_bytes + args.file_size - 1) // args.file_size
+    raw = np.ascontiguousarray(corpus.json_files(0, nrec, args.file_size), dtype=np.uint8).tobytes()[:args.bgzf_bytes]
+    buf = b"".join(F.bgzf(raw[at: at + 65280]) for at in range(0, len(raw), 65280)) + F.EOF_MARKER
+    src, dst = V.DeviceCopy(L, np.frombuffer(buf, dtype=np.uint8).copy()), V.DeviceCopy(L, np.zeros(len(raw), dtype=np.uint8))
+    out = {"bgzf_input_bytes": len(raw), "bgzf_file_bytes": len(buf), "file_kernel_ms_by_tile": {}}
+    for tile in FILE_TILES:
+        os.environ["ZULTRA_HIP_INDEX_TILE"] = str(tile)   # (read per call)
+        times, calls = [], []
+        for it in range(2 + args.reps):   # (two warm-up calls)
+            t0 = time.perf_counter()
+            rc, res, _, ms = L.inflate_file(src.ptr, len(buf), dst.ptr, len(raw), None)
+            calls.append(1e3 * (time.perf_counter() - t0))
+            assert rc == 0 and res.stop == 0 and res.out_size == len(raw), (tile, rc, res.stop, res.out_size)
+            if it >= 2:
+                times.append(ms)
+        med = [float(np.median([t[k] for t in times])) for k in range(4)]
+        out["file_kernel_ms_by_tile"][str(tile)] = {"index": med[0], "frame": med[1], "inflate": med[2], "check": med[3], "call_ms_min": min(calls[2:]), "members": res.members,
+                                                    "tiles": res.tiles, "tiles_rewalked": res.tiles_rewalked}
+    del os.environ["ZULTRA_HIP_INDEX_TILE"]
+    assert I.device_read(L, dst, len(raw)).tobytes() == raw, "the inflated file differs from the input"
+    assert V._Hip.lib().hipMemset(C.c_void_p(dst.ptr), 0, C.c_size_t(len(raw))) == 0
+    # the route without the index: the host walks BSIZE over a host copy of the file, zultra_hip_inflate_members takes the items
+    walks, times, calls = [], [], []
+    for it in range(2 + args.reps):
+        t0 = time.perf_counter()
+        items, stop, at, total = F.walk(buf)
+        walks.append(1e3 * (time.perf_counter() - t0))
+        t0 = time.perf_counter()
+        rc, mres, ms = L.inflate_members(src.ptr, len(buf), dst.ptr, len(raw), None, 0, 2, items)
+        calls.append(1e3 * (time.perf_counter() - t0))
+        assert rc == 0 and stop == 0 and total == len(raw)
+        if it >= 2:
+            times.append(ms)
+    assert I.device_read(L, dst, len(raw)).tobytes() == raw, "the inflated file differs from the input (members route)"
+    med = [float(np.median([t[k] for t in times])) for k in range(3)]
+    out["file_members_route"] = {"host_walk_python_ms_min": min(walks), "frame": med[0], "inflate": med[1], "check": med[2], "call_ms_min": min(calls[2:]), "members": len(items)}
+    best = min(out["file_kernel_ms_by_tile"].items(), key=lambda kv: kv[1]["index"])
+    out["file_best_tile"] = int(best[0])
+    out["file_index_over_inflate_at_best_tile"] = best[1]["index"] / best[1]["inflate"]
+    src.free()
+    dst.free()
+    print(json.dumps(out), flush=True)
+    return 0
+
+
 def gpu_step(name, args):
     cmd = [sys.executable, os.path.abspath(__file__), "--child", name, "--files", str(args.files), "--file-size", str(args.file_size), "--reps", str(args.reps),
-           "--dict-size", str(args.dict_size), "--stream-file", args.stream_file] + (["--lib", args.lib] if args.lib else [])
+           "--dict-size", str(args.dict_size), "--bgzf-bytes", str(args.bgzf_bytes), "--stream-file", args.stream_file] + (["--lib", args.lib] if args.lib else [])
     r = subprocess.run(cmd, timeout=args.step_timeout, capture_output=True, text=True)
     if r.returncode != 0:
         sys.stderr.write(r.stdout + r.stderr)
@@ -239,13 +305,18 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--step-timeout", type=int, default=300, help="seconds every GPU step may take")
     ap.add_argument("--dict-size", type=int, default=32768, help="bytes of the dictionary leg's preset dictionary")
+    ap.add_argument("--bgzf-bytes", type=int, default=100 * 1000 * 1000, help="bytes of the corpus the file leg frames as one BGZF file")
+    ap.add_argument("--only", default="", help="run only this step (e.g. file) and print its JSON line")
     ap.add_argument("--lib", default="", help="another build of libzultra_amd.so to time instead of the tree's")
-    ap.add_argument("--child", choices=["inflate", "verify", "dict", "members"], help="(internal) the process that opens the GPU")
+    ap.add_argument("--child", choices=["inflate", "verify", "dict", "members", "file"], help="(internal) the process that opens the GPU")
     ap.add_argument("--stream-file", default="", help="(internal) where the inflate step leaves the streams for host zlib")
     args = ap.parse_args()
     if args.child:
-        sys.exit({"inflate": child_inflate, "verify": child_verify, "dict": child_dict, "members": child_members}[args.child](args))
+        sys.exit({"inflate": child_inflate, "verify": child_verify, "dict": child_dict, "members": child_members, "file": child_file}[args.child](args))
     import numpy as np
+    if args.only:
+        print(json.dumps(gpu_step(args.only, args)), flush=True)
+        return
     with tempfile.TemporaryDirectory() as tmp:
         args.stream_file = os.path.join(tmp, "streams.npz")
         out = {"files": args.files, "file_size": args.file_size, "input_bytes": args.files * args.file_size}
@@ -261,6 +332,8 @@ def main():
         with_members = not args.lib or hasattr(library(args).L, "zultra_hip_inflate_members")
         if with_members:
             out.update(gpu_step("members", args))
+        if not args.lib or hasattr(library(args).L, "zultra_hip_inflate_file"):
+            out.update(gpu_step("file", args))
     host = []
     for _ in range(3):
         t0 = time.perf_counter()

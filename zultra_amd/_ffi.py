@@ -86,6 +86,11 @@ class MemberResult(C.Structure):
     _fields_ = [("reason", C.c_uint32), ("blocks", C.c_uint32), ("out_size", C.c_uint64), ("src_used", C.c_uint64), ("head_size", C.c_uint32), ("check", C.c_uint32)]
 
 
+class IndexResult(C.Structure):
+    # zultra_hip_index_result_t
+    _fields_ = [("members", C.c_uint32), ("stop", C.c_uint32), ("out_size", C.c_uint64), ("src_used", C.c_uint64), ("tiles", C.c_uint32), ("tiles_rewalked", C.c_uint32)]
+
+
 MEMBER_RESULT_DTYPE = [("reason", "<u4"), ("blocks", "<u4"), ("out_size", "<u8"), ("src_used", "<u8"), ("head_size", "<u4"), ("check", "<u4")]
 
 
@@ -110,6 +115,7 @@ EXPORTS = [
     # decompression
     "zultra_memory_decompress", "zultra_hip_inflate_streams", "zultra_memory_decompress_dict", "zultra_hip_inflate_streams_dict",
     "zultra_memory_decompress_batch", "zultra_hip_inflate_members",
+    "zultra_hip_index_members", "zultra_hip_inflate_file", "zultra_memory_decompress_members",
 ]
 
 
@@ -286,6 +292,48 @@ class Lib:
                None if dictionary is None else int(dictionary) if dict_dev else dictionary.ctypes.data, dict_size, 1 if dict_dev else 0, framing, arr.ctypes.data, len(arr),
                res.ctypes.data, ms)
         return rc, res, [float(v) for v in ms]
+
+    def index_members(self, src, src_size, cap, device=0):
+        """zultra_hip_index_members. src: a uint8 array (host memory, staged by the call) or an integer device pointer; cap: room for that many
+        items, 0 to pass items = NULL. -> (rc, IndexResult, items as rows of (src_off, src_size, dst_off, dst_cap), kernel_ms)."""
+        items = np.zeros((cap, 4), dtype=np.uint64)
+        res = IndexResult()
+        src_dev = not isinstance(src, np.ndarray)
+        ms = C.c_float(0)
+        f = self.L.zultra_hip_index_members
+        f.argtypes = [C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_uint32, C.POINTER(IndexResult), C.POINTER(C.c_float)]
+        f.restype = C.c_int
+        rc = f(device, None if src is None else int(src) if src_dev else src.ctypes.data, src_size, 1 if src_dev else 0, items.ctypes.data if cap else None, cap, C.byref(res), C.byref(ms))
+        return rc, res, items[:res.members if rc == 0 else 0], float(ms.value)
+
+    def inflate_file(self, src, src_size, dst, dst_size, results_cap=None, device=0):
+        """zultra_hip_inflate_file. src / dst: a uint8 array (host memory, staged by the call) or an integer device pointer (used in place);
+        results_cap: room for that many per-member results, None to pass results = NULL. -> (rc, IndexResult, results (MemberResult's layout,
+        the indexed members'), kernel_ms = [index, frame, inflate, check])."""
+        res = IndexResult()
+        out = np.zeros(results_cap or 0, dtype=MEMBER_RESULT_DTYPE)
+        src_dev, dst_dev = not isinstance(src, np.ndarray), not isinstance(dst, np.ndarray)
+        ms = (C.c_float * 4)()
+        f = self.L.zultra_hip_inflate_file
+        f.argtypes = [C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(IndexResult), C.c_void_p, C.c_uint32, C.POINTER(C.c_float)]
+        f.restype = C.c_int
+        rc = f(device, None if src is None else int(src) if src_dev else src.ctypes.data, src_size, 1 if src_dev else 0,
+               None if dst is None else int(dst) if dst_dev else dst.ctypes.data, dst_size, 1 if dst_dev else 0, C.byref(res),
+               out.ctypes.data if results_cap is not None else None, results_cap or 0, ms)
+        return rc, res, out[:res.members if rc >= 0 else 0], [float(v) for v in ms]
+
+    def memory_decompress_members(self, data, max_out):
+        """zultra_memory_decompress_members -> (the concatenated output, members), or (None, 0) where the call returns (size_t)-1."""
+        data = _as_u8(data)
+        out = np.empty(max(max_out, 1), dtype=np.uint8)
+        members = C.c_size_t(0)
+        f = self.L.zultra_memory_decompress_members
+        f.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+        f.restype = C.c_size_t
+        r = f(data.ctypes.data if len(data) else None, len(data), out.ctypes.data, max_out, C.byref(members))
+        if r == _SIZE_MAX:
+            return None, 0
+        return out[:r].tobytes(), int(members.value)
 
     def memory_decompress_batch(self, data, members, flags, out_caps, dictionary=None):
         """zultra_memory_decompress_batch over the members [(offset, size)] of `data`, member i with out_caps[i] bytes of room (the outputs lie back

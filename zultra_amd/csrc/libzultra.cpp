@@ -1297,3 +1297,45 @@ extern "C" size_t zultra_memory_decompress_batch(const unsigned char *pIn, size_
    }
    return failed;
 }
+
+// gzip(1) over a whole file: runs of hinted members through zultra_hip_inflate_file, a member without a hint through zultra_hip_inflate_members on its own
+extern "C" void *zh_device_upload(int device, const void *host, size_t n);   // (zh_device.hip: this file has no HIP of its own)
+extern "C" void zh_device_release(void *p);
+extern "C" size_t zultra_memory_decompress_members(const unsigned char *pIn, size_t nIn, unsigned char *pOut, size_t nMaxOut, size_t *pnMembers) {
+   if (pnMembers) *pnMembers = 0;
+   if (!pIn || nIn == 0 || (!pOut && nMaxOut)) return (size_t)-1;
+   const int device = zh_pick_device();
+   uint8_t *const d_in = (uint8_t *)zh_device_upload(device, pIn, nIn);
+   if (!d_in) return (size_t)-1;
+   unsigned char none = 0;
+   size_t at = 0, written = 0, members = 0;
+   bool ok = true;
+   while (ok) {
+      unsigned char *const out = pOut ? pOut + written : &none;
+      zultra_hip_index_result_t ix;
+      if (zultra_hip_inflate_file(device, d_in + at, nIn - at, 1, out, nMaxOut - written, 0, &ix, NULL, 0, NULL) != 0) ok = false;   // a member failed, too little room, an error
+      else {
+         at += (size_t)ix.src_used;
+         written += (size_t)ix.out_size;
+         members += ix.members;
+         if (ix.stop == 0) break;
+         if (ix.stop != 1) ok = false;   // cut off, garbage, zeros
+         else {
+            // a gzip member the index cannot size: the rest of the file is its item, the room left its room; src_used says where it ends
+            const zultra_hip_inflate_item_t item = {0, nIn - at, 0, nMaxOut - written};
+            zultra_hip_member_result_t r;
+            if (zultra_hip_inflate_members(device, d_in + at, nIn - at, 1, pOut ? pOut + written : &none, nMaxOut - written, 0, NULL, 0, 0, ZULTRA_FLAG_GZIP_FRAMING, &item, 1, &r, NULL) != 0 || r.src_used == 0) ok = false;
+            else {
+               at += (size_t)r.src_used;
+               written += (size_t)r.out_size;
+               members++;
+               if (at == nIn) break;
+            }
+         }
+      }
+   }
+   zh_device_release(d_in);
+   if (!ok) return (size_t)-1;
+   if (pnMembers) *pnMembers = members;
+   return written;
+}

@@ -39,6 +39,7 @@
 #include "zh_verify.h"
 #include "zh_inflate_out.h"
 #include "zh_inflate_check.h"
+#include "zh_inflate_index.h"
 
 #ifdef ZH_EMU
 #include <mutex>
@@ -1878,13 +1879,14 @@ static_assert(sizeof(zultra_hip_member_result_t) == sizeof(zh_member_result_t), 
 struct zh_inflate_call_t {
    void *d_src = NULL, *d_dst = NULL, *d_items = NULL, *d_results = NULL, *d_hist = NULL;
    void *d_inner = NULL, *d_members = NULL, *d_idx = NULL, *d_tables = NULL, *d_dict = NULL, *d_dictjob = NULL;   // (members only)
-   hipEvent_t ev[4] = {NULL, NULL, NULL, NULL};
+   void *d_ix_tiles = NULL, *d_ix_totals = NULL;   // (the member index only)
+   hipEvent_t ev[8] = {NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL};
    std::vector<uint32_t> order;   // the items with room, by dst_off
    const uint8_t *s8 = NULL, *hist = NULL;
    uint8_t *d8 = NULL;
    ~zh_inflate_call_t() {
-      for (void *p : {d_src, d_dst, d_items, d_results, d_hist, d_inner, d_members, d_idx, d_tables, d_dict, d_dictjob}) (void)hipFree(p);
-      for (int i = 0; i < 4; i++)
+      for (void *p : {d_src, d_dst, d_items, d_results, d_hist, d_inner, d_members, d_idx, d_tables, d_dict, d_dictjob, d_ix_tiles, d_ix_totals}) (void)hipFree(p);
+      for (int i = 0; i < 8; i++)
          if (ev[i]) (void)hipEventDestroy(ev[i]);
    }
 };
@@ -2074,20 +2076,8 @@ static int zh_check_launch(const uint8_t *src, const uint8_t *dst, uint64_t dst_
    return 0;
 }
 
-// Many gzip / zlib members (or raw streams): headers, inflate, checksums and trailers in three launches on the null stream, one synchronisation at the end.
-extern "C" int zultra_hip_inflate_members(int device, const void *src, size_t src_size, int src_on_device, void *dst, size_t dst_size, int dst_on_device, const void *dict, size_t dict_size,
-                                          int dict_on_device, unsigned int framing, const zultra_hip_inflate_item_t *items, uint32_t n, zultra_hip_member_result_t *results, float *kernel_ms) {
-   ZH_EMU_SERIALIZE();
-   if (kernel_ms) kernel_ms[0] = kernel_ms[1] = kernel_ms[2] = 0.f;
-   if ((!dict && dict_size) || (framing != ZH_M_RAW && framing != ZH_M_ZLIB && framing != ZH_M_GZIP)) return -1;
-   const uint32_t hist_len = (uint32_t)zh_min64(dict_size, ZH_MAX_DIST);
-   const uint8_t *hist = dict ? (const uint8_t *)dict + (dict_size - hist_len) : NULL;
-   zh_inflate_call_t C;
-   if (zh_inflate_args(C, device, src, src_size, dst, dst_size, dst_on_device, hist, hist_len, dict_on_device, items, n, results)) return -1;
-   if (zh_inflate_stage(C, device, src, src_size, src_on_device, dst, dst_size, dst_on_device, hist, hist_len, dict_on_device, items, n, 4)) return -1;
-   ZH_TRY(hipMalloc(&C.d_inner, (size_t)n * sizeof(zh_inflate_item_t)));
-   ZH_TRY(hipMalloc(&C.d_members, (size_t)n * sizeof(zh_member_result_t)));
-   // the checksum kernel's two forms: by the room an item has (what it will have written is known on the device only)
+// The checksum kernel's two forms: by the room an item has (what it will have written is known on the device only). Uploads idx and, for gzip, the tables.
+static int zh_check_plan(zh_inflate_call_t &C, const zultra_hip_inflate_item_t *items, uint32_t n, unsigned int framing, uint32_t *pnsmall, uint32_t *pnlarge, uint32_t *pspg) {
    std::vector<uint32_t> idx(n);
    uint32_t nsmall = 0, nlarge = 0, spg = 1;
    for (uint32_t k = 0; k < n; k++)
@@ -2103,6 +2093,27 @@ extern "C" int zultra_hip_inflate_members(int device, const void *src, size_t sr
       ZH_TRY(hipMalloc(&C.d_tables, ZH_CK_TABLE_WORDS * sizeof(uint32_t)));
       ZH_TRY(hipMemcpy(C.d_tables, zh_ck_tables().data(), ZH_CK_TABLE_WORDS * sizeof(uint32_t), hipMemcpyHostToDevice));
    }
+   *pnsmall = nsmall;
+   *pnlarge = nlarge;
+   *pspg = spg;
+   return 0;
+}
+
+// Many gzip / zlib members (or raw streams): headers, inflate, checksums and trailers in three launches on the null stream, one synchronisation at the end.
+extern "C" int zultra_hip_inflate_members(int device, const void *src, size_t src_size, int src_on_device, void *dst, size_t dst_size, int dst_on_device, const void *dict, size_t dict_size,
+                                          int dict_on_device, unsigned int framing, const zultra_hip_inflate_item_t *items, uint32_t n, zultra_hip_member_result_t *results, float *kernel_ms) {
+   ZH_EMU_SERIALIZE();
+   if (kernel_ms) kernel_ms[0] = kernel_ms[1] = kernel_ms[2] = 0.f;
+   if ((!dict && dict_size) || (framing != ZH_M_RAW && framing != ZH_M_ZLIB && framing != ZH_M_GZIP)) return -1;
+   const uint32_t hist_len = (uint32_t)zh_min64(dict_size, ZH_MAX_DIST);
+   const uint8_t *hist = dict ? (const uint8_t *)dict + (dict_size - hist_len) : NULL;
+   zh_inflate_call_t C;
+   if (zh_inflate_args(C, device, src, src_size, dst, dst_size, dst_on_device, hist, hist_len, dict_on_device, items, n, results)) return -1;
+   if (zh_inflate_stage(C, device, src, src_size, src_on_device, dst, dst_size, dst_on_device, hist, hist_len, dict_on_device, items, n, 4)) return -1;
+   ZH_TRY(hipMalloc(&C.d_inner, (size_t)n * sizeof(zh_inflate_item_t)));
+   ZH_TRY(hipMalloc(&C.d_members, (size_t)n * sizeof(zh_member_result_t)));
+   uint32_t nsmall = 0, nlarge = 0, spg = 1;
+   if (zh_check_plan(C, items, n, framing, &nsmall, &nlarge, &spg)) return -1;
    // DICTID (zlib): the Adler-32 of the WHOLE dictionary, once per call — the host's sum of a host dictionary; of a device dictionary the checksum kernel's, as
    // a batch of one item whose "output" is the dictionary (no trailer behind it: its reason is not looked at, its `check` is)
    struct {
@@ -2148,6 +2159,193 @@ extern "C" int zultra_hip_inflate_members(int device, const void *src, size_t sr
       for (int i = 0; i < 3; i++) (void)hipEventElapsedTime(kernel_ms + i, C.ev[i], C.ev[i + 1]);
    return zh_inflate_collect(C, dst, dst_on_device, items, n, results);
 }
+
+// ---- the member index of a whole file (zh_inflate_index.h) -------------------------------------------------------------------------------------------
+static_assert(sizeof(zh_ix_tile_t) == 64, "one record per tile");
+
+// what the two calls below keep of an index between its passes
+struct zh_index_t {
+   uint64_t T = 0, ntiles = 0;
+   uint32_t grid_cap = 0;
+   int cus = 0;
+   zh_ix_totals_t tot = {};
+};
+// 1. the arguments, the device, the source staged
+static int zh_index_stage(zh_inflate_call_t &C, int device, const void *src, size_t src_size, int src_on_device, int nevents) {
+   if (!src || src_size == 0 || device < 0 || device >= zultra_hip_device_count()) return -1;
+   ZH_TRY(hipSetDevice(device));
+   for (int i = 0; i < nevents; i++) ZH_TRY(hipEventCreate(&C.ev[i]));
+   C.s8 = (const uint8_t *)src;
+   if (!src_on_device) {
+      ZH_TRY(hipMalloc(&C.d_src, src_size));
+      ZH_TRY(hipMemcpy(C.d_src, src, src_size, hipMemcpyHostToDevice));
+      C.s8 = (const uint8_t *)C.d_src;
+   }
+   return 0;
+}
+// 2. zh_ix_tiles and zh_ix_resolve between ev[0] and ev[1]; the totals read back (the call's first synchronisation)
+static int zh_index_run(zh_inflate_call_t &C, zh_index_t &X, int device, size_t src_size) {
+   const int tile = zh_env("ZULTRA_HIP_INDEX_TILE", 0);   // tests, tools/inflate_time.py: any value >= 32, no power of two needed
+   X.T = tile >= (int)ZH_IX_TILE_MIN ? (uint64_t)tile : (uint64_t)ZH_IX_TILE;
+   X.ntiles = ((uint64_t)src_size + X.T - 1) / X.T;
+   X.grid_cap = (uint32_t)max(0, zh_env("ZULTRA_HIP_GRID_CAP", 0));   // tests: fewer waves than tiles, every wave strides
+   if (hipDeviceGetAttribute(&X.cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || X.cus <= 0) X.cus = 256;
+   ZH_TRY(hipMalloc(&C.d_ix_tiles, (size_t)X.ntiles * sizeof(zh_ix_tile_t)));
+   ZH_TRY(hipMalloc(&C.d_ix_totals, sizeof(zh_ix_totals_t)));
+   uint32_t grid = (uint32_t)zh_min64(X.ntiles, 32ull * (uint32_t)X.cus);   // (one wave per workgroup, as the inflate kernel)
+   if (X.grid_cap) grid = max(1u, min(grid, X.grid_cap));
+   ZH_TRY(hipEventRecord(C.ev[0], 0));
+   ZH_LAUNCH(zh_ix_tiles, grid, ZH_IX_THREADS, 0, C.s8, (uint64_t)src_size, X.T, X.ntiles, (zh_ix_tile_t *)C.d_ix_tiles);
+   ZH_LAUNCH(zh_ix_resolve, 1, ZH_IX_THREADS, 0, C.s8, (uint64_t)src_size, X.T, X.ntiles, (zh_ix_tile_t *)C.d_ix_tiles, (zh_ix_totals_t *)C.d_ix_totals);
+   ZH_TRY(hipEventRecord(C.ev[1], 0));
+   ZH_TRY(hipMemcpy(&X.tot, C.d_ix_totals, sizeof(X.tot), hipMemcpyDeviceToHost));
+   ZH_TRY(hipGetLastError());
+   return 0;
+}
+static void zh_index_report(const zh_index_t &X, zultra_hip_index_result_t *res) {
+   res->members = (uint32_t)zh_min64(X.tot.members, 0xFFFFFFFFull);
+   res->stop = X.tot.stop;
+   res->out_size = X.tot.out_size;
+   res->src_used = X.tot.src_used;
+   res->tiles = (uint32_t)zh_min64(X.tot.tiles, 0xFFFFFFFFull);
+   res->tiles_rewalked = (uint32_t)zh_min64(X.tot.tiles_rewalked, 0xFFFFFFFFull);
+}
+// 3. zh_ix_items into C.d_items (the index's member count of them), between ev[2] and ev[3]
+static int zh_index_items(zh_inflate_call_t &C, const zh_index_t &X, size_t src_size) {
+   ZH_TRY(hipMalloc(&C.d_items, (size_t)X.tot.members * sizeof(zh_inflate_item_t)));
+   uint32_t grid = (uint32_t)zh_min64((X.ntiles + ZH_IX_THREADS - 1) / ZH_IX_THREADS, 4096);
+   if (X.grid_cap) grid = max(1u, min(grid, X.grid_cap));
+   ZH_TRY(hipEventRecord(C.ev[2], 0));
+   ZH_LAUNCH(zh_ix_items, grid, ZH_IX_THREADS, 0, C.s8, (uint64_t)src_size, X.T, X.ntiles, (const zh_ix_tile_t *)C.d_ix_tiles, (zh_inflate_item_t *)C.d_items);
+   ZH_TRY(hipEventRecord(C.ev[3], 0));
+   return 0;
+}
+static float zh_index_ms(const zh_inflate_call_t &C, bool with_items) {
+   float a = 0.f, b = 0.f;
+   (void)hipEventElapsedTime(&a, C.ev[0], C.ev[1]);
+   if (with_items) (void)hipEventElapsedTime(&b, C.ev[2], C.ev[3]);
+   return a + b;
+}
+
+// The index alone.
+extern "C" int zultra_hip_index_members(int device, const void *src, size_t src_size, int src_on_device, zultra_hip_inflate_item_t *items, uint32_t cap, zultra_hip_index_result_t *res,
+                                        float *kernel_ms) {
+   ZH_EMU_SERIALIZE();
+   if (kernel_ms) *kernel_ms = 0.f;
+   if (!res || (!items && cap)) return -1;
+   memset(res, 0, sizeof(*res));
+   zh_inflate_call_t C;
+   zh_index_t X;
+   if (zh_index_stage(C, device, src, src_size, src_on_device, 4)) return -1;
+   if (zh_index_run(C, X, device, src_size)) return -1;
+   zh_index_report(X, res);
+   const bool want = items != NULL && cap != 0;
+   if (X.tot.members > 0xFFFFFFFFull || (want && X.tot.members > cap)) {
+      res->stop = 4;
+      return -1;
+   }
+   const bool with_items = want && X.tot.members != 0;
+   if (with_items) {
+      if (zh_index_items(C, X, src_size)) return -1;
+      ZH_TRY(hipMemcpy(items, C.d_items, (size_t)X.tot.members * sizeof(zh_inflate_item_t), hipMemcpyDeviceToHost));
+   }
+   ZH_TRY(hipDeviceSynchronize());
+   ZH_TRY(hipGetLastError());
+   if (kernel_ms) *kernel_ms = zh_index_ms(C, with_items);
+   return 0;
+}
+
+// A whole file: the index, then the three launches of zultra_hip_inflate_members over the items where the index left them, in device memory. The index makes
+// the destination ranges disjoint and in range, so nothing is sorted here; the host reads the items once, for the checksum kernel's two forms.
+extern "C" int zultra_hip_inflate_file(int device, const void *src, size_t src_size, int src_on_device, void *dst, size_t dst_size, int dst_on_device, zultra_hip_index_result_t *res,
+                                       zultra_hip_member_result_t *results, uint32_t results_cap, float *kernel_ms) {
+   ZH_EMU_SERIALIZE();
+   if (kernel_ms) kernel_ms[0] = kernel_ms[1] = kernel_ms[2] = kernel_ms[3] = 0.f;
+   if (!res || !dst) return -1;
+   memset(res, 0, sizeof(*res));
+   zh_inflate_call_t C;
+   zh_index_t X;
+   if (zh_index_stage(C, device, src, src_size, src_on_device, 8)) return -1;
+   if (zh_index_run(C, X, device, src_size)) return -1;
+   zh_index_report(X, res);
+   if (X.tot.members > 0xFFFFFFFFull || X.tot.out_size > dst_size || (results && X.tot.members > results_cap)) {
+      res->stop = 4;   // nothing is decoded: res says how much room the file needs
+      return -1;
+   }
+   const uint32_t n = (uint32_t)X.tot.members;
+   if (n == 0) {
+      if (kernel_ms) kernel_ms[0] = zh_index_ms(C, false);
+      return 0;
+   }
+   const size_t out_size = (size_t)X.tot.out_size;
+   if (zh_index_items(C, X, src_size)) return -1;
+   std::vector<zultra_hip_inflate_item_t> items(n);
+   ZH_TRY(hipMemcpy(items.data(), C.d_items, (size_t)n * sizeof(zh_inflate_item_t), hipMemcpyDeviceToHost));
+   ZH_TRY(hipGetLastError());
+   C.d8 = (uint8_t *)dst;
+   const size_t room = dst_on_device ? dst_size : out_size;   // (a host destination is staged: exactly the bytes the index counted)
+   if (!dst_on_device) {
+      ZH_TRY(hipMalloc(&C.d_dst, out_size ? out_size : 1));
+      C.d8 = (uint8_t *)C.d_dst;
+   }
+   ZH_TRY(hipMalloc(&C.d_results, (size_t)n * sizeof(zh_inflate_result_t)));
+   ZH_TRY(hipMalloc(&C.d_inner, (size_t)n * sizeof(zh_inflate_item_t)));
+   ZH_TRY(hipMalloc(&C.d_members, (size_t)n * sizeof(zh_member_result_t)));
+   uint32_t nsmall = 0, nlarge = 0, spg = 1;
+   if (zh_check_plan(C, items.data(), n, ZH_M_GZIP, &nsmall, &nlarge, &spg)) return -1;
+   const zh_inflate_item_t *d_items = (const zh_inflate_item_t *)C.d_items;
+   ZH_TRY(hipEventRecord(C.ev[4], 0));
+   ZH_LAUNCH(zh_frame_heads, (uint32_t)zh_min64(((uint64_t)n + ZH_FRAME_THREADS - 1) / ZH_FRAME_THREADS, 4096), ZH_FRAME_THREADS, 0, C.s8, (uint64_t)src_size, d_items, n, (uint32_t)ZH_M_GZIP, 0u,
+             (const zh_member_result_t *)NULL, (zh_inflate_item_t *)C.d_inner, (zh_member_result_t *)C.d_members);
+   ZH_TRY(hipEventRecord(C.ev[5], 0));
+   if (zh_inflate_launch(C, device, src_size, room, 0, (const zh_inflate_item_t *)C.d_inner, n)) return -1;
+   ZH_TRY(hipEventRecord(C.ev[6], 0));
+   if (zh_check_launch<ZH_M_GZIP>(C.s8, C.d8, room, d_items, (const zh_inflate_result_t *)C.d_results, (zh_member_result_t *)C.d_members, (const uint32_t *)C.d_idx, nsmall, nlarge, spg,
+                                  (const uint32_t *)C.d_tables))
+      return -1;
+   ZH_TRY(hipEventRecord(C.ev[7], 0));
+   std::vector<zultra_hip_member_result_t> own;
+   if (!results) {
+      own.resize(n);
+      results = own.data();
+   }
+   ZH_TRY(hipMemcpy(results, C.d_members, (size_t)n * sizeof(zh_member_result_t), hipMemcpyDeviceToHost));
+   ZH_TRY(hipDeviceSynchronize());
+   ZH_TRY(hipGetLastError());
+   if (kernel_ms) {
+      kernel_ms[0] = zh_index_ms(C, true);
+      for (int i = 1; i < 4; i++) (void)hipEventElapsedTime(kernel_ms + i, C.ev[3 + i], C.ev[4 + i]);
+   }
+   int bad = 0;
+   bool whole = true;   // every member wrote all of its range
+   for (uint32_t k = 0; k < n; k++) {
+      if (results[k].reason != 0) bad++;
+      if (results[k].out_size > items[k].dst_cap) return -1;   // (the kernel checks every store: never)
+      whole = whole && results[k].out_size == items[k].dst_cap;
+   }
+   if (!dst_on_device && out_size) {   // of a host dst only the out_size bytes of every member are written
+      if (whole)
+         ZH_TRY(hipMemcpy(dst, C.d8, out_size, hipMemcpyDeviceToHost));
+      else {
+         std::vector<uint8_t> span(out_size);
+         ZH_TRY(hipMemcpy(span.data(), C.d8, out_size, hipMemcpyDeviceToHost));
+         for (uint32_t k = 0; k < n; k++) memcpy((uint8_t *)dst + items[k].dst_off, span.data() + items[k].dst_off, (size_t)results[k].out_size);
+      }
+   }
+   return bad;
+}
+
+// For libzultra.cpp, which has no HIP of its own: a device copy of a host buffer, so that a call that walks a file run by run uploads it once.
+extern "C" void *zh_device_upload(int device, const void *host, size_t n) {
+   void *p = NULL;
+   if (!host || n == 0 || device < 0 || device >= zultra_hip_device_count() || hipSetDevice(device) != hipSuccess || hipMalloc(&p, n) != hipSuccess) return NULL;
+   if (hipMemcpy(p, host, n, hipMemcpyHostToDevice) != hipSuccess) {
+      (void)hipFree(p);
+      return NULL;
+   }
+   return p;
+}
+extern "C" void zh_device_release(void *p) { (void)hipFree(p); }
 
 extern "C" void zultra_hip_last_timing(const zultra_hip_ctx_t *c, zultra_hip_timing_t *t) {
    if (c && t) *t = c->timing;

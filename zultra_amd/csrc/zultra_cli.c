@@ -8,6 +8,7 @@
  *
  *    zultra_amd_cli [-b <max block size>] [-f gzip|zlib|raw] [-k <chunk KiB>] [-d <device>] [-D <dictionary>] [-c] [-v] <infile> <outfile>
  *    zultra_amd_cli -x [-f gzip|zlib|raw] [-d <device>] [-D <dictionary>] [-v] <infile> <outfile>
+ *    zultra_amd_cli -x -m [-f gzip] [-d <device>] [-v] <infile> <outfile>
  *
  * -D: a preset dictionary, loaded as the reference's tool loads it (zultra_dictionary_load: the last 32 KiB of the file; tool/zultra.c -D). Compressing,
  *     it is set before the first zultra_stream_compress (zultra_stream_set_dictionary: the history of the first max-block; a zlib header gets FDICT and
@@ -16,6 +17,9 @@
  *     run with a non-zero status. With -v the number of bytes checked is printed.
  * -x: extract — <infile> is one stream in the framing -f names, inflated on the device (zultra_memory_decompress: header, checksum and the end of
  *     the stream are checked); a stream that does not decode ends the run with a non-zero status and an empty <outfile>.
+ * -m: with -x -f gzip — <infile> is any number of gzip members back to back (bgzip, pigz -i, cat a.gz b.gz) and <outfile> the concatenation of their
+ *     outputs (zultra_memory_decompress_members: runs of BGZF members are indexed and inflated on the device in one batch). No dictionary. With -v
+ *     the members, the index's tiles and the tiles walked again are printed.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -23,6 +27,7 @@
 #include <time.h>
 
 #include "../../include/libzultra.h"
+#include "../../include/zultra_hip.h"
 
 static double now_s(void) {
    struct timespec ts;
@@ -32,7 +37,7 @@ static double now_s(void) {
 
 /* -x: the whole file through zultra_memory_decompress. The output size is not known in advance (gzip's ISIZE is a hint, modulo 2^32): the buffer
  * grows until the call succeeds or the bound of the format is passed (a deflate stream expands at most 1032 : 1). */
-static int extract(FILE *fin, FILE *fout, unsigned flags, int verbose, const void *dict, int dict_size) {
+static int extract(FILE *fin, FILE *fout, unsigned flags, int verbose, const void *dict, int dict_size, int members, int device) {
    size_t n = 0, cap = (size_t)1 << 20;
    unsigned char *in = (unsigned char *)malloc(cap);
    for (size_t got; in && (got = fread(in + n, 1, cap - n, fin)) > 0;) {
@@ -46,6 +51,13 @@ static int extract(FILE *fin, FILE *fout, unsigned flags, int verbose, const voi
    const size_t bound = n * 1032 + 1024;
    size_t room = n * 4 + 4096, size = (size_t)-1;
    if ((flags & ZULTRA_FLAG_GZIP_FRAMING) && n >= 18) room = (size_t)in[n - 4] | ((size_t)in[n - 3] << 8) | ((size_t)in[n - 2] << 16) | ((size_t)in[n - 1] << 24);
+   /* -m: where the whole file indexes (a BGZF file), the index says how much room it needs; else the buffer grows as above */
+   zultra_hip_index_result_t ix;
+   memset(&ix, 0, sizeof(ix));
+   size_t nmembers = 0;
+   const int indexed = members && n && zultra_hip_index_members(device, in, n, 0, NULL, 0, &ix, NULL) == 0;
+   if (indexed && ix.stop == 0) room = (size_t)ix.out_size;
+   else if (members) room = n * 4 + 4096;   /* (the last member's ISIZE says nothing about the others) */
    const double t0 = now_s();
    unsigned char *out = NULL;
    for (;;) {
@@ -53,7 +65,9 @@ static int extract(FILE *fin, FILE *fout, unsigned flags, int verbose, const voi
       free(out);
       out = (unsigned char *)malloc(room ? room : 1);
       if (!out) break;
-      size = dict ? zultra_memory_decompress_dict(in, n, out, room, flags, dict, dict_size) : zultra_memory_decompress(in, n, out, room, flags);
+      size = members ? zultra_memory_decompress_members(in, n, out, room, &nmembers)
+             : dict  ? zultra_memory_decompress_dict(in, n, out, room, flags, dict, dict_size)
+                     : zultra_memory_decompress(in, n, out, room, flags);
       if (size != (size_t)-1 || room == bound) break;
       room = room < 4096 ? 8192 : room * 2;
    }
@@ -68,6 +82,8 @@ static int extract(FILE *fin, FILE *fout, unsigned flags, int verbose, const voi
       rc = 100;
    }
    if (verbose && !rc) fprintf(stdout, "%llu -> %llu bytes, %.1f MB/s\n", (unsigned long long)n, (unsigned long long)size, dt > 0 ? (double)size / dt / 1e6 : 0.0);
+   if (verbose && !rc && members)
+      fprintf(stdout, "%llu members; the index from the start of the file: %u members, %u tiles, %u rewalked\n", (unsigned long long)nmembers, ix.members, ix.tiles, ix.tiles_rewalked);
    free(in);
    free(out);
    return rc;
@@ -76,15 +92,16 @@ static int extract(FILE *fin, FILE *fout, unsigned flags, int verbose, const voi
 int main(int argc, char **argv) {
    unsigned flags = ZULTRA_FLAG_GZIP_FRAMING, block = 0;
    size_t chunk = (size_t)8 << 20;
-   int verbose = 0, verify = 0, do_extract = 0, i = 1;
+   int verbose = 0, verify = 0, do_extract = 0, members = 0, device = 0, i = 1;
    const char *dict_name = NULL;
+   if (getenv("ZULTRA_HIP_DEVICE")) device = atoi(getenv("ZULTRA_HIP_DEVICE"));   /* (the library's own default: -m sizes its buffer with an index call on the same device) */
    for (; i < argc && argv[i][0] == '-' && argv[i][1]; i++) {
       if (!strcmp(argv[i], "-b") && i + 1 < argc)
          block = (unsigned)strtoul(argv[++i], NULL, 0);
       else if (!strcmp(argv[i], "-k") && i + 1 < argc)
          chunk = (size_t)strtoul(argv[++i], NULL, 0) << 10;
       else if (!strcmp(argv[i], "-d") && i + 1 < argc)
-         zultra_set_device(atoi(argv[++i]));
+         zultra_set_device(device = atoi(argv[++i]));
       else if (!strcmp(argv[i], "-f") && i + 1 < argc) {
          const char *f = argv[++i];
          flags = !strcmp(f, "gzip") ? ZULTRA_FLAG_GZIP_FRAMING : !strcmp(f, "zlib") ? ZULTRA_FLAG_ZLIB_FRAMING : ZULTRA_FLAG_DEFLATE_FRAMING;
@@ -95,6 +112,8 @@ int main(int argc, char **argv) {
          verbose = 1;
       else if (!strcmp(argv[i], "-x"))
          do_extract = 1;
+      else if (!strcmp(argv[i], "-m"))
+         members = 1;
       else if (!strcmp(argv[i], "-c")) {
          verify = 1;
          zultra_set_verify(1);
@@ -102,9 +121,10 @@ int main(int argc, char **argv) {
       else
          break;
    }
-   if (argc - i != 2 || chunk == 0) {
+   if (argc - i != 2 || chunk == 0 || (members && (!do_extract || flags != ZULTRA_FLAG_GZIP_FRAMING || dict_name))) {
       fprintf(stderr, "usage: %s [-b <max block size>] [-f gzip|zlib|raw] [-k <chunk KiB>] [-d <device>] [-D <dictionary>] [-c] [-v] <infile> <outfile>\n"
-                      "       %s -x [-f gzip|zlib|raw] [-d <device>] [-D <dictionary>] [-v] <infile> <outfile>\n", argv[0], argv[0]);
+                      "       %s -x [-f gzip|zlib|raw] [-d <device>] [-D <dictionary>] [-v] <infile> <outfile>\n"
+                      "       %s -x -m [-f gzip] [-d <device>] [-v] <infile> <outfile>   (any number of gzip members: BGZF, pigz -i, cat a.gz b.gz)\n", argv[0], argv[0], argv[0]);
       return 100;
    }
    void *dict = NULL;
@@ -126,7 +146,7 @@ int main(int argc, char **argv) {
       return 100;
    }
    if (do_extract) {
-      const int xrc = extract(fin, fout, flags, verbose, dict, dict_size);
+      const int xrc = extract(fin, fout, flags, verbose, dict, dict_size, members, device);
       fclose(fin);
       fclose(fout);
       zultra_dictionary_free(&dict);

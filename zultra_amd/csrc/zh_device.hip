@@ -155,6 +155,9 @@ struct zultra_hip_ctx_s {
                                                      // length class and their positions, cut tasks / segments, the tickets of the persistent kernels per pass
    uint32_t *h_ntasks;          // pinned mirror, read after the batch (zultra_hip_last_stats)
    uint32_t *d_hugelist;
+   uint32_t *d_lanelist, *d_lane_acc;   // the bundles of zh_parse_lanes by length class, ZH_LANE_CLASSES lists per run, and the word per task they are gathered in (zh_parse.h); not in files mode
+   int lane_bundles;                    // ZULTRA_HIP_LANE_BUNDLES (default 1; 0: no lists are kept, the hand-out of before bundles)
+   uint32_t lane_order, lane_tasks;     // ZULTRA_HIP_LANE_ORDER (1, the default: by length class; 0: one list, in the order of arrival), ZULTRA_HIP_LANE_TASKS (0: zh_tasks_per_wave picks)
    uint4 *d_segtasks;           // tasks cut into speculative segments (zh_parse_chain.h): per max-block seg_tasks_per_block entries
    uint2 *d_segitems;           // their segments, as jobs of zh_parse_chain: per max-block seg_items_per_block entries
    uint2 *d_segwaves;           // ... or as segment waves of zh_parse_lanes' launch (four segments each), likewise
@@ -551,6 +554,8 @@ extern "C" void zultra_hip_destroy(zultra_hip_ctx_t *c) {
    if (c->h_scan_out) (void)hipHostFree(c->h_scan_out);
    (void)hipFree(c->d_ntasks);
    (void)hipFree(c->d_hugelist);
+   (void)hipFree(c->d_lanelist);
+   (void)hipFree(c->d_lane_acc);
    (void)hipFree(c->d_segtasks);
    (void)hipFree(c->d_segwaves);
    (void)hipFree(c->d_segitems);
@@ -737,6 +742,9 @@ static int zh_create_buffers(zultra_hip_ctx_t *c) {
       c->chain_seen_runs = 0;
       c->grid_cap = (uint32_t)max(0, zh_env("ZULTRA_HIP_GRID_CAP", 0));   // tests: cap of the <false> grids of zh_sb_init / zh_sb_build / zh_list_huge / zh_post_tasks / zh_emit_tasks (0: none) — the
                                                                           // <true> forms that stride over what lies beyond a grid are otherwise reached by heavily splitting data only
+      c->lane_order = zh_env("ZULTRA_HIP_LANE_ORDER", 1) != 0;         // 1: zh_parse_lanes takes its bundles longest class first; 0: as zh_list_huge completed them (the A/B of the order)
+      c->lane_bundles = zh_env("ZULTRA_HIP_LANE_BUNDLES", 1) != 0;     // 0: no bundle lists are kept, zh_parse_lanes takes consecutive tasks of the task list as it did before bundles (the A/B of the bundles)
+      c->lane_tasks = (uint32_t)min(max(0, zh_env("ZULTRA_HIP_LANE_TASKS", 0)), (int)ZH_LP_TASKS);   // tasks per bundle; 0: by the run's size (zh_tasks_per_wave: one below a chip's worth of tasks)
       c->seg_wide = (uint32_t)zh_env("ZULTRA_HIP_SEG_WIDE", 1024);     // a run with at least this many segments parses them in the segment workgroups of zh_parse_lanes' launch
       c->mf_lds_cap = (uint32_t)max(0, zh_env("ZULTRA_HIP_MF_CAP", (int)ZH_MFL_CAP_LIMIT));   // elements per chunk of zh_mf_group's refinement in LDS (zh_mf_group_lds.h)
       const int streams = zh_env("ZULTRA_HIP_STREAMS", 0);              // staggered runs per batch; not set: three, four for batches of 256 MiB and more
@@ -785,6 +793,7 @@ static int zh_create_buffers(zultra_hip_ctx_t *c) {
        zh_alloc(c, &c->d_nsubs, 1 + ZH_MAX_RUNS) || zh_alloc(c, &c->d_blk_start, B + 1) || zh_alloc(c, &c->d_scan_out, 1) || (c->files_mode && (zh_alloc(c, &c->d_file_off, B + 1) || zh_alloc(c, &c->d_task_prefix, B + 1))) ||
        zh_alloc(c, &c->d_prev3, B * c->segs_per_block * c->sort_stride) || zh_alloc(c, &c->d_runs, B * c->segs_per_block * c->run_stride) ||
        zh_alloc(c, &c->d_segs, B * c->segs_per_block) || zh_alloc(c, &c->d_chunk_ctr, 2 * B * c->segs_per_block + 3 * ZH_MAX_RUNS) || zh_alloc(c, &c->d_ntasks, ZH_NCNT) || zh_alloc(c, &c->d_hugelist, 4 * c->max_tasks) ||
+       (!c->files_mode && (zh_alloc(c, &c->d_lanelist, ZH_LANE_CLASSES * c->max_tasks) || zh_alloc(c, &c->d_lane_acc, c->max_tasks))) ||
        zh_alloc(c, &c->d_segtasks, B * c->seg_tasks_per_block) || zh_alloc(c, &c->d_segwaves, B * c->seg_items_per_block) || zh_alloc(c, &c->d_segitems, B * c->seg_items_per_block) ||
        zh_alloc(c, &c->d_vecs, B * c->seg_items_per_block * 2 * ZH_VEC) || zh_alloc(c, &c->d_hist_part, c->max_tasks * ZH_NSYM) || zh_alloc(c, &c->d_task_bits, c->max_tasks))
       return -1;
@@ -974,7 +983,10 @@ static int zh_build_segments(zultra_hip_ctx_t *c, const zultra_hip_block_t *bloc
 
 // tasks a wave of zh_parse_lanes takes (zh_parse_lanes.h): as many as ZH_LP_TASKS, as few as it takes to fill the chip's wave slots
 static uint32_t zh_tasks_per_wave(const zultra_hip_ctx_t *c, uint32_t ntasks) {
-   const uint32_t slots = c->total_cus * 8u;   // (measured: eight tasks per wave at 16 K tasks per run beat four by 2 % of the step)
+   if (c->lane_tasks && !c->files_mode) return c->lane_tasks;
+   // (measured on the 100 MB step with the bundles handed out longest class first, bench.py --config 2, two runs each: T = 8 44.54 / 44.32 ms, T = 4 47.40 / 47.36,
+   // T = 2 50.39 / 50.12; in the order of arrival: 45.64 / 45.35, 47.73 / 47.61, 50.05 / 50.35 — eight stays. profiles/lane_order_time.txt)
+   const uint32_t slots = c->total_cus * 8u;
    return max(1u, min((uint32_t)ZH_LP_TASKS, (ntasks + slots - 1) / slots));
 }
 
@@ -1044,6 +1056,9 @@ static int zh_enqueue_run(zultra_hip_ctx_t *c, int k, uint32_t b0, uint32_t nb, 
    uint2 *taskmap = c->d_taskmap + t0;
    uint2 *taskinfo = c->d_taskinfo + t0;
    uint32_t *hist_part = c->d_hist_part + t0 * ZH_NSYM, *task_bits = c->d_task_bits + t0;
+   // the bundles of zh_parse_lanes (zh_parse.h): ZH_LANE_CLASSES lists of `cap` entries; files mode keeps none — its inputs are one sub-block of a task or two each
+   const bool bundles = !files && c->lane_bundles != 0;
+   uint32_t *lanelist = bundles ? c->d_lanelist + ZH_LANE_CLASSES * t0 : (uint32_t *)NULL, *lane_acc = bundles ? c->d_lane_acc + t0 : (uint32_t *)NULL;
    uint32_t *hugelist = c->d_hugelist + 4 * t0;   // four lists of `cap` entries each: three by zh_list_huge, the cut tasks given up on by the segment workgroups
    const uint32_t cap = (uint32_t)zh_min64((uint64_t)nb * tasks_per_block, 0xFFFFFFFFull);
    uint4 *segtasks = c->d_segtasks + (uint64_t)b0 * c->seg_tasks_per_block;
@@ -1111,7 +1126,7 @@ static int zh_enqueue_run(zultra_hip_ctx_t *c, int k, uint32_t b0, uint32_t nb, 
    // ---- stage 3: the sub-block coder, one kernel per step over the run (zh_encode.h) -----------------------------------------------------
 #define ZH_LAUNCH_PLAN(T_)                                                                                                                                                               \
    ZH_LAUNCH(zh_plan_subblocks<T_>, 1, T_, st, blk, nb, (const uint32_t *)(c->d_tok_pos + (uint64_t)b0 * c->tok_stride), c->tok_stride, (const uint32_t *)(c->d_ntok + b0),              \
-             (const uint32_t *)(c->d_split_tok + (uint64_t)b0 * (ZH_MAX_SPLITS + 1)), (const uint32_t *)(c->d_split_cnt + b0), c->d_sub_base + b0, c->slot_stride, work, taskmap, cnt)
+             (const uint32_t *)(c->d_split_tok + (uint64_t)b0 * (ZH_MAX_SPLITS + 1)), (const uint32_t *)(c->d_split_cnt + b0), c->d_sub_base + b0, c->slot_stride, work, taskmap, cnt, lane_acc)
    if (files)   // one sub-block per input, the task ranges from the sizes the host was handed (zh_plan_files)
       ZH_LAUNCH(zh_plan_files, (nb + ZH_PLAN_FILES_THREADS - 1) / ZH_PLAN_FILES_THREADS, ZH_PLAN_FILES_THREADS, st, blk, nb, (const uint32_t *)(c->d_ntok + b0), (const uint32_t *)(c->d_task_prefix + b0),
                 c->d_sub_base + b0, c->slot_stride, work, taskmap, cnt);
@@ -1121,15 +1136,16 @@ static int zh_enqueue_run(zultra_hip_ctx_t *c, int k, uint32_t b0, uint32_t nb, 
       ZH_LAUNCH_PLAN(256u);
 #undef ZH_LAUNCH_PLAN
    ZH_LAUNCH_BOTH(zh_sb_init, sb_grid, sb_bound, st, (const uint16_t *)(c->d_tok_info + (uint64_t)b0 * c->tok_stride), c->tok_stride, (const zh_work_t *)work, states, (const uint32_t *)cnt);
+   const uint32_t tpw = zh_tasks_per_wave(c, est_tasks);   // tasks per bundle of zh_parse_lanes: zh_list_huge lists the bundles
+   const zh_lane_order_t lane_lo = {lanelist, lane_acc, tpw, c->lane_order};
    // (inputs of a files batch are never cut into speculative segments: seg_min = all ones; a run of at most as many tasks as CUs counts as small)
    ZH_LAUNCH_BOTH(zh_list_huge, task_grid, cap, st, blk, bars, c->bar_stride, (const zh_work_t *)work, (const uint2 *)taskmap, (const uint32_t *)(c->d_match + (uint64_t)b0 * c->match_stride),
              c->match_stride, hugelist, cap, segtasks, segitems, segwaves, files ? 0xFFFFFFFFu : (uint32_t)ZH_CUT_MIN, (uint32_t)ZH_CUT_LEN, cnt, taskinfo, (uint32_t)ZH_COOP_MIN,
-             files ? (uint32_t)ZH_COOP_MIN : c->coop_small, files ? 0u : c->num_cus);
+             files ? (uint32_t)ZH_COOP_MIN : c->coop_small, files ? 0u : c->num_cus, lane_lo);
    if (!files) ZH_CHECK(c, hipEventRecord(ev[ZH_EV_INIT], st));   // (timing marks)
    // Persistent workgroups of zh_parse_chain take the listed chains from a ticket (none listed: they leave at once); zh_parse_lanes takes the task
    // list in groups, as a grid that fills the chip's wave slots — next to chains only ZH_LANE_WAVES per CU stay, so that the chain workgroups find
    // room the moment they are launched (the run's counters tell the kernel which); the first workgroups of zh_parse_lanes' grid take the cut tasks' segments when there are many.
-   const uint32_t tpw = zh_tasks_per_wave(c, est_tasks);
    const uint32_t lane_grid = max(1u, min((est_tasks + tpw - 1) / tpw, c->num_cus * 16u));
    // (two chain workgroups fit a CU — 169 registers, four waves — and they are persistent: a third per CU would only queue behind them, find the tickets
    // gone and leave; and in a run without chains every workgroup of this grid has to find a slot among the quad kernel's waves before the pass can end)
@@ -1169,7 +1185,7 @@ static int zh_enqueue_run(zultra_hip_ctx_t *c, int k, uint32_t b0, uint32_t nb, 
          sg.seg_grid = files ? 0u : seg_grid;
          ZH_LAUNCH(zh_parse_lanes, sg.seg_grid + lane_grid, 64, st, c->cur_data, blk, match, c->match_stride, bars, c->bar_stride, (const zh_work_t *)work, (const uint2 *)taskmap, cnt,
                    (const zh_sbstate_t *)states, best, c->best_stride, cost, hist_part, pass, cnt + ZH_CNT_TASK_TICKET + pass, (const uint2 *)taskinfo, tpw,
-                   files ? 0xFFFFFFFFu : c->num_cus * ZH_LANE_WAVES, sg);
+                   files ? 0xFFFFFFFFu : c->num_cus * ZH_LANE_WAVES, sg, (const uint32_t *)lanelist, cap);
       }
       if (!chains_idle) ZH_CHECK(c, hipStreamWaitEvent(st, c->side_ev[k][2 * pass + 1], 0));
       if (!files) ZH_CHECK(c, hipEventRecord(ev[ZH_EV_PARSE0 + 2 * pass], st));   // (timing marks)

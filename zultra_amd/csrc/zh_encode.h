@@ -46,7 +46,8 @@ template <uint32_t ZH_PLAN_THREADS>
 __global__ void __launch_bounds__(ZH_PLAN_THREADS)
 zh_plan_subblocks(const zh_block_t *__restrict__ blocks, uint32_t nblocks, const uint32_t *__restrict__ tok_pos, uint64_t tok_stride, const uint32_t *__restrict__ ntok,
                   const uint32_t *__restrict__ split_tok, const uint32_t *__restrict__ split_cnt, uint32_t *sub_base /* out: exclusive scan of split_cnt */,
-                  uint64_t slot_stride, zh_work_t *work, uint2 *taskmap, uint32_t *cnt /* the run's counters */) {
+                  uint64_t slot_stride, zh_work_t *work, uint2 *taskmap, uint32_t *cnt /* the run's counters */,
+                  uint32_t *lane_acc /* a word per task, cleared here: where zh_list_huge gathers the bundles of zh_parse_lanes (zh_parse.h) */) {
    __shared__ uint32_t wsum[2][ZH_PLAN_THREADS / 64];
    __shared__ uint32_t carry[2];
    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
@@ -113,6 +114,7 @@ zh_plan_subblocks(const zh_block_t *__restrict__ blocks, uint32_t nblocks, const
                e.x = w.index;
                e.y = j;
                taskmap[w.task_base + j] = e;
+               if (lane_acc) lane_acc[w.task_base + j] = 0;
             }
             work[w.index] = w;
             task0 += w.ntasks;

@@ -102,8 +102,35 @@ enum {
    ZH_CNT_DEMOTED = 23 /* cut tasks handed to zh_parse_chain as whole chains for the passes left (zh_parse_one_task) */, ZH_CNT_DEMOTED_PASS = 24 /* .. 27: listed in pass p */,
    ZH_CNT_NSUBS = 28 /* sub-blocks of the run (zh_plan_subblocks: the host never sees the splitter's counts) */,
    ZH_CNT_NOCHAINS = 29 /* set by the HOST when it enqueues the run: no chain kernels were launched for it (zh_run_is_void) */,
-   ZH_CNT_SBGRID = 30, ZH_CNT_TASKGRID = 31 /* set by the HOST (non-zero) when it launches no <true> overflow forms for the run: the grids of its <false> forms */, ZH_CNT_STRIDE = 32
+   ZH_CNT_SBGRID = 30, ZH_CNT_TASKGRID = 31 /* set by the HOST (non-zero) when it launches no <true> overflow forms for the run: the grids of its <false> forms */,
+   ZH_CNT_LANE_CLASS = 32 /* .. 35: bundles of zh_parse_lanes in length class c (zh_list_huge; below) */, ZH_CNT_STRIDE = 40
 };
+
+// ---- what a wave of zh_parse_lanes takes: a BUNDLE, handed out longest first -------------------------------------------------------------------------
+// A bundle is up to T consecutive tasks of ONE sub-block (tasks j with the same j / T; T = the host's tasks per wave): a sub-block of n tasks has
+// ceil(n / T) of them, and none spans two sub-blocks — one price table, one call of zh_lp_group per ticket. A pass of zh_parse_lanes ends when its
+// last wave does, and what a wave cannot shorten is its longest piece (one quad's chain of dependent steps, up to ZH_COOP_MIN of them): so the
+// bundles are listed in ZH_LANE_CLASSES classes by the longest piece among their tasks that are parsed on the quads, each class a list of its own
+// with a counter among the run's (as the chain lists are, zh_parse_chain.h), and a ticket walks the classes longest first. The lists are filled
+// once per run, by zh_list_huge — which visits every task and computes its pieces anyway — and serve all four passes. Nothing waits for anything:
+// each task's wave adds its class to a word of its bundle (a 6-bit count per class, and one of the tasks that are listed for the chain kernel or
+// cut into segments), and the wave whose addition completes the bundle lists it — under its highest class; a bundle whose tasks are all listed
+// elsewhere gets no entry and no ticket. The order inside a class is the order of arrival and does not matter: a task's outputs go to its own slots.
+// MEASURED (profiles/lane_order_time.txt, 100 MB of text): the bundles take 2.8 ms off the 48.3 ms step, the order by class 0.9 ms more.
+#define ZH_LANE_CLASSES 4u
+#define ZH_LANE_FIELD 6u            // bits per count in a bundle's word: T <= 63
+#define ZH_LANE_NOQUAD ZH_LANE_CLASSES   // the field of the tasks with nothing for the quads
+// what zh_list_huge is given to fill the lists: lists = ZH_LANE_CLASSES lists of `cap` entries (a bundle's first task); acc = a word per task slot, zero
+// (zh_plan_subblocks clears it), used at a bundle's first task; NULL lists: none are kept (files mode, zh_device.hip)
+struct zh_lane_order_t {
+   uint32_t *lists, *acc;
+   uint32_t tasks;     // T
+   uint32_t ordered;   // 0 (ZULTRA_HIP_LANE_ORDER=0): every bundle goes to the first list, in the order in which the waves of zh_list_huge complete them —
+                       // close to list order, not list order itself; it isolates the order. The hand-out of before bundles is ZULTRA_HIP_LANE_BUNDLES=0.
+};
+// class of a task by its longest piece: a bundle of T tasks is ~ T * ZH_TASK / 16 = 128 T positions per quad, so a piece of 1024 outlasts the rest
+// of a bundle of eight, one of 320 that of a bundle of two
+__device__ __forceinline__ uint32_t zh_lane_class(uint32_t longest) { return longest >= 1024u ? 0u : (longest >= 640u ? 1u : (longest >= 320u ? 2u : 3u)); }
 static_assert(ZH_CNT_TASKS == 0, "zh_post_tasks / zh_emit_tasks take the run's counter block as the pointer to its task count");
 
 // A stream without chains must not pay for them (round 6). Whether a run lists anything for zh_parse_chain is known on the device only, and an empty chain grid still

@@ -399,7 +399,7 @@ __device__ inline void zh_chain_parse(zh_chain_ws_t &ws, const uint4 *rows, cons
 __device__ __forceinline__ void zh_list_huge_one(uint32_t *bnd /* LDS, ZH_MAXPIECES + 1 */, uint32_t gt, const zh_block_t *__restrict__ blocks, const uint64_t *__restrict__ bars, uint64_t bar_stride,
                                                  const zh_work_t *__restrict__ work, const uint2 *__restrict__ taskmap, const uint32_t *__restrict__ longest, uint64_t longest_stride,
                                                  uint32_t *hugelist, uint32_t cap, uint4 *segtasks, uint2 *segitems, uint2 *segwaves, uint32_t seg_min, uint32_t cut_len, uint32_t *cnt,
-                                                 uint2 *taskinfo, uint32_t coop_min) {
+                                                 uint2 *taskinfo, uint32_t coop_min, zh_lane_order_t lo) {
    const uint2 tm = taskmap[gt];
    const zh_work_t wk = work[tm.x];
    const uint32_t prev = blocks[wk.block].prev;
@@ -413,6 +413,26 @@ __device__ __forceinline__ void zh_list_huge_one(uint32_t *bnd /* LDS, ZH_MAXPIE
    // the task's range and whether it is listed here, for the four passes of zh_parse_lanes: looking a boundary up means scanning the
    // barrier bitmap, 64 positions per dependent load — on data with few barriers that was a third of that kernel's time
    if (lane == 0) taskinfo[gt] = make_uint2(t0, t1 | (huge ? 0x80000000u : 0u));
+   if (lo.lists) {
+      // the task's part in its bundle of zh_parse_lanes (zh_parse.h): its class by its longest piece; the wave that completes the bundle lists it
+      const uint32_t plen = lane < np ? bnd[lane + 1] - bnd[lane] : 0u;
+      uint32_t field = ZH_LANE_CLASSES - 1u;
+      for (uint32_t cl = ZH_LANE_CLASSES - 1u; cl-- > 0u;)
+         if (zh_ballot(zh_lane_class(plen) <= cl)) field = cl;
+      if (!lo.ordered) field = 0;   // one list, in the order of arrival
+      if (huge) field = ZH_LANE_NOQUAD;
+      if (lane == 0) {
+         const uint32_t j0 = tm.y - tm.y % lo.tasks, n = min(lo.tasks, wk.ntasks - j0);
+         const uint32_t acc = atomicAdd(&lo.acc[gt - (tm.y - j0)], 1u << (ZH_LANE_FIELD * field)) + (1u << (ZH_LANE_FIELD * field));
+         uint32_t seen = 0, top = ZH_LANE_NOQUAD;
+         for (uint32_t cl = ZH_LANE_NOQUAD + 1u; cl-- > 0u;) {
+            const uint32_t k = (acc >> (ZH_LANE_FIELD * cl)) & ((1u << ZH_LANE_FIELD) - 1u);
+            seen += k;
+            if (k) top = cl;
+         }
+         if (seen == n && top != ZH_LANE_NOQUAD) lo.lists[top * cap + atomicAdd(&cnt[ZH_CNT_LANE_CLASS + top], 1u)] = gt - (tm.y - j0);
+      }
+   }
    if (!huge) return;
    const uint32_t len = t1 - t0;
    if (len >= seg_min) {
@@ -469,17 +489,17 @@ __global__ void __launch_bounds__(64)
 zh_list_huge(const zh_block_t *__restrict__ blocks, const uint64_t *__restrict__ bars, uint64_t bar_stride, const zh_work_t *__restrict__ work,
              const uint2 *__restrict__ taskmap, const uint32_t *__restrict__ longest, uint64_t longest_stride, uint32_t *hugelist, uint32_t cap, uint4 *segtasks,
              uint2 *segitems, uint2 *segwaves, uint32_t seg_min, uint32_t cut_len, uint32_t *cnt, uint2 *taskinfo,
-             uint32_t coop_min /* <= ZH_COOP_MIN */, uint32_t coop_small /* <= coop_min */, uint32_t small_tasks, uint32_t first) {
+             uint32_t coop_min /* <= ZH_COOP_MIN */, uint32_t coop_small /* <= coop_min */, uint32_t small_tasks, zh_lane_order_t lo, uint32_t first) {
    __shared__ uint32_t bnd[ZH_MAXPIECES + 1];
    const uint32_t ntasks = cnt[ZH_CNT_TASKS];
    const uint32_t cm = ntasks <= small_tasks ? coop_small : coop_min;
    if (!MORE) {
-      if (blockIdx.x < ntasks) zh_list_huge_one(bnd, blockIdx.x, blocks, bars, bar_stride, work, taskmap, longest, longest_stride, hugelist, cap, segtasks, segitems, segwaves, seg_min, cut_len, cnt, taskinfo, cm);
+      if (blockIdx.x < ntasks) zh_list_huge_one(bnd, blockIdx.x, blocks, bars, bar_stride, work, taskmap, longest, longest_stride, hugelist, cap, segtasks, segitems, segwaves, seg_min, cut_len, cnt, taskinfo, cm, lo);
       return;
    }
    for (uint32_t gt = first + blockIdx.x; gt < ntasks; gt += gridDim.x) {
       zh_sync();   // the task before this one is done with bnd
-      zh_list_huge_one(bnd, gt, blocks, bars, bar_stride, work, taskmap, longest, longest_stride, hugelist, cap, segtasks, segitems, segwaves, seg_min, cut_len, cnt, taskinfo, cm);
+      zh_list_huge_one(bnd, gt, blocks, bars, bar_stride, work, taskmap, longest, longest_stride, hugelist, cap, segtasks, segitems, segwaves, seg_min, cut_len, cnt, taskinfo, cm, lo);
    }
 }
 

@@ -27,8 +27,9 @@
 // Memory: the quad fetches four positions per request — lane q the row, the second plane of the row and the byte of position
 // p-1-q — two batches ahead of their use, stages them in LDS, and stores the four parse entries of a batch with one instruction.
 //
-// Work: a wave takes ZH_LP_TASKS consecutive tasks of the run's task list (zh_parse.h: a task = ~2048 positions between two
-// barriers), groups them by sub-block (prices differ), cuts each task into pieces (zh_task_pieces) and hands the
+// Work: a wave takes a bundle — up to ZH_LP_TASKS consecutive tasks of one sub-block (one set of prices), from the run's lists of bundles by their
+// longest piece, longest class first (zh_parse.h; files mode: consecutive tasks of the task list, grouped by sub-block) — cuts each task
+// (zh_parse.h: a task = ~2048 positions between two barriers) into pieces (zh_task_pieces) and hands the
 // pieces to its quads, the long ones first, a new one whenever a quad runs out. Tasks with a barrier-free run of more than
 // ZH_COOP_MIN positions are left to zh_parse_chain / the segment workgroups of this launch (zh_list_huge lists them with the same
 // test). The histogram of the chosen parse (blockdeflate.c:371-400) is taken by the 64 lanes, each walking pieces forward (a
@@ -54,6 +55,7 @@
 // (zh_task_pieces); a group whose pieces outgrew ZH_LP_MAXP would silently lose a task — variant builds (-D...) must keep these
 static_assert((ZH_TASK + ZH_COOP_MIN + ZH_PIECE - 1) / ZH_PIECE <= ZH_LP_PPT && ZH_LP_PPT <= ZH_MAXPIECES, "pieces per task must stay within ZH_LP_PPT (ZH_LP_MAXP = ZH_LP_PPT per task)");
 static_assert(ZH_LP_TASKS >= 1 && ZH_LP_TASKS <= 64, "the parsed-task mask of a group is 64 bits");
+static_assert(ZH_LP_TASKS < (1u << ZH_LANE_FIELD), "a bundle's word counts its tasks in fields of ZH_LANE_FIELD bits (zh_parse.h)");
 // The prefix scratch [row][column]: row L - 3, and piece i in column i ^ 8 for the rows of lanes 2 and 3 — the four lanes of a quad
 // write rows 9 q + k, whose LDS banks (16 per row) would coincide for lanes 0 / 2 and for lanes 1 / 3
 #define ZH_LP_PCOL(row_, piece_) ((piece_) ^ ((row_) >= 2u * ZH_LP_QSTRIDE ? 8u : 0u))
@@ -496,8 +498,8 @@ struct zh_seg_args_t {
    uint32_t seg_grid;       // workgroups of this launch that take segment entries (0: none — files mode)
 };
 
-// Behind them, single-wave workgroups take groups of tasks_per_wave consecutive tasks from *ticket until the run's task list — whose length only the device
-// knows (cnt[ZH_CNT_TASKS]) — is used up. The host gives a wave up to ZH_LP_TASKS tasks — a pool of pieces large enough to keep its sixteen quads
+// Behind them, single-wave workgroups take bundles of up to tasks_per_wave tasks from *ticket until the run's lists of bundles — whose lengths only the device
+// knows (cnt[ZH_CNT_LANE_CLASS ..]) — are used up (without lists: groups of tasks_per_wave consecutive tasks of the task list, cnt[ZH_CNT_TASKS]). The host gives a wave up to ZH_LP_TASKS tasks — a pool of pieces large enough to keep its sixteen quads
 // busy — but no more than it takes to give every wave slot of the chip a wave: a small batch (one 40 KB input: 20 tasks) is a matter of latency,
 // not of lane utilisation. Next to chains (zh_parse_chain, the segment workgroups: the run's counters say whether it has any) only the first
 // `bounded` workgroups stay: a grid that keeps every wave slot, register and LDS granule of the chip taken would make the four-wave workgroup that
@@ -510,7 +512,8 @@ zh_parse_lanes(const uint8_t *__restrict__ data, const zh_block_t *__restrict__ 
                const uint64_t *__restrict__ bars, uint64_t bar_stride, const zh_work_t *__restrict__ work, const uint2 *__restrict__ taskmap,
                uint32_t *cnt, const zh_sbstate_t *__restrict__ states, uint32_t *best_all, uint64_t best_stride, uint16_t *cost_all,
                uint32_t *hist_part, int pass, uint32_t *ticket, const uint2 *__restrict__ taskinfo, uint32_t tasks_per_wave /* 1 .. ZH_LP_TASKS */,
-               uint32_t bounded /* quad workgroups that stay when the run has chains */, zh_seg_args_t sg) {
+               uint32_t bounded /* quad workgroups that stay when the run has chains */, zh_seg_args_t sg,
+               const uint32_t *__restrict__ lanelists /* the run's bundles by class, list_cap entries per class (zh_list_huge); NULL: none were listed */, uint32_t list_cap) {
    __shared__ union {
       zh_lp_ws_t ws;
       zh_parse_ws_t seg_ws;
@@ -533,16 +536,35 @@ zh_parse_lanes(const uint8_t *__restrict__ data, const zh_block_t *__restrict__ 
    zh_lp_ws_t &ws = sh.ws;
    const uint32_t ntasks = cnt[ZH_CNT_TASKS];
    if (blockIdx.x - sg.seg_grid >= bounded && (cnt[ZH_CNT_VLONG] | cnt[ZH_CNT_LONG] | cnt[ZH_CNT_SHORT] | cnt[ZH_CNT_SEGTASKS]) != 0u) return;
+   // (ONE call of zh_lp_group for both ways of handing out: inlined twice, the kernel took 139 registers instead of 116 — three waves per SIMD instead of four,
+   // and less room next to them for the chain workgroups, whose kernel then lasted 40 % longer)
+   const bool by_lists = lanelists && ticket;
+   uint32_t ncls[ZH_LANE_CLASSES];
+#pragma unroll
+   for (uint32_t cl = 0; cl < ZH_LANE_CLASSES; cl++) ncls[cl] = by_lists ? cnt[ZH_CNT_LANE_CLASS + cl] : 0u;
    for (;;) {
       uint32_t w = blockIdx.x - sg.seg_grid;
       if (ticket) {
          if (zh_lane() == 0) w = atomicAdd(ticket, 1u);
          w = zh_readfirstlane(w);
       }
-      const uint32_t g0 = w * tasks_per_wave;
-      if (g0 >= ntasks) return;
-      const uint32_t g1 = min(ntasks, g0 + tasks_per_wave);
-      // the wave's tasks, sub-block by sub-block
+      uint32_t g0, g1;
+      if (by_lists) {
+         // ---- a bundle, longest class first (zh_parse.h): ticket w is entry w of the classes' lists laid end to end
+         uint32_t cl = 0;
+         while (cl < ZH_LANE_CLASSES && w >= ncls[cl]) w -= ncls[cl++];
+         if (cl == ZH_LANE_CLASSES) return;
+         g0 = lanelists[cl * list_cap + w];
+         const uint2 tm = taskmap[g0];
+         g1 = g0 + min(tasks_per_wave, work[tm.x].ntasks - tm.y);   // (tm.y is a multiple of tasks_per_wave: zh_list_huge)
+      }
+      else {
+         // ---- no lists (files mode, ZULTRA_HIP_LANE_BUNDLES=0): tasks_per_wave consecutive tasks of the task list
+         g0 = w * tasks_per_wave;
+         if (g0 >= ntasks) return;
+         g1 = min(ntasks, g0 + tasks_per_wave);
+      }
+      // the wave's tasks, sub-block by sub-block (a bundle is of one sub-block)
       for (uint32_t g = g0; g < g1;) {
          const uint32_t sb = taskmap[g].x;
          uint32_t ge = g + 1;

@@ -391,8 +391,9 @@ def check_large_file(lib):
 
 
 def check_damage(lib):
-    """Member k of 9 damaged in four ways: only the members path's verdicts, every other member's bytes right where they belong; one byte short of
-    room is stop 4 with nothing written."""
+    """Member k of 9 damaged in four ways, with a device and with a host destination (of the latter check_file holds every byte outside the
+    members' out_size bytes to the canary): only the members path's verdicts, every other member's bytes right where they belong; one byte short
+    of room is stop 4 with nothing written."""
     parts = [text(300 + 50 * k, 60 + k) for k in range(9)]
     ms = [bgzf(p, raw=stored(p)) if k == 4 else bgzf(p) for k, p in enumerate(parts)]
     k = 4
@@ -401,13 +402,14 @@ def check_damage(lib):
     for what, at, delta in (("payload", start + 18 + 5 + 100, 0x20), ("crc", start + len(ms[k]) - 8, 1), ("isize_up", start + len(ms[k]) - 4, 1), ("isize_down", start + len(ms[k]) - 4, -1)):
         buf = bytearray(b"".join(ms))
         buf[at] = (buf[at] + delta) & 255 if what.startswith("isize") else buf[at] ^ delta
-        rc, res, mem, back = check_file(lib, what, bytes(buf))
         items = walk(buf)[0]
-        assert rc == 1 and [r[0] for j, r in enumerate(mem) if j != k] == [0] * 8 and mem[k][0] in (13, 15, 16), (what, [r[0] for r in mem])
-        seen.add(mem[k][0])
-        for j, (it, p) in enumerate(zip(items, parts)):
-            if j != k:
-                assert back[it[2]: it[2] + len(p)].tobytes() == p, (what, j)
+        for dev in (True, False):
+            rc, res, mem, back = check_file(lib, what, bytes(buf), on_device=dev)
+            assert rc == 1 and [r[0] for j, r in enumerate(mem) if j != k] == [0] * 8 and mem[k][0] in (13, 15, 16), (what, dev, [r[0] for r in mem])
+            seen.add(mem[k][0])
+            for j, (it, p) in enumerate(zip(items, parts)):
+                if j != k:
+                    assert back[it[2]: it[2] + len(p)].tobytes() == p, (what, dev, j)
     assert seen == {13, 15, 16}, seen
     buf = b"".join(ms)
     for dev in (True, False):

@@ -271,7 +271,7 @@ def check_cuts(lib, big):
 
 def check_trailers(lib):
     """Every trailer byte flipped: gzip 15 for the CRC-32's bytes and 16 for ISIZE's, zlib 15; both wrong is 15. A payload byte of a stored block
-    flipped: it decodes, 15, and `check` is the checksum of what was written."""
+    flipped: it decodes, 15, and `check` is the checksum of what was written. Then check_host_gaps."""
     for framing, m, foot in ((GZIP, gzip_member(gzip_header(0)), 8), (ZLIB, zlib_member(BODY_TEXT), 4)):
         muts = []
         for i in range(foot):
@@ -295,6 +295,32 @@ def check_trailers(lib):
         wrote[333] ^= 0x40
         rc, res = run_members(lib, [bytes(x)], [len(data)], framing)
         assert res[0][0] == BAD_CHECK and res[0][6] == bytes(wrote) and res[0][5] == checksum(framing, bytes(wrote)), res[0][:6]
+    check_host_gaps(lib)
+
+
+def check_host_gaps(lib):
+    """A host destination whose ranges lie CANARY bytes apart (run_members), in both framings: an item without room, one whose stream breaks part-way
+    (its second block is of type 3: the first block's bytes are written), one with a byte too little room, the others filling their ranges
+    exactly. run_members holds every byte in front of, between and behind the items' out_size bytes to the canary; here the verdicts, what was
+    written of the damaged items, and the sound items' bytes."""
+    datas = [corpus.text_like(n, 90 + k).tobytes() for k, n in enumerate((300, 450, 0, 700, 380, 520))]
+    for framing in (GZIP, ZLIB):
+        members = [member_of(framing, d, 6) for d in datas]
+        c = zlib.compressobj(6, zlib.DEFLATED, WBITS[framing])
+        first = c.compress(datas[3][:333]) + c.flush(zlib.Z_FULL_FLUSH)   # (ends on a byte boundary: the next block's header is the next byte's low bits)
+        broken = bytearray(first + c.compress(datas[3][333:]) + c.flush())
+        assert zlib_verdict(bytes(broken), framing)[:2] == (True, datas[3])
+        broken[len(first)] |= 6
+        members[3] = bytes(broken)
+        caps = [len(d) for d in datas]
+        caps[1] = 0
+        caps[4] -= 1
+        rc, res = run_members(lib, members, caps, framing, on_device=False)
+        assert rc == 3 and [r[0] == OK for r in res] == [True, False, True, False, False, True], [r[:6] for r in res]
+        assert res[1][2] == 0 and res[3][2] == 333 and res[3][6] == datas[3][:333], [r[:6] for r in res]
+        assert res[4][2] <= caps[4] and res[4][6] == datas[4][:res[4][2]], res[4][:6]
+        for k in (0, 2, 5):
+            assert res[k][6] == datas[k] and res[k][2] == caps[k] and res[k][5] == checksum(framing, datas[k]), (framing, k, res[k][:6])
 
 
 EDGE_SIZES = [0, 1, 255, 256, 257, 65535, 65536, 65537, 3 * 65536 + 1]

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Prints registers / LDS / occupancy of every kernel in zh_device.hip as reported by the compiler (no GPU needed); exits 1 when a kernel
+"""Prints registers / LDS / occupancy of every kernel in zh_device.hip and zh_inflate.hip as reported by the compiler (no GPU needed); exits 1 when a kernel
 uses scratch memory (spilled registers, arrays indexed at run time, out-of-line calls): none of the product's kernels may."""
 import os
 import re
@@ -8,9 +8,11 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "zultra_amd", "csrc")
-cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-x", "hip", "-I", CSRC, "-c", os.path.join(CSRC, "zh_device.hip"),
-       "-o", "/tmp/zh_device_res.o", "-Rpass-analysis=kernel-resource-usage"]
-err = subprocess.run(cmd, capture_output=True, text=True).stderr
+err = ""
+for source in ("zh_device", "zh_inflate"):
+    cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-x", "hip", "-I", CSRC, "-c", os.path.join(CSRC, source + ".hip"),
+           "-o", "/tmp/%s_res.o" % source, "-Rpass-analysis=kernel-resource-usage"]
+    err += subprocess.run(cmd, capture_output=True, text=True).stderr
 cur = None
 rows = {}
 for line in err.splitlines():

@@ -1299,7 +1299,7 @@ extern "C" size_t zultra_memory_decompress_batch(const unsigned char *pIn, size_
 }
 
 // gzip(1) over a whole file: runs of hinted members through zultra_hip_inflate_file, a member without a hint through zultra_hip_inflate_members on its own
-extern "C" void *zh_device_upload(int device, const void *host, size_t n);   // (zh_device.hip: this file has no HIP of its own)
+extern "C" void *zh_device_upload(int device, const void *host, size_t n);   // (zh_inflate.hip: this file has no HIP of its own)
 extern "C" void zh_device_release(void *p);
 extern "C" size_t zultra_memory_decompress_members(const unsigned char *pIn, size_t nIn, unsigned char *pOut, size_t nMaxOut, size_t *pnMembers) {
    if (pnMembers) *pnMembers = 0;

@@ -1,0 +1,24 @@
+// zh_host.h — what the host code of more than one source file needs (zh_device.hip, zh_inflate.hip): nothing for a kernel in here.
+#pragma once
+#include <stdint.h>
+#include <stdlib.h>
+
+#ifdef ZH_EMU
+#include <mutex>
+// the lock-step emulator (tests/emu) runs one kernel at a time on one OS thread's fibers: host threads that drive contexts of their
+// own (libzultra.cpp: lanes of zultra_memory_compress) take turns here — one lock for the whole library, in however many files it is compiled. The product build has no such lock.
+inline std::recursive_mutex g_emu_mutex;
+#define ZH_EMU_SERIALIZE() std::lock_guard<std::recursive_mutex> emu_lock_(g_emu_mutex)
+#else
+#define ZH_EMU_SERIALIZE()
+#endif
+
+// (64-bit min / max by name: hipcc's host-side `min` picks the int overload for two 64-bit arguments — 0xFFFFFFFF became -1)
+static inline uint64_t zh_min64(uint64_t a, uint64_t b) { return a < b ? a : b; }
+static inline uint64_t zh_max64(uint64_t a, uint64_t b) { return a > b ? a : b; }
+
+// Environment switches: part of the shipped library's surface
+static inline int zh_env(const char *name, int dflt) {
+   const char *e = getenv(name);
+   return e ? atoi(e) : dflt;
+}

@@ -170,6 +170,20 @@ def test_memory_compress_over_two_device_lanes(emu, oracle, monkeypatch):
     assert got == want
 
 
+def test_memory_compress_lane_takes_a_second_job(emu, oracle, monkeypatch):
+    """ZULTRA_HIP_BATCH_BLOCKS=2 and no devices named: one lane, a job of two max-blocks and a job of one. The lane takes its second job
+    only when the first has been stitched and has left the context, and the second job is stitched at the bit phase the first one left — a
+    stored sub-block sits right behind the cut. Same bytes as the oracle's one stream (the knob does not change them)."""
+    d = corpus.text_like(2 * 32768 + 300, 9)
+    d[32768:32768 + 12000] = corpus.noise(12000, 4)
+    d[2 * 32768:] = corpus.noise(300, 5)
+    want = oracle.memory_compress(d, 2, 32768)
+    monkeypatch.setenv("ZULTRA_HIP_BATCH_BLOCKS", "2")
+    monkeypatch.delenv("ZULTRA_HIP_DEVICES", raising=False)
+    got = emu.memory_compress(d, 2, 32768)
+    assert got == want
+
+
 @pytest.mark.parametrize("name", ["tiny_100", "one_byte", "two_bytes", "json_4k", "json_4k_b"])
 def test_golden_streams(emu, name):
     c = G.stream_case(name)

@@ -1107,6 +1107,39 @@ def test_streaming_batches_that_end_at_their_edges(gpu, checker, monkeypatch, en
                 assert bytes(out) == want, (env, batch, n, flags, with_dict, chunk)
 
 
+@pytest.mark.parametrize("with_dict", [False, True], ids=["no_dict", "dict"])
+@pytest.mark.parametrize("flags", [0, 1, 2])
+@pytest.mark.parametrize("devices", [None, "0,0"], ids=["one_lane_three_jobs", "two_lanes_lane0_takes_jobs_0_and_2"])
+def test_memory_compress_lanes_that_take_a_second_job(gpu, checker, monkeypatch, devices, flags, with_dict):
+    """ZULTRA_HIP_BATCH_BLOCKS=2 bounds a job of zultra_memory_compress's lanes too: five max-blocks and a bit are three jobs, so a lane takes a
+    second job — after its previous one has been stitched and has left the context — and every job after the first starts at the bit phase the
+    jobs before it left. Noise lies across both job boundaries (max-blocks 2 and 4): a stored sub-block right behind every cut. The bytes are
+    the reference's one stream, and zlib inflates them to the input."""
+    bs = 32768
+    d = corpus.text_like_fast(5 * bs + 1234, 41)
+    for cut in (2 * bs, 4 * bs):
+        d[cut - 6000:cut + 6000] = corpus.noise(12000, cut)
+    dic = corpus.text_like_fast(5000, 42) if with_dict else None
+    monkeypatch.setenv("ZULTRA_HIP_CACHE", "0")   # (a context's capacity is fixed when it is created)
+    gpu.L.zultra_release_cached_contexts()
+    monkeypatch.setenv("ZULTRA_HIP_BATCH_BLOCKS", "2")
+    if devices is None:
+        monkeypatch.delenv("ZULTRA_HIP_DEVICES", raising=False)
+    else:
+        monkeypatch.setenv("ZULTRA_HIP_DEVICES", devices)
+    want = checker.memory_compress(d, flags, bs, dic)
+    got = gpu.memory_compress(d, flags, bs, dic)
+    assert got == want, (devices, flags, with_dict, None if got is None else len(got), len(want))
+    # (a gzip member carries no dictionary id: its deflate stream is inflated behind the dictionary, the trailer checked by hand)
+    bare = flags == 2 and with_dict
+    body = got[10:-8] if bare else got
+    wbits = -15 if flags == 0 or bare else 15 if flags == 1 else 31
+    dec = zlib.decompressobj(wbits, zdict=dic.tobytes()) if with_dict else zlib.decompressobj(wbits)
+    assert dec.decompress(body) == d.tobytes() and dec.eof
+    if bare:
+        assert got[-8:] == (zlib.crc32(d.tobytes()) & 0xFFFFFFFF).to_bytes(4, "little") + (len(d) & 0xFFFFFFFF).to_bytes(4, "little")
+
+
 def test_files_mode_at_declared_sizes_that_are_not_powers_of_two(gpu, checker):
     """Files contexts declared for 5000, 6143 and 777 bytes (the device rounds its slots up to 64): inputs that fill the declared size
     exactly, miss it by a byte and anything smaller, each its own raw stream equal to the checker's; one byte more is refused. A declared

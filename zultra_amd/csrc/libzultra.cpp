@@ -18,6 +18,7 @@
 
 #include "../../include/libzultra.h"
 #include "../../include/zultra_hip.h"
+#include "zh_host.h"
 
 // ================================================================================================================
 // Framing and checksums (reference src/frame.c)
@@ -395,16 +396,8 @@ extern "C" size_t zultra_hip_stitch_finish(zultra_hip_bitstate_t *state, uint8_t
 }
 
 // ================================================================================================================
-// Streaming API (reference src/libzultra.c:82-565)
+// Devices, cached contexts, verification
 // ================================================================================================================
-
-enum {
-   ST_HAS_DICTIONARY = 1,
-   ST_HEADER_EMITTED = 2,
-   ST_FINALIZED = 4,
-   ST_FOOTER_EMITTED = 8,
-   ST_STREAM_ENDED = 16,
-};
 
 static int g_device = -1;
 static std::mutex g_ctx_mutex;
@@ -415,11 +408,7 @@ struct CachedCtx {
 };
 static std::vector<CachedCtx> g_ctx_pool;   // contexts released by finished streams, reused by later ones
 
-static int zh_pick_device() {
-   if (g_device >= 0) return g_device;
-   const char *e = getenv("ZULTRA_HIP_DEVICE");
-   return e ? atoi(e) : 0;
-}
+static int zh_pick_device() { return g_device >= 0 ? g_device : zh_env("ZULTRA_HIP_DEVICE", 0); }
 
 extern "C" void zultra_set_device(int nDevice) { g_device = nDevice; }
 
@@ -459,10 +448,8 @@ static std::vector<int> zh_pick_devices() {
    return v;
 }
 
-__attribute__((visibility("hidden"))) uint32_t zh_clamp_block(uint32_t n);   // (zh_device.hip: the max-block size as the library takes it)
-
 // input bytes -> pinned staging, split over a few threads from 2 * piece bytes on. Shared with the device layer (zh_device.hip), not exported.
-__attribute__((visibility("hidden"))) void zh_threaded_copy(uint8_t *dst, const uint8_t *src, size_t n, size_t piece) {
+ZH_HIDDEN void zh_threaded_copy(uint8_t *dst, const uint8_t *src, size_t n, size_t piece) {
    if (n < 2 * piece) {
       memcpy(dst, src, n);
       return;
@@ -487,9 +474,7 @@ extern "C" void zultra_set_verify(int nEnable) { g_verify.store(nEnable ? 1 : 0)
 extern "C" unsigned long long zultra_verified_bytes(void) { return g_verified_bytes.load(); }
 static bool zh_verify_on() {
    const int v = g_verify.load();
-   if (v >= 0) return v != 0;
-   const char *e = getenv("ZULTRA_HIP_VERIFY");
-   return e && atoi(e) != 0;
+   return v >= 0 ? v != 0 : zh_env("ZULTRA_HIP_VERIFY", 0) != 0;
 }
 // The batch the context has just stitched, inflated on its device and compared with its input. false: a mismatch (one line on stderr) or an error.
 static bool zh_verify_stitched(zultra_hip_ctx_t *c) {
@@ -527,14 +512,12 @@ static zultra_hip_ctx_t *ctx_acquire_on(int dev, uint32_t bs, uint32_t want_bloc
    }
    return zultra_hip_create(dev, bs, want_blocks);
 }
-static zultra_hip_ctx_t *ctx_acquire(uint32_t bs, uint32_t want_blocks) { return ctx_acquire_on(zh_pick_device(), bs, want_blocks); }
 
 // A finished stream's context goes back under what the CONTEXT says it is (device, block size, capacity) — not under what the
 // stream asked for or what zultra_set_device says now.
 static void ctx_release(zultra_hip_ctx_t *c) {
    if (!c) return;
-   const char *e = getenv("ZULTRA_HIP_CACHE");
-   if (e && atoi(e) == 0) {
+   if (zh_env("ZULTRA_HIP_CACHE", 1) == 0) {
       zultra_hip_destroy(c);
       return;
    }
@@ -563,41 +546,137 @@ extern "C" int zultra_release_cached_contexts(void) {
    return n;
 }
 
+// The max-blocks a context on `device` gets when `want` are asked for (0: a stream, which does not know its input, stages 64 MiB): at most 8192, at
+// most ZULTRA_HIP_BATCH_BLOCKS where that is set (2 at the least; a negative value counts as not set), and no more than 24 GiB of device memory
+// (MI355X has 288 GB), sized from the layout the context will really allocate.
+static uint32_t ctx_blocks(int device, uint32_t bs, uint64_t want) {
+   const int knob = zh_env("ZULTRA_HIP_BATCH_BLOCKS", -1);
+   uint64_t n = want;
+   if (knob >= 0 || !want) {
+      const uint64_t k = zh_max64(knob >= 0 ? (uint64_t)knob : (64u << 20) / bs, 2);
+      n = want ? zh_min64(want, k) : k;
+   }
+   n = zh_min64(n, 8192);
+   while (n > 1 && (uint64_t)zultra_hip_context_bytes_on(device, bs, (uint32_t)n) > (24ull << 30)) n -= (n + 7) / 8;
+   return (uint32_t)n;
+}
+
+// ================================================================================================================
+// One batch of max-blocks (reference src/libzultra.c:250-253, 279, 287-303, 327-398, 414-436): what a batch of the stream API and a job of
+// zultra_memory_compress's lanes both do, stated once
+// ================================================================================================================
+
+// Descriptors of `count` max-blocks of `bs` bytes (the last one `last_n`) that lie one behind the other after `hist` bytes of history: the first
+// block's history is those bytes, every later block's the 32 KiB in front of it (blocks are >= 32 KiB unless last).
+static void batch_describe(zultra_hip_block_t *blocks, size_t hist, uint32_t bs, size_t count, uint32_t last_n) {
+   for (size_t b = 0; b < count; b++) {
+      const uint32_t prev = b == 0 ? (uint32_t)hist : (uint32_t)HISTORY_SIZE;
+      blocks[b].win_off = (uint64_t)hist + (uint64_t)b * bs - prev;
+      blocks[b].prev = prev;
+      blocks[b].n = b + 1 == count ? last_n : bs;
+   }
+}
+
+// A preset dictionary is the pre-filled history of a stream's first max-block (libzultra.c:250-253): its last 32 KiB, or all of it
+static const uint8_t *dict_history(const void *dict, int dict_size, size_t *hist) {
+   *hist = dict_size > HISTORY_SIZE ? (size_t)HISTORY_SIZE : (size_t)dict_size;
+   return (const uint8_t *)dict + ((size_t)dict_size - *hist);
+}
+
+// Checksum once per max-block over its bytes (libzultra.c:279): both kinds are computed on the device next to the compression and folded into the
+// running checksum here. `crc` has room for one value per max-block, `adler_parts` for two.
+static bool batch_fold_checksums(zultra_hip_ctx_t *c, unsigned flags, const zultra_hip_block_t *blocks, uint32_t count, uint32_t *crc, uint32_t *adler_parts,
+                                 zultra_frame_checksum_t *sum) {
+   if (flags & ZULTRA_FLAG_GZIP_FRAMING) {
+      if (zultra_hip_block_crc32(c, crc) != (int)count) return false;
+      for (uint32_t b = 0; b < count; b++) *sum = zultra_crc32_append(*sum, crc[b], blocks[b].n);
+   }
+   else if (flags & ZULTRA_FLAG_ZLIB_FRAMING) {
+      if (zultra_hip_block_adler32(c, adler_parts) != (int)count) return false;
+      for (uint32_t b = 0; b < count; b++) *sum = zultra_adler32_append(*sum, adler_parts[2 * b], adler_parts[2 * b + 1], blocks[b].n);
+   }
+   return true;
+}
+
+// Finish the context's batch on the device at the phase `bit` has reached: descriptors -> plan, the bits moved by a kernel (nothing is launched where the
+// stitch went out with the batch, zultra_hip_stitch_with_batch), verified there if asked, one D2H of the finished bytes into pinned memory — *dst of
+// dst_cap bytes, or, where *dst is NULL, the context's output staging grown to the batch, which *dst then names. The pending bits of the batches before
+// go into byte 0; *whole bytes are the caller's to hand out; a trailing partial byte stays pending in `bit` for the next batch, the final batch's is
+// already zero padded (libzultra.c:414-417). ZULTRA_ERROR_DST where the reference fails with it (the stitch's -2) and where dst_cap is too little.
+static zultra_status_t batch_finish(zultra_hip_ctx_t *c, zultra_hip_bitstate_t *bit, int final_block, uint8_t **dst, size_t dst_cap, size_t *whole) {
+   const uint32_t pending = bit->acc & ((1u << bit->nacc) - 1);
+   uint64_t end_bit = 0;
+   const int rc = zultra_hip_stitch_device(c, bit, final_block, &end_bit);
+   if (rc == -2) return ZULTRA_ERROR_DST;
+   if (rc != 0) return ZULTRA_ERROR_COMPRESSION;
+   if (zh_verify_on() && !zh_verify_stitched(c)) return ZULTRA_ERROR_COMPRESSION;
+   const size_t total = (size_t)((end_bit + 7) >> 3);
+   if (!*dst) {
+      if (!(*dst = (uint8_t *)zultra_hip_staging(c, 1, total + 16))) return ZULTRA_ERROR_COMPRESSION;
+   }
+   else if (total > dst_cap)
+      return ZULTRA_ERROR_DST;
+   if (zultra_hip_stream_read(c, *dst, 0, total) != 0) return ZULTRA_ERROR_COMPRESSION;
+   (*dst)[0] |= (uint8_t)pending;
+   if (final_block >= 0) {
+      *whole = total;
+      bit->acc = bit->nacc = 0;
+   }
+   else {
+      *whole = (size_t)(end_bit >> 3);
+      bit->acc = (end_bit & 7) ? (*dst)[*whole] : 0;
+   }
+   return ZULTRA_OK;
+}
+
+// ================================================================================================================
+// Streaming API (reference src/libzultra.c:82-565)
+// ================================================================================================================
+
+enum StreamState : unsigned {   // bits of _zultra_compressor_s::state
+   ST_HAS_DICTIONARY = 1,
+   ST_HEADER_EMITTED = 2,
+   ST_FINALIZED = 4,
+   ST_FOOTER_EMITTED = 8,
+   ST_STREAM_ENDED = 16,
+};
+
 struct _zultra_compressor_s {
-   unsigned flags;
-   uint32_t max_block;
-   uint32_t batch_blocks;       // max-blocks per device batch
-   uint64_t flush_bytes;        // staged full max-blocks of this many bytes are compressed when a call's input is used up (0: only when the staging area is full)
-   const void *dict;
-   int dict_size;
-   unsigned state;
+   unsigned flags = 0;
+   uint32_t max_block = 0;
+   uint32_t batch_blocks = 0;       // max-blocks per device batch
+   uint64_t flush_bytes = 0;        // staged full max-blocks of this many bytes are compressed when a call's input is used up (0: only when the staging area is full)
+   const void *dict = NULL;
+   int dict_size = 0;
+   unsigned state = 0;              // StreamState bits
 
-   zultra_hip_ctx_t *hip;
-   zultra_hip_bitstate_t bitstate;
+   zultra_hip_ctx_t *hip = NULL;
+   zultra_hip_bitstate_t bitstate = {};
 
-   uint8_t *in;                 // [32 KiB history][batch_blocks * max_block]
-   size_t in_bytes;             // input bytes staged after the history area
-   int prev;                    // valid history bytes (end-aligned in the history area)
+   uint8_t *in = NULL;              // [32 KiB history][batch_blocks * max_block]
+   size_t in_bytes = 0;             // input bytes staged after the history area
+   int prev = 0;                    // valid history bytes (end-aligned in the history area)
 
-   uint8_t *out;                // stitched bytes of the last batch
-   size_t out_cap, out_pos, out_pending;
+   uint8_t *out = NULL;             // stitched bytes of the last batch
+   size_t out_cap = 0, out_pos = 0, out_pending = 0;
 
    unsigned char frame[16];
-   size_t frame_pos, frame_pending;
+   size_t frame_pos = 0, frame_pending = 0;
 
    // per max-block of a batch, batch_blocks entries each, from the caller's allocator (libzultra.c:94-147: every buffer of a stream
    // comes from zalloc; what does not here is the device context — device memory and pinned staging — which belongs to the backend)
-   zultra_hip_block_t *blocks;
-   uint64_t *raw_off;
-   uint32_t *crc;
-   uint32_t *adler_parts;       // two per max-block
-   bool host_stitch;            // ZULTRA_HIP_HOST_STITCH=1: stitch on the host (A/B checking)
+   zultra_hip_block_t *blocks = NULL;
+   uint64_t *raw_off = NULL;
+   uint32_t *crc = NULL;
+   uint32_t *adler_parts = NULL;    // two per max-block
+   bool host_stitch = false;        // ZULTRA_HIP_HOST_STITCH=1: stitch on the host (A/B checking)
 };
 
 static void *default_zalloc(void *, unsigned int items, unsigned int size) { return malloc((size_t)items * size); }
 static void default_zfree(void *, void *p) { free(p); }
 
-static zultra_status_t stream_init_sized(zultra_stream_t *s, unsigned flags, unsigned bs_in, uint32_t batch_blocks) {
+// want_blocks: the max-blocks of the input where the whole of it is at hand, 0 for a stream (ctx_blocks)
+static zultra_status_t stream_init_sized(zultra_stream_t *s, unsigned flags, unsigned bs_in, uint64_t want_blocks) {
    const uint32_t bs = zh_clamp_block(bs_in);
    if (!s->zalloc) s->zalloc = default_zalloc;
    if (!s->zfree) s->zfree = default_zfree;
@@ -606,62 +685,27 @@ static zultra_status_t stream_init_sized(zultra_stream_t *s, unsigned flags, uns
 
    zultra_compressor_t *c = (zultra_compressor_t *)s->zalloc(s->opaque, 1, (unsigned)sizeof(zultra_compressor_t));
    if (!c) return ZULTRA_ERROR_MEMORY;
-   new (c) zultra_compressor_t();
+   new (c) zultra_compressor_t();   // (the object itself is the caller's memory like its arrays; the member initialisers above are its start state)
    s->state = c;
    c->flags = flags;
    c->max_block = bs;
-   c->dict = NULL;
-   c->dict_size = 0;
-   c->state = 0;
-   c->bitstate.acc = c->bitstate.nacc = 0;
-   c->in_bytes = 0;
-   c->prev = 0;
-   c->out_pos = c->out_pending = 0;
-   c->frame_pos = c->frame_pending = 0;
-   c->in = c->out = NULL;
-   c->hip = NULL;
-   c->blocks = NULL;
-   c->raw_off = NULL;
-   c->crc = c->adler_parts = NULL;
-   {
-      const char *e = getenv("ZULTRA_HIP_HOST_STITCH");
-      c->host_stitch = e && atoi(e) != 0;
-   }
+   c->host_stitch = zh_env("ZULTRA_HIP_HOST_STITCH", 0) != 0;
+   c->flush_bytes = zh_env64("ZULTRA_HIP_FLUSH_BYTES", 4ull << 20);
+   const uint32_t batch_blocks = c->batch_blocks = ctx_blocks(zh_pick_device(), bs, want_blocks);
 
-   if (!batch_blocks) {
-      const char *e = getenv("ZULTRA_HIP_BATCH_BLOCKS");
-      batch_blocks = e ? (uint32_t)atoi(e) : (uint32_t)((64u << 20) / bs);
-      if (batch_blocks < 2) batch_blocks = 2;
-   }
-   // device bytes per context (MI355X has 288 GB): sized from the layout the context will really allocate
-   const uint64_t budget = 24ull << 30;
-   while (batch_blocks > 1 && (uint64_t)zultra_hip_context_bytes_on(zh_pick_device(), bs, batch_blocks) > budget) batch_blocks = batch_blocks - (batch_blocks + 7) / 8;
-   c->batch_blocks = batch_blocks;
-   {
-      const char *e = getenv("ZULTRA_HIP_FLUSH_BYTES");
-      c->flush_bytes = e ? (uint64_t)strtoull(e, NULL, 10) : (4ull << 20);
-   }
    c->blocks = (zultra_hip_block_t *)s->zalloc(s->opaque, batch_blocks, (unsigned)sizeof(zultra_hip_block_t));
    c->raw_off = (uint64_t *)s->zalloc(s->opaque, batch_blocks, (unsigned)sizeof(uint64_t));
    c->crc = (uint32_t *)s->zalloc(s->opaque, batch_blocks, (unsigned)sizeof(uint32_t));
    c->adler_parts = (uint32_t *)s->zalloc(s->opaque, 2 * batch_blocks, (unsigned)sizeof(uint32_t));
-   if (!c->blocks || !c->raw_off || !c->crc || !c->adler_parts) {
-      zultra_stream_end(s);
-      return ZULTRA_ERROR_MEMORY;
+   if (c->blocks && c->raw_off && c->crc && c->adler_parts) c->hip = ctx_acquire_on(zh_pick_device(), bs, batch_blocks);
+   if (c->hip) {
+      // worst case per max-block: all sub-blocks stored (libzultra.c:576-587)
+      c->out_cap = (size_t)batch_blocks * ((size_t)bs + 6 * 64 + 16) + 16;
+      // staging lives in pinned memory owned by the (pooled) device context: it survives this stream and is reused by the next
+      c->in = (uint8_t *)zultra_hip_staging(c->hip, 0, (size_t)HISTORY_SIZE + (size_t)batch_blocks * bs);
+      c->out = (uint8_t *)zultra_hip_staging(c->hip, 1, c->out_cap);
    }
-
-   c->hip = ctx_acquire(bs, batch_blocks);
-   if (!c->hip) {
-      zultra_stream_end(s);
-      return ZULTRA_ERROR_MEMORY;   // no usable HIP device / device memory: there is no CPU path
-   }
-   const size_t in_size = (size_t)HISTORY_SIZE + (size_t)batch_blocks * bs;
-   // worst case per max-block: all sub-blocks stored (libzultra.c:576-587)
-   c->out_cap = (size_t)batch_blocks * ((size_t)bs + 6 * 64 + 16) + 16;
-   // staging lives in pinned memory owned by the (pooled) device context: it survives this stream and is reused by the next
-   c->in = (uint8_t *)zultra_hip_staging(c->hip, 0, in_size);
-   c->out = (uint8_t *)zultra_hip_staging(c->hip, 1, c->out_cap);
-   if (!c->in || !c->out) {
+   if (!c->in || !c->out) {   // an array, or no usable HIP device / device memory (there is no CPU path), or the staging
       zultra_stream_end(s);
       return ZULTRA_ERROR_MEMORY;
    }
@@ -698,79 +742,42 @@ extern "C" void zultra_stream_end(zultra_stream_t *s) {
    }
 }
 
-static void drain_frame(zultra_stream_t *s, zultra_compressor_t *c) {
-   if (c->frame_pending && s->avail_out) {
-      size_t k = s->avail_out < c->frame_pending ? s->avail_out : c->frame_pending;
-      memcpy(s->next_out, c->frame + c->frame_pos, k);
-      c->frame_pos += k;
-      c->frame_pending -= k;
-      s->next_out += k;
-      s->avail_out -= k;
-      s->total_out += k;
-   }
+// The output pump: pending bytes of `buf` (frame bytes, a batch's bytes) go to next_out as far as there is room
+static void pump_out(zultra_stream_t *s, const uint8_t *buf, size_t *pos, size_t *pending) {
+   const size_t k = s->avail_out < *pending ? s->avail_out : *pending;
+   if (!k) return;
+   memcpy(s->next_out, buf + *pos, k);
+   *pos += k;
+   *pending -= k;
+   s->next_out += k;
+   s->avail_out -= k;
+   s->total_out += k;
 }
 
 // Compress `count` max-blocks staged at c->in + HISTORY (the last one `last_n` bytes long).
 static zultra_status_t compress_staged(zultra_stream_t *s, zultra_compressor_t *c, uint32_t count, uint32_t last_n, bool final_last) {
    const uint32_t bs = c->max_block;
    if (count > c->batch_blocks) return ZULTRA_ERROR_COMPRESSION;
-   const uint64_t base = (uint64_t)HISTORY_SIZE - (uint64_t)c->prev;   // window of block 0 starts here
-   size_t consumed = 0;
-   for (uint32_t b = 0; b < count; b++) {
-      const uint32_t n = (b + 1 == count) ? last_n : bs;
-      const uint32_t prev = (b == 0) ? (uint32_t)c->prev : (uint32_t)HISTORY_SIZE;   // blocks are >= 32 KiB unless last
-      c->blocks[b].win_off = (uint64_t)HISTORY_SIZE + (uint64_t)b * bs - prev - base;
-      c->blocks[b].prev = prev;
-      c->blocks[b].n = n;
-      c->raw_off[b] = (uint64_t)b * bs;
-      consumed += n;
-   }
-   const size_t data_size = (size_t)c->prev + consumed;
+   const int final_block = final_last ? (int)count - 1 : -1;
+   const size_t consumed = (size_t)(count - 1) * bs + last_n;
+   batch_describe(c->blocks, (size_t)c->prev, bs, count, last_n);
    // the phase this batch starts at is what the batches before it left (libzultra.c:327-398): its stitch goes out with its kernels
-   if (!c->host_stitch) (void)zultra_hip_stitch_with_batch(c->hip, 1, c->bitstate.nacc, final_last ? (int)count - 1 : -1);
-   int nsubs = zultra_hip_compress_blocks(c->hip, c->in + base, data_size, 0, c->blocks, count);
-   if (nsubs <= 0) return ZULTRA_ERROR_COMPRESSION;
-
-   // checksum once per max-block over its bytes (libzultra.c:279): both kinds come from the device, folded here
-   if (c->flags & ZULTRA_FLAG_GZIP_FRAMING) {
-      if (zultra_hip_block_crc32(c->hip, c->crc) != (int)count) return ZULTRA_ERROR_COMPRESSION;
-      for (uint32_t b = 0; b < count; b++) s->adler = zultra_crc32_append(s->adler, c->crc[b], c->blocks[b].n);
-   }
-   else if (c->flags & ZULTRA_FLAG_ZLIB_FRAMING) {
-      if (zultra_hip_block_adler32(c->hip, c->adler_parts) != (int)count) return ZULTRA_ERROR_COMPRESSION;
-      for (uint32_t b = 0; b < count; b++) s->adler = zultra_adler32_append(s->adler, c->adler_parts[2 * b], c->adler_parts[2 * b + 1], c->blocks[b].n);
-   }
+   if (!c->host_stitch) (void)zultra_hip_stitch_with_batch(c->hip, 1, c->bitstate.nacc, final_block);
+   if (zultra_hip_compress_blocks(c->hip, c->in + HISTORY_SIZE - c->prev, (size_t)c->prev + consumed, 0, c->blocks, count) <= 0) return ZULTRA_ERROR_COMPRESSION;
+   if (!batch_fold_checksums(c->hip, c->flags, c->blocks, count, c->crc, c->adler_parts, &s->adler)) return ZULTRA_ERROR_COMPRESSION;
 
    size_t w = 0;
    if (!c->host_stitch) {
-      // device stitch: descriptors -> plan on the host, bits moved by a kernel, one D2H of the finished bytes
-      uint64_t end_bit = 0;
-      const uint32_t phase = c->bitstate.nacc;
-      const uint32_t pending = c->bitstate.acc & ((1u << phase) - 1);
-      int rc = zultra_hip_stitch_device(c->hip, &c->bitstate, final_last ? (int)count - 1 : -1, &end_bit);
-      if (rc == -2) return ZULTRA_ERROR_DST;
-      if (rc != 0) return ZULTRA_ERROR_COMPRESSION;
-      if (zh_verify_on() && !zh_verify_stitched(c->hip)) return ZULTRA_ERROR_COMPRESSION;
-      const size_t total = (size_t)((end_bit + 7) >> 3);
-      if (total > c->out_cap) return ZULTRA_ERROR_DST;
-      if (zultra_hip_stream_read(c->hip, c->out, 0, total) != 0) return ZULTRA_ERROR_COMPRESSION;
-      c->out[0] |= (uint8_t)pending;
-      if (final_last) {
-         w = total;   // the last partial byte is already zero padded (libzultra.c:414-417)
-         c->bitstate.acc = c->bitstate.nacc = 0;
-         c->state |= ST_FINALIZED;
-      }
-      else {
-         w = (size_t)(end_bit >> 3);
-         c->bitstate.acc = (end_bit & 7) ? c->out[w] : 0;
-      }
+      uint8_t *out = c->out;
+      const zultra_status_t st = batch_finish(c->hip, &c->bitstate, final_block, &out, c->out_cap, &w);
+      if (st != ZULTRA_OK) return st;
    }
    else {
       if (zh_verify_on()) {
          // the host stitcher's bytes never reach the device: the same batch is stitched there too, from the same phase, and that stream is checked
          zultra_hip_bitstate_t dev_state = c->bitstate;
          uint64_t end_bit = 0;
-         const int rc = zultra_hip_stitch_device(c->hip, &dev_state, final_last ? (int)count - 1 : -1, &end_bit);
+         const int rc = zultra_hip_stitch_device(c->hip, &dev_state, final_block, &end_bit);
          if (rc == -2) return ZULTRA_ERROR_DST;
          if (rc != 0 || !zh_verify_stitched(c->hip)) return ZULTRA_ERROR_COMPRESSION;
       }
@@ -778,16 +785,16 @@ static zultra_status_t compress_staged(zultra_stream_t *s, zultra_compressor_t *
       const zultra_hip_subblock_t *subs = zultra_hip_subblocks(c->hip, &cnt);
       size_t psize = 0;
       const uint8_t *payload = zultra_hip_payload(c->hip, &psize);
-      w = zultra_hip_stitch(&c->bitstate, subs, cnt, payload, c->in + HISTORY_SIZE, c->raw_off, bs,
-                            final_last ? (int)count - 1 : -1, c->out, c->out_cap);
+      for (uint32_t b = 0; b < count; b++) c->raw_off[b] = (uint64_t)b * bs;
+      w = zultra_hip_stitch(&c->bitstate, subs, cnt, payload, c->in + HISTORY_SIZE, c->raw_off, bs, final_block, c->out, c->out_cap);
       if (w == (size_t)-1) return ZULTRA_ERROR_DST;
       if (final_last) {
          size_t f = zultra_hip_stitch_finish(&c->bitstate, c->out + w, c->out_cap - w);
          if (f == (size_t)-1) return ZULTRA_ERROR_DST;
          w += f;
-         c->state |= ST_FINALIZED;
       }
    }
+   if (final_last) c->state |= ST_FINALIZED;
    c->out_pos = 0;
    c->out_pending = w;
 
@@ -831,13 +838,13 @@ extern "C" zultra_status_t zultra_stream_compress(zultra_stream_t *s, const int 
          }
          s->adler = zultra_frame_init_checksum(c->flags);
       }
-      if (!err) drain_frame(s, c);
+      if (!err) pump_out(s, c->frame, &c->frame_pos, &c->frame_pending);
 
       if (!err && !c->prev && c->dict_size && c->dict && c->in_bytes == 0) {
-         // preset dictionary = pre-filled history of the first max-block (libzultra.c:250-253)
-         int d = c->dict_size > HISTORY_SIZE ? HISTORY_SIZE : c->dict_size;
-         memcpy(c->in + HISTORY_SIZE - d, (const uint8_t *)c->dict + (c->dict_size - d), (size_t)d);
-         c->prev = d;
+         size_t d = 0;
+         const uint8_t *tail = dict_history(c->dict, c->dict_size, &d);
+         memcpy(c->in + HISTORY_SIZE - d, tail, d);
+         c->prev = (int)d;
       }
 
       if (!err && !c->frame_pending && !c->out_pending) {
@@ -875,15 +882,7 @@ extern "C" zultra_status_t zultra_stream_compress(zultra_stream_t *s, const int 
          if (count) err = compress_staged(s, c, count, last_n, final_last && count > 0);
       }
 
-      if (!err && !c->frame_pending && c->out_pending && s->avail_out) {
-         size_t k = s->avail_out < c->out_pending ? s->avail_out : c->out_pending;
-         memcpy(s->next_out, c->out + c->out_pos, k);
-         c->out_pos += k;
-         c->out_pending -= k;
-         s->next_out += k;
-         s->avail_out -= k;
-         s->total_out += k;
-      }
+      if (!err && !c->frame_pending) pump_out(s, c->out, &c->out_pos, &c->out_pending);
 
       if (!err && !c->frame_pending && !c->out_pending && (c->state & ST_FINALIZED) && !(c->state & ST_FOOTER_EMITTED)) {
          int f = zultra_frame_encode_footer(c->frame, 16, s->adler, (long long)s->total_in, c->flags);
@@ -895,7 +894,7 @@ extern "C" zultra_status_t zultra_stream_compress(zultra_stream_t *s, const int 
             c->frame_pending = (size_t)f;
          }
       }
-      if (!err) drain_frame(s, c);
+      if (!err) pump_out(s, c->frame, &c->frame_pos, &c->frame_pending);
    } while (!err && s->avail_in && s->avail_out);
 
    if (err) return err;
@@ -925,235 +924,142 @@ extern "C" size_t zultra_memory_bound(size_t nInputSize, const unsigned int nFla
 // thread job by job in stream order, on the job's own device, as soon as the job's batch is done; the stitched bytes go to pOut
 // while the lanes are at their next jobs. Same bytes as the one-stream path: both cut max-blocks at multiples of the block size.
 namespace {
+enum class JobState { Waiting, BatchDone, Stitched };   // Stitched: and read out — the lane's context is free for the lane's next job
 struct MemJob {
-   size_t block0, nblocks;   // max-blocks [block0, block0 + nblocks) of the input
-   int state;                // 0 waiting, 1 batch done, -1 failed, 2 stitched (the lane's context is free again)
+   size_t first, bytes;                       // the job's input: `bytes` from offset `first`
+   const uint8_t *hist_src;                   // history of its first max-block: the `hist` bytes of input in front of it, or the preset dictionary's
+   size_t hist;
+   std::vector<zultra_hip_block_t> blocks;   // its max-blocks: the lane compresses them, the stitching thread folds their checksums
+   JobState state = JobState::Waiting;
 };
 struct MemLanes {
-   const unsigned char *in;
-   size_t n_in;
-   uint32_t bs;
-   size_t total_blocks;
-   const void *dict;
-   int dict_size;
+   const uint8_t *in = NULL;
+   uint32_t bs = 0;
    std::vector<MemJob> jobs;
-   std::vector<zultra_hip_ctx_t *> ctx;
+   std::vector<zultra_hip_ctx_t *> ctx;   // one per lane
+   std::vector<std::thread> threads;
    std::mutex m;
    std::condition_variable cv;
-   bool abort;
+   bool failed = false;
+
+   void fail() {
+      {
+         std::lock_guard<std::mutex> lk(m);
+         failed = true;
+      }
+      cv.notify_all();
+   }
+   void set(MemJob &J, JobState s) {
+      {
+         std::lock_guard<std::mutex> lk(m);
+         J.state = s;
+      }
+      cv.notify_all();
+   }
+   // until J is in state s (J == NULL: nothing to wait for); false: the call has failed meanwhile
+   bool wait(const MemJob *J, JobState s) {
+      std::unique_lock<std::mutex> lk(m);
+      cv.wait(lk, [&] { return failed || !J || J->state == s; });
+      return !failed;
+   }
+   void lane(size_t l);
+   // the one exit: whoever still waits gives up, every thread is joined, every context goes back
+   ~MemLanes() {
+      fail();
+      for (auto &t : threads) t.join();
+      for (auto *c : ctx) ctx_release(c);
+   }
 };
 
-static void mem_lane_body(MemLanes *M, size_t lane);
-static void mem_lane_thread(MemLanes *M, size_t lane) {
-   try {
-      mem_lane_body(M, lane);
-   } catch (...) {   // (std::bad_alloc from the block list: the batch fails, the process does not)
-      {
-         std::lock_guard<std::mutex> lk(M->m);
-         for (size_t j = lane; j < M->jobs.size(); j += M->ctx.size())
-            if (M->jobs[j].state == 0) M->jobs[j].state = -1;
-         M->abort = true;
-      }
-      M->cv.notify_all();
-   }
-}
-static void mem_lane_body(MemLanes *M, size_t lane) {
-   zultra_hip_ctx_t *c = M->ctx[lane];
-   std::vector<zultra_hip_block_t> blocks;
-   for (size_t j = lane; j < M->jobs.size(); j += M->ctx.size()) {
-      MemJob &J = M->jobs[j];
-      if (j >= M->ctx.size()) {   // the lane's previous job must have left the context (stitched and read out)
-         std::unique_lock<std::mutex> lk(M->m);
-         M->cv.wait(lk, [&] { return M->abort || M->jobs[j - M->ctx.size()].state == 2; });
-      }
-      {
-         std::lock_guard<std::mutex> lk(M->m);
-         if (M->abort) return;
-      }
-      const size_t first = J.block0 * M->bs, last = first + J.nblocks * M->bs < M->n_in ? first + J.nblocks * M->bs : M->n_in;
-      // history of the job's first max-block: the 32 KiB of input in front of it, or the preset dictionary (libzultra.c:250-253)
-      size_t hist = first < (size_t)HISTORY_SIZE ? first : (size_t)HISTORY_SIZE;
-      const uint8_t *hsrc = M->in + first - hist;
-      if (J.block0 == 0 && M->dict && M->dict_size > 0) {
-         hist = M->dict_size > HISTORY_SIZE ? (size_t)HISTORY_SIZE : (size_t)M->dict_size;
-         hsrc = (const uint8_t *)M->dict + (M->dict_size - (int)hist);
-      }
+void MemLanes::lane(size_t l) try {
+   zultra_hip_ctx_t *c = ctx[l];
+   for (size_t j = l; j < jobs.size(); j += ctx.size()) {
+      MemJob &J = jobs[j];
+      // the lane's previous job must have left the context (stitched and read out)
+      if (!wait(j >= ctx.size() ? &jobs[j - ctx.size()] : NULL, JobState::Stitched)) return;
       // The job's windows are contiguous in the caller's buffer — unless its history is the preset dictionary — and are handed over
       // as they are: the device layer stages and uploads them run by run (zultra_hip_compress_blocks, data_on_device == 2).
-      const bool in_place = hsrc + hist == M->in + first;
-      uint8_t *stage = in_place ? (uint8_t *)(M->in + first - hist) : (uint8_t *)zultra_hip_staging(c, 0, (size_t)HISTORY_SIZE + J.nblocks * M->bs);
-      int ok = stage != NULL;
-      if (ok) {
-         if (!in_place) {
-            memcpy(stage, hsrc, hist);
-            zh_threaded_copy(stage + hist, M->in + first, last - first, 16u << 20);   // (what a lane's first job waits for)
-         }
-         blocks.resize(J.nblocks);
-         for (size_t b = 0; b < J.nblocks; b++) {
-            const uint32_t prev = b == 0 ? (uint32_t)hist : (uint32_t)HISTORY_SIZE;
-            const size_t at = first + b * M->bs;
-            blocks[b].win_off = hist + b * M->bs - prev;
-            blocks[b].prev = prev;
-            blocks[b].n = (uint32_t)(at + M->bs <= M->n_in ? M->bs : M->n_in - at);
-         }
-         // the stream's first job starts at phase 0: its stitch goes out with its kernels (the later jobs' phases are known when the jobs before them are stitched)
-         if (j == 0) (void)zultra_hip_stitch_with_batch(c, 1, 0, M->jobs.size() == 1 ? (int)J.nblocks - 1 : -1);
-         ok = zultra_hip_compress_blocks(c, stage, hist + (last - first), in_place ? 2 : 0, blocks.data(), (uint32_t)J.nblocks) > 0;
+      const bool in_place = J.hist_src + J.hist == in + J.first;
+      uint8_t *stage = in_place ? (uint8_t *)J.hist_src : (uint8_t *)zultra_hip_staging(c, 0, (size_t)HISTORY_SIZE + J.blocks.size() * bs);
+      if (stage && !in_place) {
+         memcpy(stage, J.hist_src, J.hist);
+         zh_threaded_copy(stage + J.hist, in + J.first, J.bytes, 16u << 20);   // (what a lane's first job waits for)
       }
-      {
-         std::lock_guard<std::mutex> lk(M->m);
-         J.state = ok ? 1 : -1;
-         if (!ok) M->abort = true;
+      // the stream's first job starts at phase 0: its stitch goes out with its kernels (the later jobs' phases are known when the jobs before them are stitched)
+      if (stage && j == 0) (void)zultra_hip_stitch_with_batch(c, 1, 0, jobs.size() == 1 ? (int)J.blocks.size() - 1 : -1);
+      if (!stage || zultra_hip_compress_blocks(c, stage, J.hist + J.bytes, in_place ? 2 : 0, J.blocks.data(), (uint32_t)J.blocks.size()) <= 0) {
+         fail();
+         return;
       }
-      M->cv.notify_all();
-      if (!ok) return;
+      set(J, JobState::BatchDone);
    }
+} catch (...) {   // (std::system_error from a lock: the call fails, the process does not)
+   fail();
 }
 }   // namespace
 
+// Nothing thrown in here crosses the C ABI (std::bad_alloc from the vectors, std::system_error from a thread that cannot start): the call fails, and
+// ~MemLanes has joined what was started and released the contexts before the handler runs.
 static size_t memory_compress_lanes(const unsigned char *pIn, size_t nIn, unsigned char *pOut, size_t nOutCap, const unsigned int nFlags, uint32_t bs,
-                                    const void *pDict, int nDictSize, const std::vector<int> &devices) {
+                                    const void *pDict, int nDictSize, const std::vector<int> &devices) try {
+   // jobs: as few as there are lanes when the input fits that way, else batches of the size a one-stream call would use
+   const size_t total_blocks = (nIn + bs - 1) / bs;
+   size_t per = (total_blocks + devices.size() - 1) / devices.size();
+   for (int dv : devices) per = ctx_blocks(dv, bs, per);   // (the listed devices need not be alike: a job must fit the smallest budget)
    MemLanes M;
    M.in = pIn;
-   M.n_in = nIn;
    M.bs = bs;
-   M.total_blocks = (nIn + bs - 1) / bs;
-   M.dict = pDict;
-   M.dict_size = nDictSize;
-   M.abort = false;
-   // jobs: as few as there are lanes when the input fits that way, else batches of the size a one-stream call would use
-   size_t per = (M.total_blocks + devices.size() - 1) / devices.size();
-   const uint64_t budget = 24ull << 30;
-   if (per > 8192) per = 8192;
-   for (int dv : devices)   // (the listed devices need not be alike: a job must fit the smallest budget)
-      while (per > 1 && (uint64_t)zultra_hip_context_bytes_on(dv, bs, (uint32_t)per) > budget) per -= (per + 7) / 8;
-   std::vector<std::thread> threads;
-   size_t lanes = 0;
-   try {
-      for (size_t b = 0; b < M.total_blocks; b += per) M.jobs.push_back(MemJob{b, M.total_blocks - b < per ? M.total_blocks - b : per, 0});
-      const size_t want = M.jobs.size() < devices.size() ? M.jobs.size() : devices.size();
-      // a lane whose context cannot be had (a second large context on a device listed twice, a busy or smaller device) is left out: the
-      // jobs go round the lanes that exist; none at all is the only failure
-      for (size_t l = 0; l < want; l++) {
-         zultra_hip_ctx_t *c = ctx_acquire_on(devices[l], bs, (uint32_t)per);
-         if (c) M.ctx.push_back(c);
-      }
-      lanes = M.ctx.size();
-      if (!lanes) return (size_t)-1;
-      // (one lane with one job — a call on a few max-blocks, where 50 us of thread start-up and wake-ups count — runs on the calling thread)
-      if (lanes == 1 && M.jobs.size() == 1)
-         mem_lane_thread(&M, 0);
-      else {
-         threads.reserve(lanes);
-         for (size_t l = 0; l < lanes; l++) threads.emplace_back(mem_lane_thread, &M, l);
-      }
-   } catch (...) {   // std::bad_alloc / std::system_error must not cross the C ABI
-      {
-         std::lock_guard<std::mutex> lk(M.m);
-         M.abort = true;
-      }
-      M.cv.notify_all();
-      for (auto &t : threads) t.join();
-      for (auto *k : M.ctx) ctx_release(k);
-      return (size_t)-1;
+   for (size_t b = 0; b < total_blocks; b += per) {
+      const size_t nb = total_blocks - b < per ? total_blocks - b : per, first = b * bs, bytes = nb * bs < nIn - first ? nb * bs : nIn - first;
+      size_t hist = first < (size_t)HISTORY_SIZE ? first : (size_t)HISTORY_SIZE;
+      const uint8_t *hist_src = pIn + first - hist;
+      if (b == 0 && pDict && nDictSize > 0) hist_src = dict_history(pDict, nDictSize, &hist);
+      M.jobs.push_back(MemJob{first, bytes, hist_src, hist, std::vector<zultra_hip_block_t>(nb)});
+      batch_describe(M.jobs.back().blocks.data(), hist, bs, nb, (uint32_t)(bytes - (nb - 1) * bs));
+   }
+   // a lane whose context cannot be had (a second large context on a device listed twice, a busy or smaller device) is left out: the
+   // jobs go round the lanes that exist; none at all is the only failure
+   for (size_t l = 0; l < devices.size() && l < M.jobs.size(); l++) {
+      zultra_hip_ctx_t *c = ctx_acquire_on(devices[l], bs, (uint32_t)per);
+      if (c) M.ctx.push_back(c);
+   }
+   const size_t lanes = M.ctx.size();
+   if (!lanes) return (size_t)-1;
+   // (one lane with one job — a call on a few max-blocks, where 50 us of thread start-up and wake-ups count — runs on the calling thread)
+   if (lanes == 1 && M.jobs.size() == 1)
+      M.lane(0);
+   else {
+      M.threads.reserve(lanes);
+      for (size_t l = 0; l < lanes; l++) M.threads.emplace_back(&MemLanes::lane, &M, l);
    }
 
-   size_t w = 0;
-   bool fail = false;
-   {
-      unsigned char hdr[16];
-      const int h = zultra_frame_encode_header(hdr, 16, nFlags, pDict, nDictSize);
-      if (h < 0 || (size_t)h > nOutCap)
-         fail = true;
-      else {
-         memcpy(pOut, hdr, (size_t)h);
-         w = (size_t)h;
-      }
-   }
+   unsigned char frame[16];
+   const int h = zultra_frame_encode_header(frame, 16, nFlags, pDict, nDictSize);
+   if (h < 0 || (size_t)h > nOutCap) return (size_t)-1;
+   memcpy(pOut, frame, (size_t)h);
+   size_t w = (size_t)h;
    zultra_frame_checksum_t sum = zultra_frame_init_checksum(nFlags);
-   zultra_hip_bitstate_t bit;
-   bit.acc = bit.nacc = 0;
-   std::vector<uint32_t> parts;
-   try {
-      parts.reserve(2 * per);
-   } catch (...) {
-      fail = true;
-   }
-   for (size_t j = 0; j < M.jobs.size() && !fail; j++) {
+   zultra_hip_bitstate_t bit = {};
+   std::vector<uint32_t> parts(2 * per);
+   for (size_t j = 0; j < M.jobs.size(); j++) {
       MemJob &J = M.jobs[j];
-      {
-         std::unique_lock<std::mutex> lk(M.m);
-         M.cv.wait(lk, [&] { return J.state != 0 || M.abort; });
-         if (J.state != 1) fail = true;
-      }
       zultra_hip_ctx_t *c = M.ctx[j % lanes];
-      if (!fail) {
-         // checksum once per max-block over its bytes (libzultra.c:279): computed on the device next to the compression, folded here
-         const size_t first = J.block0 * bs;
-         if (nFlags & ZULTRA_FLAG_GZIP_FRAMING) {
-            parts.resize(J.nblocks);
-            fail = zultra_hip_block_crc32(c, parts.data()) != (int)J.nblocks;
-            for (size_t b = 0; b < J.nblocks && !fail; b++) {
-               const size_t at = first + b * bs;
-               sum = zultra_crc32_append(sum, parts[b], at + bs <= nIn ? bs : nIn - at);
-            }
-         }
-         else if (nFlags & ZULTRA_FLAG_ZLIB_FRAMING) {
-            parts.resize(2 * J.nblocks);
-            fail = zultra_hip_block_adler32(c, parts.data()) != (int)J.nblocks;
-            for (size_t b = 0; b < J.nblocks && !fail; b++) {
-               const size_t at = first + b * bs;
-               sum = zultra_adler32_append(sum, parts[2 * b], parts[2 * b + 1], at + bs <= nIn ? bs : nIn - at);
-            }
-         }
-      }
-      if (!fail) {
-         const bool last = j + 1 == M.jobs.size();
-         uint64_t end_bit = 0;
-         const uint32_t phase = bit.nacc;
-         const uint32_t pending = bit.acc & ((1u << phase) - 1);
-         const int rc = zultra_hip_stitch_device(c, &bit, last ? (int)J.nblocks - 1 : -1, &end_bit);
-         const size_t total = (size_t)((end_bit + 7) >> 3);
-         uint8_t *stage = rc == 0 ? (uint8_t *)zultra_hip_staging(c, 1, total + 16) : NULL;
-         if (rc != 0 || !stage || (zh_verify_on() && !zh_verify_stitched(c)) || zultra_hip_stream_read(c, stage, 0, total) != 0)
-            fail = true;
-         else {
-            stage[0] |= (uint8_t)pending;
-            // whole bytes go out; a trailing partial byte stays pending for the next job (the last job's is zero padded, libzultra.c:414-417)
-            const size_t whole = last ? total : (size_t)(end_bit >> 3);
-            if (w + whole > nOutCap)
-               fail = true;
-            else {
-               memcpy(pOut + w, stage, whole);
-               w += whole;
-               bit.acc = (!last && (end_bit & 7)) ? stage[whole] : 0;
-               if (last) bit.nacc = 0;
-            }
-         }
-      }
-      {
-         std::lock_guard<std::mutex> lk(M.m);
-         J.state = 2;
-         if (fail) M.abort = true;
-      }
-      M.cv.notify_all();
-      if (fail) break;
+      const uint32_t nb = (uint32_t)J.blocks.size();
+      uint8_t *bytes = NULL;   // (the context's output staging)
+      size_t whole = 0;
+      if (!M.wait(&J, JobState::BatchDone) || !batch_fold_checksums(c, nFlags, J.blocks.data(), nb, parts.data(), parts.data(), &sum) ||
+          batch_finish(c, &bit, j + 1 == M.jobs.size() ? (int)nb - 1 : -1, &bytes, 0, &whole) != ZULTRA_OK || w + whole > nOutCap)
+         return (size_t)-1;
+      memcpy(pOut + w, bytes, whole);
+      w += whole;
+      M.set(J, JobState::Stitched);
    }
-   if (fail) {
-      {
-         std::lock_guard<std::mutex> lk(M.m);
-         M.abort = true;
-      }
-      M.cv.notify_all();
-   }
-   for (auto &t : threads) t.join();
-   for (auto *k : M.ctx) ctx_release(k);
-   if (fail) return (size_t)-1;
-   unsigned char ftr[16];
-   const int f = zultra_frame_encode_footer(ftr, 16, sum, (long long)nIn, nFlags);
+   const int f = zultra_frame_encode_footer(frame, 16, sum, (long long)nIn, nFlags);
    if (f < 0 || w + (size_t)f > nOutCap) return (size_t)-1;
-   memcpy(pOut + w, ftr, (size_t)f);
+   memcpy(pOut + w, frame, (size_t)f);
    return w + (size_t)f;
+} catch (...) {
+   return (size_t)-1;
 }
 
 extern "C" size_t zultra_memory_compress_dict(const unsigned char *pIn, size_t nIn, unsigned char *pOut, size_t nOutCap,
@@ -1161,23 +1067,21 @@ extern "C" size_t zultra_memory_compress_dict(const unsigned char *pIn, size_t n
    zultra_stream_t strm;
    memset(&strm, 0, sizeof(strm));
    const uint32_t bs = zh_clamp_block(nMaxBlockSize);
+   const size_t nblocks = (nIn + bs - 1) / bs;
    // The whole input is at hand: shards of max-blocks over the devices asked for (ZULTRA_HIP_DEVICES / zultra_set_devices; "0,0" = two
    // contexts on device 0), at least two max-blocks per lane — or one lane on the one device, its batch staged and uploaded run by run.
    // (ZULTRA_HIP_MEMORY_LANES=0: through the stream API instead, as the reference does, libzultra.c:601-619.)
-   {
+   try {
       std::vector<int> devs = zh_pick_devices();
-      const char *e = getenv("ZULTRA_HIP_MEMORY_LANES");
-      const int lanes = e ? atoi(e) : 1;
       if (devs.empty())
-         for (int l = 0; l < lanes; l++) devs.push_back(zh_pick_device());
-      while (devs.size() > 1 && (nIn + bs - 1) / bs < 2 * devs.size()) devs.pop_back();
+         for (int l = zh_env("ZULTRA_HIP_MEMORY_LANES", 1); l > 0; l--) devs.push_back(zh_pick_device());
+      while (devs.size() > 1 && nblocks < 2 * devs.size()) devs.pop_back();
       if (!devs.empty() && pIn && nIn) return memory_compress_lanes(pIn, nIn, pOut, nOutCap, nFlags, bs, pDict, nDictSize, devs);
+   } catch (...) {   // (std::bad_alloc from the device list)
+      return (size_t)-1;
    }
    // the whole input is at hand: size the device batch to it
-   uint64_t want = (nIn + bs - 1) / bs;
-   if (want < 1) want = 1;
-   if (want > 8192) want = 8192;
-   if (stream_init_sized(&strm, nFlags, nMaxBlockSize, (uint32_t)want) != ZULTRA_OK) return (size_t)-1;
+   if (stream_init_sized(&strm, nFlags, nMaxBlockSize, nblocks ? nblocks : 1) != ZULTRA_OK) return (size_t)-1;
    if (pDict && nDictSize > 0 && zultra_stream_set_dictionary(&strm, pDict, nDictSize) != ZULTRA_OK) {
       zultra_stream_end(&strm);
       return (size_t)-1;
@@ -1299,8 +1203,6 @@ extern "C" size_t zultra_memory_decompress_batch(const unsigned char *pIn, size_
 }
 
 // gzip(1) over a whole file: runs of hinted members through zultra_hip_inflate_file, a member without a hint through zultra_hip_inflate_members on its own
-extern "C" void *zh_device_upload(int device, const void *host, size_t n);   // (zh_inflate.hip: this file has no HIP of its own)
-extern "C" void zh_device_release(void *p);
 extern "C" size_t zultra_memory_decompress_members(const unsigned char *pIn, size_t nIn, unsigned char *pOut, size_t nMaxOut, size_t *pnMembers) {
    if (pnMembers) *pnMembers = 0;
    if (!pIn || nIn == 0 || (!pOut && nMaxOut)) return (size_t)-1;

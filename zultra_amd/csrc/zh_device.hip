@@ -233,16 +233,13 @@ struct zultra_hip_ctx_s {
       }                                                                                                  \
    } while (0)
 
-// Shared with the host layer (libzultra.cpp), not exported: a caller's max-block size as the library takes it (libzultra.c:87-92), and the copy of
-// large inputs into pinned staging over a few threads
-__attribute__((visibility("hidden"))) uint32_t zh_clamp_block(uint32_t n) {
+// Shared with the host layer (libzultra.cpp, declared in zh_host.h): a caller's max-block size as the library takes it (libzultra.c:87-92)
+ZH_HIDDEN uint32_t zh_clamp_block(uint32_t n) {
    if (!n) n = 1048576;
    if (n < ZH_MIN_BLOCK) n = ZH_MIN_BLOCK;
    if (n > ZH_MAX_BLOCK) n = ZH_MAX_BLOCK;
    return n;
 }
-
-__attribute__((visibility("hidden"))) void zh_threaded_copy(uint8_t *dst, const uint8_t *src, size_t n, size_t piece);   // (libzultra.cpp)
 
 // ---- wave primitive self-check -------------------------------------------------------------------------------
 __global__ void __launch_bounds__(64) zh_selftest_kernel(uint32_t seed, uint32_t *bad) {

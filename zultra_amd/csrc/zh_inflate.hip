@@ -453,7 +453,7 @@ extern "C" int zultra_hip_inflate_file(int device, const void *src, size_t src_s
 }
 
 // For libzultra.cpp, which has no HIP of its own: a device copy of a host buffer, so that a call that walks a file run by run uploads it once.
-extern "C" void *zh_device_upload(int device, const void *host, size_t n) {
+extern "C" ZH_HIDDEN void *zh_device_upload(int device, const void *host, size_t n) {
    void *p = NULL;
    if (!host || n == 0 || device < 0 || device >= zultra_hip_device_count() || hipSetDevice(device) != hipSuccess || hipMalloc(&p, n) != hipSuccess) return NULL;
    if (hipMemcpy(p, host, n, hipMemcpyHostToDevice) != hipSuccess) {
@@ -462,4 +462,4 @@ extern "C" void *zh_device_upload(int device, const void *host, size_t n) {
    }
    return p;
 }
-extern "C" void zh_device_release(void *p) { (void)hipFree(p); }
+extern "C" ZH_HIDDEN void zh_device_release(void *p) { (void)hipFree(p); }

@@ -170,6 +170,23 @@ size_t zultra_memory_decompress_batch(const unsigned char *pIn, size_t nIn, cons
  * skips the two bytes). No dictionary. */
 size_t zultra_memory_decompress_members(const unsigned char *pIn, size_t nIn, unsigned char *pOut, size_t nMaxOut, size_t *pnMembers /* may be NULL */);
 
+/* bgzip(1): pIn cut into blocks of nBlockSize bytes (0 = 65280, bgzip's; at most 65280; the last block is shorter), every block an independent BGZF
+ * member — a gzip member whose `BC` extra subfield holds its size, at most 65536 bytes —, and BGZF's 28-byte empty member behind the last: the container
+ * zultra_memory_decompress_members and zultra_hip_inflate_file read in parallel. The blocks are compressed as max-blocks without history, in as many
+ * device batches as the context's capacity needs; headers, CRC-32 and ISIZE are written on the device (include/zultra_hip.h: zultra_hip_frame_members)
+ * and every batch's framed bytes are read back once. A member's deflate stream is zultra_memory_compress(block, ZULTRA_FLAG_RAW_DEFLATE, nBlockSize)'s.
+ * An empty input gives the 28-byte marker alone. Returns the bytes written, or (size_t)-1: nMaxOut too small (zultra_memory_bound_bgzf is enough),
+ * nBlockSize above 65280, a device failure, no device. One device (zultra_set_device); with zultra_set_verify every batch is verified after framing. */
+size_t zultra_memory_bound_bgzf(size_t nIn, unsigned int nBlockSize);
+size_t zultra_memory_compress_bgzf(const unsigned char *pIn, size_t nIn, unsigned char *pOut, size_t nMaxOut, unsigned int nBlockSize /* 0 = 65280; at most 65280 */);
+/* The writing counterpart of zultra_memory_decompress_batch: n independent inputs, pIn + pInOff[i] .. + pInSize[i], give n members of ONE framing
+ * (nFlags: raw deflate, zlib or gzip) back to back in pOut, member i at pOutOff[i] .. pOutOff[i + 1] — byte for byte what zultra_memory_compress(input i,
+ * nFlags, a max-block size >= its size) returns. Inputs below 8192 bytes go through a files context (include/zultra_hip.h), larger ones through a
+ * context of max-blocks; an input is ONE max-block, so at most 2 MiB. Returns the bytes written, or (size_t)-1: bad arguments, an empty input (as
+ * zultra_memory_compress refuses it), an input above 2 MiB, nMaxOut too small, a device failure, no device. One device; verified like the call above. */
+size_t zultra_memory_compress_batch(const unsigned char *pIn, size_t nIn, const size_t *pInOff, const size_t *pInSize, size_t n,
+                                    unsigned char *pOut, size_t nMaxOut, size_t *pOutOff /* n + 1, written */, const unsigned int nFlags /* 0, ZLIB, GZIP */);
+
 #ifdef __cplusplus
 }
 #endif

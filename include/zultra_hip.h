@@ -340,14 +340,43 @@ int zultra_hip_inflate_file(int device, const void *src, size_t src_size, int sr
  * decision and its whole kernel sequence is replayed from one captured hipGraph. zultra_hip_compress_files runs
  * stages 1-3 with every input as a max-block without history, then lays the raw deflate streams end to end in the
  * device stream buffer (zultra_hip_stream_read): input i occupies bytes file_off[i] .. file_off[i+1]. Each equals what
- * zultra_memory_compress(input i, ZULTRA_FLAG_RAW_DEFLATE) produces; gzip framing = 10-byte header + these bytes +
- * CRC-32 (zultra_hip_block_crc32 / zultra_crc32_append) + ISIZE. zultra_hip_stitch_files does the assembly alone for a
+ * zultra_memory_compress(input i, ZULTRA_FLAG_RAW_DEFLATE) produces; zultra_hip_frame_members (below) lays the same
+ * streams out as complete gzip, zlib or BGZF members. zultra_hip_stitch_files does the assembly alone for a
  * batch already compressed with zultra_hip_compress_blocks. Returns the number of inputs, or a negative error.
  */
 zultra_hip_ctx_t *zultra_hip_create_files(int device, uint32_t max_file_size, uint32_t max_files);
 int zultra_hip_compress_files(zultra_hip_ctx_t *ctx, const void *data, size_t data_size, int data_on_device, const uint64_t *offsets,
                               const uint32_t *sizes, uint32_t nfiles, uint64_t *file_off /* nfiles + 1 */);
 int zultra_hip_stitch_files(zultra_hip_ctx_t *ctx, uint64_t *file_off /* blocks + 1 */);
+
+/*
+ * Framed members: every max-block of the last batch of ANY context becomes one complete member in the context's stream buffer
+ * (zultra_hip_stream_device / zultra_hip_stream_read), the members back to back: header, the max-block's raw deflate stream exactly as
+ * zultra_hip_stitch_files lays it out (BFINAL on its last sub-block, padded to a byte), trailer. The device writes all of it — the assembly leaves room
+ * around every stream, a kernel behind the bit mover fills the room and finalises the checksums from the per-max-block parts —, so a batch of members
+ * reaches the host in one read, or goes straight into zultra_hip_inflate_members / zultra_hip_inflate_file without leaving the device.
+ *   framing  : 0 raw (zultra_hip_stitch_files with the offsets as {off, size}; check = 0), ZULTRA_FLAG_ZLIB_FRAMING, ZULTRA_FLAG_GZIP_FRAMING
+ *              (libzultra.h) — member b is then zultra_memory_compress(max-block b, framing, max_block >= n) byte for byte: the header of
+ *              zultra_frame_encode_header without a dictionary, the trailer of zultra_frame_encode_footer —, or ZULTRA_HIP_FRAME_BGZF: the header
+ *              1f 8b 08 04 00 00 00 00 00 ff 06 00 42 43 02 00 + BSIZE (member size - 1, u16 LE), the trailer CRC-32 + ISIZE. Anything else is -1
+ *   bgzf_eof : BGZF only: != 0 puts BGZF's 28-byte empty member behind the last one (the end of a file)
+ *   members  : host, one per max-block: first byte and size of the member in the stream buffer, the CRC-32 / Adler-32 as written, flags bit 0 =
+ *              oversize (BGZF: n > 65536 or a member above 65536 bytes)
+ *   total_bytes : the members and the end marker
+ * Every max-block must stand alone (prev == 0), else -1. Returns 0; -1 for bad arguments, no batch, and HIP errors; -2 where the reference fails with
+ * ZULTRA_ERROR_DST or the members do not fit the stream buffer; -3 (BGZF) where a member is oversize — members[] is filled, flags set. Nothing is written
+ * for -2 and -3. A context of max-blocks of at most ZULTRA_HIP_BGZF_BLOCK bytes never returns -3: the per-max-block buffer bound keeps every stream
+ * short enough. zultra_hip_verify_device afterwards verifies the framed buffer; zultra_hip_stitch_files afterwards assembles the
+ * plain layout again.
+ */
+#define ZULTRA_HIP_FRAME_BGZF 4u   /* next to 0 raw, ZULTRA_FLAG_ZLIB_FRAMING 1, ZULTRA_FLAG_GZIP_FRAMING 2 */
+#define ZULTRA_HIP_BGZF_BLOCK 65280u   /* bgzip's block size: input bytes per BGZF member */
+typedef struct zultra_hip_member_s { uint64_t off, size; uint32_t check, flags; } zultra_hip_member_t;  /* flags bit 0: oversize (BGZF) */
+int zultra_hip_frame_members(zultra_hip_ctx_t *ctx, unsigned int framing, int bgzf_eof,
+                             zultra_hip_member_t *members /* host, blocks */, uint64_t *total_bytes);
+/* A measurement hook (tools/frame_time.py), no part of the framing itself: device time of the last zultra_hip_frame_members' launches, milliseconds, from
+ * HIP events on the context's stream — the scan with the clearing behind it, the bit mover, the frame kernel. */
+void zultra_hip_last_frame_ms(const zultra_hip_ctx_t *ctx, float *ms /* [3] */);
 
 /* CRC-32 of every max-block of the last batch, computed on the device while the blocks are compressed: out[b] is the
  * linear part (zero initial state, no final inversion). zultra_crc32_append() folds one block into a running gzip CRC

@@ -91,6 +91,8 @@ class IndexResult(C.Structure):
     _fields_ = [("members", C.c_uint32), ("stop", C.c_uint32), ("out_size", C.c_uint64), ("src_used", C.c_uint64), ("tiles", C.c_uint32), ("tiles_rewalked", C.c_uint32)]
 
 
+MEMBER_DTYPE = [("off", "<u8"), ("size", "<u8"), ("check", "<u4"), ("flags", "<u4")]   # zultra_hip_member_t
+FRAME_BGZF = 4   # ZULTRA_HIP_FRAME_BGZF
 MEMBER_RESULT_DTYPE = [("reason", "<u4"), ("blocks", "<u4"), ("out_size", "<u8"), ("src_used", "<u8"), ("head_size", "<u4"), ("check", "<u4")]
 
 
@@ -116,6 +118,8 @@ EXPORTS = [
     "zultra_memory_decompress", "zultra_hip_inflate_streams", "zultra_memory_decompress_dict", "zultra_hip_inflate_streams_dict",
     "zultra_memory_decompress_batch", "zultra_hip_inflate_members",
     "zultra_hip_index_members", "zultra_hip_inflate_file", "zultra_memory_decompress_members",
+    # framed members
+    "zultra_hip_frame_members", "zultra_hip_last_frame_ms", "zultra_memory_bound_bgzf", "zultra_memory_compress_bgzf", "zultra_memory_compress_batch",
 ]
 
 
@@ -355,6 +359,44 @@ class Lib:
         if r == _SIZE_MAX:
             return -1, []
         return int(r), [None if int(out_size[i]) == _SIZE_MAX else out[int(out_off[i]): int(out_off[i]) + int(out_size[i])].tobytes() for i in range(n)]
+
+    def memory_bound_bgzf(self, n, block_size=0):
+        f = self.L.zultra_memory_bound_bgzf
+        f.argtypes = [C.c_size_t, C.c_uint]
+        f.restype = C.c_size_t
+        return int(f(n, block_size))
+
+    def memory_compress_bgzf(self, data, block_size=0, cap=None):
+        """zultra_memory_compress_bgzf -> the BGZF file (members of block_size input bytes each, 0 = 65280, and the end marker), or None where
+        the call returns (size_t)-1. cap: bytes of room, default the bound."""
+        data = _as_u8(data)
+        if cap is None:
+            cap = self.memory_bound_bgzf(len(data), block_size)
+        out = np.empty(max(cap, 1), dtype=np.uint8)
+        f = self.L.zultra_memory_compress_bgzf
+        f.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint]
+        f.restype = C.c_size_t
+        r = f(data.ctypes.data if len(data) else None, len(data), out.ctypes.data, cap, block_size)
+        return None if r == _SIZE_MAX else out[:r].tobytes()
+
+    def memory_compress_batch(self, data, inputs, flags, cap=None):
+        """zultra_memory_compress_batch over the inputs [(offset, size)] of `data`: one member of framing `flags` (0, FLAG_ZLIB, FLAG_GZIP) each,
+        back to back. -> (the bytes, out_off as n + 1 integers), or (None, None) where the call returns (size_t)-1."""
+        data = _as_u8(data)
+        n = len(inputs)
+        in_off = np.array([m[0] for m in inputs], dtype=np.uintp)
+        in_size = np.array([m[1] for m in inputs], dtype=np.uintp)
+        if cap is None:
+            cap = sum(self.memory_bound(int(m[1]), flags, 0) + 16 for m in inputs)
+        out = np.empty(max(cap, 1), dtype=np.uint8)
+        out_off = np.zeros(n + 1, dtype=np.uintp)
+        f = self.L.zultra_memory_compress_batch
+        f.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint]
+        f.restype = C.c_size_t
+        r = f(data.ctypes.data, len(data), in_off.ctypes.data, in_size.ctypes.data, n, out.ctypes.data, cap, out_off.ctypes.data, flags)
+        if r == _SIZE_MAX:
+            return None, None
+        return out[:r].tobytes(), [int(v) for v in out_off]
 
     def checksum(self, data, flags, start=None):
         data = _as_u8(data)
@@ -622,6 +664,38 @@ class HipContext:
         self.lib.L.zultra_hip_stream_write.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t]
         if self.lib.L.zultra_hip_stream_write(self.h, d.ctypes.data, offset, len(d)) != 0:
             raise ZultraError("stream_write")
+
+    def stitch_files(self):
+        """zultra_hip_stitch_files over the last batch -> uint64 array file_off[blocks + 1] into the stream buffer."""
+        out = np.zeros(len(self._block_n) + 1, dtype=np.uint64)
+        f = self.lib.L.zultra_hip_stitch_files
+        f.argtypes = [C.c_void_p, C.c_void_p]
+        rc = f(self.h, out.ctypes.data)
+        if rc != 0:
+            raise ZultraError("zultra_hip_stitch_files: %d %s" % (rc, self.lib.L.zultra_hip_last_error(self.h).decode()))
+        return out
+
+    def frame_members(self, framing, bgzf_eof=False, blocks=None):
+        """zultra_hip_frame_members over the last batch: every max-block a complete member of `framing` (0, FLAG_ZLIB, FLAG_GZIP, FRAME_BGZF) in the
+        stream buffer. -> (rc, members as a MEMBER_DTYPE array, total_bytes); rc 0, or -1 / -2 / -3 as the call returns them. blocks: how many
+        max-blocks the last batch had, where this object did not see it."""
+        n = len(self._block_n) if blocks is None else blocks
+        members = np.zeros(max(n, 1), dtype=MEMBER_DTYPE)
+        total = C.c_uint64(0)
+        f = self.lib.L.zultra_hip_frame_members
+        f.argtypes = [C.c_void_p, C.c_uint, C.c_int, C.c_void_p, C.POINTER(C.c_uint64)]
+        f.restype = C.c_int
+        rc = f(self.h, framing, 1 if bgzf_eof else 0, members.ctypes.data, C.byref(total))
+        return rc, members[:n], int(total.value)
+
+    def frame_ms(self):
+        """Device time of the last frame_members' launches, milliseconds: (scan, mover, frame kernel)."""
+        ms = (C.c_float * 3)()
+        f = self.lib.L.zultra_hip_last_frame_ms
+        f.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+        f.restype = None
+        f(self.h, ms)
+        return [float(v) for v in ms]
 
     def verify(self):
         """zultra_hip_verify_device over the last stitched batch -> dict of the report plus "rc" (0 verified, 1 mismatch) and "verify_ms"."""

@@ -1101,6 +1101,116 @@ extern "C" size_t zultra_memory_compress(const unsigned char *pIn, size_t nIn, u
    return zultra_memory_compress_dict(pIn, nIn, pOut, nOutCap, nFlags, nMaxBlockSize, NULL, 0);
 }
 
+// ---- framed members: every max-block of a batch a complete gzip / zlib / BGZF member, written on the device ------------------------------
+// (include/zultra_hip.h: zultra_hip_frame_members). One batch: compress, frame, verify if asked, one read of the framed bytes to `out`.
+// data_mode as zultra_hip_compress_blocks' data_on_device. Returns the bytes written, (size_t)-1 on any failure (cap too small among them).
+static size_t members_batch(zultra_hip_ctx_t *c, const uint8_t *data, size_t data_size, int data_mode, const zultra_hip_block_t *blocks, uint32_t count, unsigned framing,
+                            int eof, uint8_t *out, size_t cap, zultra_hip_member_t *members) {
+   uint64_t total = 0;
+   if (zultra_hip_compress_blocks(c, data, data_size, data_mode, blocks, count) <= 0) return (size_t)-1;
+   if (zultra_hip_frame_members(c, framing, eof, members, &total) != 0) return (size_t)-1;
+   if (zh_verify_on() && !zh_verify_stitched(c)) return (size_t)-1;
+   if (total > cap || zultra_hip_stream_read(c, out, 0, (size_t)total) != 0) return (size_t)-1;
+   return (size_t)total;
+}
+
+static const unsigned char g_bgzf_eof[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+
+// per member: header and trailer, and what zultra_memory_bound allows a max-block's stream beyond its input (64 sub-blocks, stored at worst)
+extern "C" size_t zultra_memory_bound_bgzf(size_t nIn, unsigned int nBlockSize) {
+   const size_t bs = nBlockSize ? nBlockSize : ZULTRA_HIP_BGZF_BLOCK;
+   return nIn + ((nIn + bs - 1) / bs) * (18 + 8 + (1 + 4 + 1) * 64) + sizeof(g_bgzf_eof);
+}
+
+extern "C" size_t zultra_memory_compress_bgzf(const unsigned char *pIn, size_t nIn, unsigned char *pOut, size_t nMaxOut, unsigned int nBlockSize) try {
+   // (a context of max-blocks of at most ZULTRA_HIP_BGZF_BLOCK bytes cannot produce an oversize member: include/zultra_hip.h)
+   const uint32_t bs = nBlockSize ? nBlockSize : ZULTRA_HIP_BGZF_BLOCK;
+   if (!pOut || (nIn && !pIn) || bs > ZULTRA_HIP_BGZF_BLOCK || zultra_hip_device_count() <= 0) return (size_t)-1;
+   if (!nIn) {
+      if (nMaxOut < sizeof(g_bgzf_eof)) return (size_t)-1;
+      memcpy(pOut, g_bgzf_eof, sizeof(g_bgzf_eof));
+      return sizeof(g_bgzf_eof);
+   }
+   const int dev = zh_pick_device();
+   const uint32_t ctx_bs = zh_clamp_block(bs);
+   const size_t total_blocks = (nIn + bs - 1) / bs;
+   const uint32_t per = ctx_blocks(dev, ctx_bs, total_blocks);
+   zultra_hip_ctx_t *c = ctx_acquire_on(dev, ctx_bs, per);
+   if (!c) return (size_t)-1;
+   std::vector<zultra_hip_block_t> blocks(per);
+   std::vector<zultra_hip_member_t> members(per);
+   size_t w = 0;
+   for (size_t b = 0; b < total_blocks && w != (size_t)-1; b += per) {
+      const size_t nb = total_blocks - b < per ? total_blocks - b : per, first = b * bs, bytes = nb * bs < nIn - first ? nb * bs : nIn - first;
+      for (size_t k = 0; k < nb; k++) blocks[k] = zultra_hip_block_t{(uint64_t)k * bs, 0, (uint32_t)(k + 1 == nb ? bytes - k * bs : bs)};
+      const size_t got = members_batch(c, pIn + first, bytes, 2, blocks.data(), (uint32_t)nb, ZULTRA_HIP_FRAME_BGZF, b + nb == total_blocks, pOut + w, nMaxOut - w, members.data());
+      w = got == (size_t)-1 ? got : w + got;
+   }
+   ctx_release(c);
+   return w;
+} catch (...) {
+   return (size_t)-1;
+}
+
+// Consecutive inputs of one kind — below 8192 bytes: a files context; from there on: a context of max-blocks as large as the call's largest input — share
+// a batch, as many as the context takes; a batch's inputs are gathered into the context's pinned staging and its members read to where they belong in pOut.
+extern "C" size_t zultra_memory_compress_batch(const unsigned char *pIn, size_t nIn, const size_t *pInOff, const size_t *pInSize, size_t n, unsigned char *pOut, size_t nMaxOut,
+                                               size_t *pOutOff, const unsigned int nFlags) try {
+   const size_t small_limit = 8192;
+   if (!pIn || !pInOff || !pInSize || !n || !pOut || !pOutOff || (nFlags != 0 && nFlags != ZULTRA_FLAG_ZLIB_FRAMING && nFlags != ZULTRA_FLAG_GZIP_FRAMING) || zultra_hip_device_count() <= 0)
+      return (size_t)-1;
+   size_t largest = 0, nsmall = 0;
+   for (size_t i = 0; i < n; i++) {
+      if (!pInSize[i] || pInSize[i] > nIn || pInOff[i] > nIn - pInSize[i] || pInSize[i] > 2097152) return (size_t)-1;   // (an empty input is refused, as by zultra_memory_compress; a member is ONE max-block)
+      largest = pInSize[i] > largest ? pInSize[i] : largest;
+      nsmall += pInSize[i] < small_limit;
+   }
+   const int dev = zh_pick_device();
+   struct Ctxs {   // (the files context is this call's own: the cache keeps contexts of max-blocks)
+      zultra_hip_ctx_t *files = NULL, *blocks = NULL;
+      ~Ctxs() {
+         if (files) zultra_hip_destroy(files);
+         ctx_release(blocks);
+      }
+   } C;
+   uint32_t files_cap = (uint32_t)(nsmall < 65536 ? nsmall : 65536);
+   const uint32_t ctx_bs = zh_clamp_block((uint32_t)largest), blocks_cap = n - nsmall ? ctx_blocks(dev, ctx_bs, n - nsmall) : 0;
+   // (a files context for fewer inputs per batch where the device has no room for the large one: down to 256, which is 10 MB or so)
+   while (nsmall && !(C.files = zultra_hip_create_files(dev, (uint32_t)small_limit - 1, files_cap))) {
+      if (files_cap <= 256) return (size_t)-1;
+      files_cap = files_cap / 4 < 256 ? 256 : files_cap / 4;
+   }
+   if (n - nsmall && !(C.blocks = ctx_acquire_on(dev, ctx_bs, blocks_cap))) return (size_t)-1;
+   std::vector<zultra_hip_block_t> blocks;
+   std::vector<zultra_hip_member_t> members;
+   size_t w = 0;
+   for (size_t i = 0; i < n;) {
+      const bool small = pInSize[i] < small_limit;
+      zultra_hip_ctx_t *c = small ? C.files : C.blocks;
+      const size_t max_count = small ? files_cap : blocks_cap, max_bytes = zultra_hip_data_capacity(c);
+      size_t j = i, bytes = 0;
+      blocks.clear();
+      for (; j < n && (pInSize[j] < small_limit) == small && j - i < max_count && bytes + pInSize[j] <= max_bytes; j++) {
+         blocks.push_back(zultra_hip_block_t{(uint64_t)bytes, 0, (uint32_t)pInSize[j]});
+         bytes += pInSize[j];
+      }
+      if (j == i) return (size_t)-1;
+      uint8_t *stage = (uint8_t *)zultra_hip_staging(c, 0, bytes);
+      if (!stage) return (size_t)-1;
+      for (size_t k = i; k < j; k++) memcpy(stage + blocks[k - i].win_off, pIn + pInOff[k], pInSize[k]);
+      members.resize(j - i);
+      const size_t got = members_batch(c, stage, bytes, 0, blocks.data(), (uint32_t)(j - i), nFlags, 0, pOut + w, nMaxOut - w, members.data());
+      if (got == (size_t)-1) return got;
+      for (size_t k = i; k < j; k++) pOutOff[k] = w + (size_t)members[k - i].off;
+      w += got;
+      i = j;
+   }
+   pOutOff[n] = w;
+   return w;
+} catch (...) {
+   return (size_t)-1;
+}
+
 // ================================================================================================================
 // Decompression: the framing on the host, the deflate stream on the device (zultra_hip_inflate_streams)
 // ================================================================================================================

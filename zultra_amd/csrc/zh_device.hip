@@ -38,6 +38,7 @@
 #include "zh_parse_lanes.h"
 #include "zh_split.h"
 #include "zh_stitch.h"
+#include "zh_frame.h"
 #include "zh_verify.h"
 
 #define ZH_MAX_RUNS 8           // staggered runs of a batch (ZULTRA_HIP_STREAMS)
@@ -206,6 +207,11 @@ struct zultra_hip_ctx_s {
    hipEvent_t ev_verify[2];
    int stream_stitched;       // 0: nothing to verify (no stitch yet, one that failed, a phase-table call since); 1: a stream; 2: one stream per max-block (files)
    float verify_ms;
+   // framed members (zh_frame.h, zultra_hip_frame_members): allocated by the first call; the head + tail bytes between the streams the buffer holds (0: none)
+   zh_member_t *d_members;
+   uint32_t frame_gap;
+   hipEvent_t ev_frame[4];    // around the scan, the mover and the frame kernel
+   float frame_ms[3];
    uint32_t *d_crc, *d_crc_tables, *d_adler;
    uint32_t *h_adler;
    std::vector<uint32_t> adler;
@@ -572,6 +578,9 @@ extern "C" void zultra_hip_destroy(zultra_hip_ctx_t *c) {
    if (c->h_vreport) (void)hipHostFree(c->h_vreport);
    for (int i = 0; i < 2; i++)
       if (c->ev_verify[i]) (void)hipEventDestroy(c->ev_verify[i]);
+   (void)hipFree(c->d_members);
+   for (int i = 0; i < 4; i++)
+      if (c->ev_frame[i]) (void)hipEventDestroy(c->ev_frame[i]);
    (void)hipFree(c->d_crc);
    (void)hipFree(c->d_adler);
    if (c->h_adler) (void)hipHostFree(c->h_adler);
@@ -660,7 +669,8 @@ static int zh_spread_streams(zultra_hip_ctx_t *c) {
 }
 #endif
 
-static int zh_enqueue_stitch(zultra_hip_ctx_t *c, hipStream_t st, uint32_t phase, int final_block, int files, bool scan_only, bool clear);
+struct zh_frame_args_t { uint32_t framing, eof; };   // (eof: bytes of end marker behind the last member)
+static int zh_enqueue_stitch(zultra_hip_ctx_t *c, hipStream_t st, uint32_t phase, int final_block, int files, bool scan_only, bool clear, const zh_frame_args_t *frame = NULL);
 static int zh_stitch_verdict(zultra_hip_ctx_t *c, bool scan_only);
 
 // streams (and payload areas) a context holds for the staggered runs of a batch: ZULTRA_HIP_STREAMS, 0 or unset = auto = four (zh_create_buffers and
@@ -784,7 +794,7 @@ static int zh_create_buffers(zultra_hip_ctx_t *c) {
        zh_alloc(c, &c->d_items, B * c->max_subs) || zh_alloc(c, &c->d_crc, B) || zh_alloc(c, &c->d_adler, 2 * B) || zh_alloc(c, &c->d_crc_tables, 256 + 1024))
       return -1;
    ZH_CHECK(c, hipMemset(c->d_ntasks, 0, ZH_NCNT * sizeof(uint32_t)));
-   c->stream_cap = (size_t)(B * (N + 5 * (N / 65535 + 1) + 8) + 64) & ~(size_t)3;
+   c->stream_cap = (size_t)(B * (N + 5 * (N / 65535 + 1) + 8 + ZH_FRAME_ROOM) + 64) & ~(size_t)3;   // (+ 64: slack, and BGZF's end marker)
    ZH_CHECK(c, hipMalloc((void **)&c->d_stream, c->stream_cap + 16));
    {
       // CRC tables: byte table of 0xEDB88320 and the 'append ZH_CRC_SLICE zero bytes' operator, one table per state byte
@@ -898,7 +908,7 @@ extern "C" size_t zultra_hip_context_bytes_on(int device, uint32_t max_block_siz
    bytes += B * N * ZH_NMATCH * sizeof(zh_match_t) + B * tok_stride * (4 + 2 + 4 + 2);   // rows, token chain, parse, costs
    bytes += B * (tok_stride / 64) * 8;                               // barrier bitmap
    bytes += B * slot_stride;                                         // payload slots
-   bytes += (B * (N + 5 * (N / 65535 + 1) + 8) + 80);                // stitched stream
+   bytes += (B * (N + 5 * (N / 65535 + 1) + 8 + ZH_FRAME_ROOM) + 80);                // stitched stream
    bytes += subs * (sizeof(zh_sbstate_t) + sizeof(zh_work_t) + 2 * sizeof(zh_subblock_t) + sizeof(zh_stitch_item_t));
    bytes += tasks * (2 * sizeof(uint2) + 4 * 4 + 4 + ZH_NSYM * 4);   // task map and ranges, chain lists, bit counts, histograms
    bytes += B * (S * (sizeof(zh_seg_t) + 8) + sizeof(zh_block_t) + cpb * 12 + (ZH_MAX_SPLITS + 1) * 4 + 6 * 4) + 8192;
@@ -1358,6 +1368,7 @@ static int zh_run_files(zultra_hip_ctx_t *c, uint32_t nblocks) {
    c->nsubs = nblocks;
    c->files_stitch_rc = zh_stitch_verdict(c, false);
    c->stream_stitched = c->files_stitch_rc == 0 ? 2 : 0;
+   c->frame_gap = 0;
    c->files_stitched = 1;   // (no stitch_ms of its own: inside a captured graph an event is a node, not a time stamp; the batch's encode_ms covers the assembly)
    (void)hipEventElapsedTime(&c->timing.h2d_ms, c->lane_ev[0][ZH_EV_START], c->ev_input);
    (void)hipEventElapsedTime(&c->timing.encode_ms, c->lane_ev[0][ZH_EV_INPUT], c->lane_ev[0][ZH_EV_READBACK]);   // the whole graph
@@ -1447,8 +1458,8 @@ static int zh_upload_batch(zultra_hip_ctx_t *c, const void *data, size_t data_si
 
 // What a stitch clears of the stream buffer for the last batch: everything the batch can fill — no sub-block takes more than its stored form, size + 5
 // bytes per 65535 + the three header bits
-static size_t zh_stream_clear_bytes(const zultra_hip_ctx_t *c) {
-   uint64_t bound = 16;
+static size_t zh_stream_clear_bytes(const zultra_hip_ctx_t *c, uint64_t framing_bytes = 0) {
+   uint64_t bound = 16 + framing_bytes;
    for (uint32_t b = 0; b < c->nblocks; b++) bound += (uint64_t)c->blocks[b].n + 5ull * (c->blocks[b].n / 65535u + 1u);
    bound += 5ull * (uint64_t)c->nblocks * c->max_subs;
    return (size_t)zh_min64((uint64_t)c->stream_cap + 16, (bound + 3) & ~3ull);
@@ -1550,6 +1561,7 @@ static int zh_read_back(zultra_hip_ctx_t *c, const uint32_t *run_b0, int lanes, 
    if (stitch_now) {
       c->stitched_rc = zh_stitch_verdict(c, false);
       c->stream_stitched = c->stitched_rc == 0 ? 1 : 0;
+      c->frame_gap = 0;
       c->stitched_phase = c->ab_phase;
       c->stitched_final = c->ab_final;
       c->stitched_valid = 1;
@@ -1604,6 +1616,7 @@ extern "C" int zultra_hip_compress_blocks(zultra_hip_ctx_t *c, const void *data,
    c->stitched_valid = 0;
    c->files_stitched = 0;
    c->stream_stitched = 0;
+   c->frame_gap = 0;   // (whatever assembles this batch — its own graph, a stitch armed with it — lays the plain layout)
    c->nblocks = nblocks;
    c->nsubs = 0;
    c->blocks.assign((const zh_block_t *)blocks, (const zh_block_t *)blocks + nblocks);
@@ -1664,21 +1677,48 @@ extern "C" int zultra_hip_block_crc32(const zultra_hip_ctx_t *c, uint32_t *out) 
 // The stitch of the batch whose descriptors zh_compact_results has laid out (or will have, on `st`): clears what the bits are ORed into — unless the caller
 // has (clear = false) —, the scan, the bit mover, the 80 bytes the scan reports. The grids need no count from the host: the scan is one workgroup, the mover strides
 // over scan->nsubs. Enqueues only.
-static int zh_enqueue_stitch(zultra_hip_ctx_t *c, hipStream_t st, uint32_t phase, int final_block, int files, bool scan_only, bool clear) {
-   if (!scan_only && clear) ZH_CHECK(c, hipMemsetAsync(c->d_stream, 0, zh_stream_clear_bytes(c), st));   // (zero where bits will be ORed in)
+// frame (files form only, zultra_hip_frame_members): room for a header and a trailer around every stream, cleared with the rest, and zh_frame_members behind the mover to fill it.
+static int zh_enqueue_stitch(zultra_hip_ctx_t *c, hipStream_t st, uint32_t phase, int final_block, int files, bool scan_only, bool clear, const zh_frame_args_t *frame) {
+   const uint32_t head = frame ? zh_frame_head(frame->framing) : 0u, tail = frame ? zh_frame_tail(frame->framing) : 0u, eof = frame ? frame->eof : 0u;
+   const uint32_t member_max = frame && frame->framing == ZH_FRAME_BGZF ? ZH_BGZF_MEMBER_MAX : 0u;
+   if (!scan_only && clear && !frame) ZH_CHECK(c, hipMemsetAsync(c->d_stream, 0, zh_stream_clear_bytes(c), st));   // (zero where bits will be ORed in)
    // (the inputs of a files context are smaller than any max-block: their streams are assembled with the buffer bound of the smallest)
    const uint32_t block_size = c->max_block < ZH_MIN_BLOCK ? (uint32_t)ZH_MIN_BLOCK : c->max_block;
    // (the scan's chunk tables are 32-bit: a chunk of ceil(nblocks / 1024) max-blocks must stay below 2^32 bits — only HBM capacity has ruled that out so far)
-   if (((uint64_t)c->nblocks + ZH_SCAN_THREADS - 1) / ZH_SCAN_THREADS * zh_stitch_blockbuf_cap(block_size) * 8ull >= (1ull << 32)) {
+   if (((uint64_t)c->nblocks + ZH_SCAN_THREADS - 1) / ZH_SCAN_THREADS * (zh_stitch_blockbuf_cap(block_size) + 1 + head + tail) * 8ull >= (1ull << 32)) {
       snprintf(c->err, sizeof(c->err), "batch too large for the stream assembly's 32-bit chunk tables (%u max-blocks of %u bytes)", c->nblocks, c->max_block);
       return -1;
    }
-   ZH_LAUNCH(zh_stitch_scan, 1, ZH_SCAN_THREADS, st, (const zh_subblock_t *)c->d_results_compact, (const uint32_t *)c->d_nsubs, c->nblocks, phase,
-             files ? block_size : c->max_block, final_block, files, c->d_blk_start, c->d_items, c->d_file_off, c->d_scan_out);
+   if (frame)
+      ZH_LAUNCH(zh_stitch_scan<true>, 1, ZH_SCAN_THREADS, st, (const zh_subblock_t *)c->d_results_compact, (const uint32_t *)c->d_nsubs, c->nblocks, phase,
+                files ? block_size : c->max_block, final_block, files, head, tail, member_max, c->d_blk_start, c->d_items, c->d_file_off, c->d_scan_out);
+   else
+      ZH_LAUNCH(zh_stitch_scan<false>, 1, ZH_SCAN_THREADS, st, (const zh_subblock_t *)c->d_results_compact, (const uint32_t *)c->d_nsubs, c->nblocks, phase,
+                files ? block_size : c->max_block, final_block, files, 0u, 0u, 0u, c->d_blk_start, c->d_items, c->d_file_off, c->d_scan_out);
+   if (frame) {
+      // (a framed assembly clears behind its scan, which knows how much — and whether: a refused call writes nothing)
+      const uint64_t worst = zh_stream_clear_bytes(c, (uint64_t)c->nblocks * (head + tail) + eof);
+      ZH_LAUNCH(zh_frame_clear, (uint32_t)zh_max64(1, zh_min64(worst / (16 * ZH_FRAME_CLEAR_THREADS), 4096)), ZH_FRAME_CLEAR_THREADS, st, (const zh_scan_out_t *)c->d_scan_out,
+                (uint64_t)c->stream_cap - eof, eof, (uint4 *)c->d_stream);
+      ZH_CHECK(c, hipEventRecord(c->ev_frame[1], st));
+   }
    if (!scan_only) {
       const uint32_t grid = (uint32_t)zh_min64((uint64_t)c->nblocks * c->max_subs, zh_max64(4ull * c->nblocks, 1024));
       ZH_LAUNCH(zh_stitch, grid, ZH_STITCH_THREADS, st, (const zh_subblock_t *)c->d_results_compact, (const zh_stitch_item_t *)c->d_items, (const zh_block_t *)c->d_blocks, c->cur_data,
-                (const uint8_t *)c->d_payload, c->d_stream, (const zh_scan_out_t *)c->d_scan_out, (uint64_t)c->stream_cap);
+                (const uint8_t *)c->d_payload, c->d_stream, (const zh_scan_out_t *)c->d_scan_out, (uint64_t)c->stream_cap - eof);
+   }
+   if (frame) {
+      // one lane per member and one for the end marker, the kernel strides. ZULTRA_HIP_GRID_CAP (tests) caps the LANES here — a member is one lane's work, and
+      // a cap on workgroups of 64 would need hundreds of members before a lane saw a second one
+      uint32_t threads = ZH_FRAME_THREADS, grid = (c->nblocks + 1 + ZH_FRAME_THREADS - 1) / ZH_FRAME_THREADS;
+      if (c->grid_cap && (uint64_t)grid * threads > c->grid_cap) {
+         threads = min(threads, c->grid_cap);
+         grid = max(1u, c->grid_cap / threads);
+      }
+      ZH_CHECK(c, hipEventRecord(c->ev_frame[2], st));
+      ZH_LAUNCH(zh_frame_members, grid, threads, st, (const zh_block_t *)c->d_blocks, c->nblocks, (const uint64_t *)c->d_file_off, (const uint32_t *)c->d_crc, (const uint32_t *)c->d_adler,
+                (const zh_scan_out_t *)c->d_scan_out, (uint64_t)c->stream_cap - eof, frame->framing, member_max, eof, (uint8_t *)c->d_stream, c->d_members);
+      ZH_CHECK(c, hipEventRecord(c->ev_frame[3], st));
    }
    ZH_CHECK(c, hipEventRecord(c->ev_stitch[ZH_STITCH_EV_END], st));
    ZH_CHECK(c, hipMemcpyAsync(c->h_scan_out, c->d_scan_out, sizeof(zh_scan_out_t), hipMemcpyDeviceToHost, st));
@@ -1703,19 +1743,36 @@ static int zh_stitch_verdict(zultra_hip_ctx_t *c, bool scan_only) {
    return 0;
 }
 
-static int zh_stitch_on_device(zultra_hip_ctx_t *c, uint32_t phase, int final_block, int files, bool scan_only = false) {
+static int zh_stitch_on_device(zultra_hip_ctx_t *c, uint32_t phase, int final_block, int files, bool scan_only = false, const zh_frame_args_t *frame = NULL) {
    ZH_CHECK(c, hipSetDevice(c->device));
    hipStream_t st = c->stream;
    c->stitched_valid = 0;   // (the items and the scan's report are rewritten)
    c->files_stitched = 0;
    c->stream_stitched = 0;
+   c->frame_gap = 0;
    ZH_CHECK(c, hipEventRecord(c->ev_stitch[ZH_STITCH_EV_START], st));
-   if (zh_enqueue_stitch(c, st, phase, final_block, files, scan_only, true) != 0) return -1;
+   if (frame) ZH_CHECK(c, hipEventRecord(c->ev_frame[0], st));
+   if (zh_enqueue_stitch(c, st, phase, final_block, files, scan_only, true, frame) != 0) return -1;
    ZH_CHECK(c, hipStreamSynchronize(st));
    ZH_CHECK(c, hipGetLastError());
    if (!scan_only) (void)hipEventElapsedTime(&c->timing.stitch_ms, c->ev_stitch[ZH_STITCH_EV_START], c->ev_stitch[ZH_STITCH_EV_END]);
-   const int rc = zh_stitch_verdict(c, scan_only);
-   if (!scan_only && rc == 0) c->stream_stitched = files ? 2 : 1;
+   if (frame)
+      for (int i = 0; i < 3; i++) (void)hipEventElapsedTime(&c->frame_ms[i], c->ev_frame[i], c->ev_frame[i + 1]);
+   int rc = zh_stitch_verdict(c, scan_only);
+   if (frame && c->h_scan_out->nsubs == c->nsubs && !c->h_scan_out->failed) {   // (what a framed assembly reports of its own; the end marker needs its room too)
+      if (c->h_scan_out->oversize) {
+         snprintf(c->err, sizeof(c->err), "a max-block, or its member, is larger than a BGZF member can be (%u bytes)", ZH_BGZF_MEMBER_MAX);
+         rc = -3;
+      }
+      else if (((c->h_scan_out->end_bit + 7) >> 3) + 8 + frame->eof > c->stream_cap) {
+         snprintf(c->err, sizeof(c->err), "the framed members do not fit the stream buffer");
+         rc = -2;
+      }
+   }
+   if (!scan_only && rc == 0) {
+      c->stream_stitched = files ? 2 : 1;
+      if (frame) c->frame_gap = zh_frame_head(frame->framing) + zh_frame_tail(frame->framing);
+   }
    return rc;
 }
 
@@ -1782,6 +1839,38 @@ extern "C" int zultra_hip_stitch_files(zultra_hip_ctx_t *c, uint64_t *file_off /
    return 0;
 }
 
+// Framed members (zh_frame.h): the files-form assembly with room around every stream, and the kernel that fills the room, for the last batch of any context.
+// A files context's captured graph holds the plain assembly: here the batch is assembled again — scan, clearing, mover, frame kernel, one synchronisation.
+static_assert(sizeof(zultra_hip_member_t) == sizeof(zh_member_t), "zultra_hip_member_t is zh_member_t");
+static_assert(zh_bgzf_member_bound(ZULTRA_HIP_BGZF_BLOCK) <= ZH_BGZF_MEMBER_MAX, "a block of the default BGZF block size always fits a member (DESIGN.md 3.12)");
+extern "C" int zultra_hip_frame_members(zultra_hip_ctx_t *c, unsigned int framing, int bgzf_eof, zultra_hip_member_t *members, uint64_t *total_bytes) {
+   ZH_EMU_SERIALIZE();
+   if (!c || !members || !total_bytes || c->nsubs == 0) return -1;
+   if (framing != ZH_FRAME_RAW && framing != ZH_FRAME_ZLIB && framing != ZH_FRAME_GZIP && framing != ZH_FRAME_BGZF) {
+      snprintf(c->err, sizeof(c->err), "framing %u: one of raw (0), zlib (1), gzip (2), BGZF (4)", framing);
+      return -1;
+   }
+   for (uint32_t b = 0; b < c->nblocks; b++)
+      if (c->blocks[b].prev != 0) {
+         snprintf(c->err, sizeof(c->err), "max-block %u has history: a member stands alone", b);
+         return -1;
+      }
+   ZH_CHECK(c, hipSetDevice(c->device));
+   if (!c->d_file_off && zh_alloc(c, &c->d_file_off, (size_t)c->max_blocks + 1)) return -1;
+   if (!c->d_members && zh_alloc(c, &c->d_members, (size_t)c->max_blocks)) return -1;
+   for (int i = 0; i < 4; i++)
+      if (!c->ev_frame[i]) ZH_CHECK(c, hipEventCreate(&c->ev_frame[i]));
+   const zh_frame_args_t frame = {framing, (framing == ZH_FRAME_BGZF && bgzf_eof) ? ZH_BGZF_EOF_SIZE : 0u};
+   const int rc = zh_stitch_on_device(c, 0, -1, 1, false, &frame);
+   if (rc != 0 && rc != -3) return rc;
+   ZH_CHECK(c, hipMemcpy(members, c->d_members, (size_t)c->nblocks * sizeof(zh_member_t), hipMemcpyDeviceToHost));
+   if (rc == 0) *total_bytes = members[c->nblocks - 1].off + members[c->nblocks - 1].size + frame.eof;
+   return rc;
+}
+extern "C" void zultra_hip_last_frame_ms(const zultra_hip_ctx_t *c, float *ms /* [3]: scan, mover, frame kernel */) {
+   for (int i = 0; c && ms && i < 3; i++) ms[i] = c->frame_ms[i];
+}
+
 extern "C" int zultra_hip_compress_files(zultra_hip_ctx_t *c, const void *data, size_t data_size, int data_on_device, const uint64_t *offsets,
                                          const uint32_t *sizes, uint32_t nfiles, uint64_t *file_off) {
    if (!c || !offsets || !sizes || !file_off || nfiles == 0) return -1;
@@ -1838,7 +1927,7 @@ extern "C" int zultra_hip_verify_device(zultra_hip_ctx_t *c, zultra_hip_verify_t
    const uint32_t grid = (uint32_t)zh_min64(c->nsubs, zh_max64(12ull * c->total_cus, 64));   // (one wave per workgroup, three to a SIMD — zh_verify.h: a CU holds 12; more would only queue)
    ZH_LAUNCH(zh_verify_subblocks, grid, ZH_VERIFY_THREADS, st, (const uint32_t *)c->d_stream, (uint64_t)c->stream_cap, (const zh_stitch_item_t *)c->d_items,
              (const zh_subblock_t *)c->d_results_compact, (const zh_block_t *)c->d_blocks, c->nblocks, c->cur_data, (const zh_scan_out_t *)c->d_scan_out, (const uint64_t *)c->d_file_off, files,
-             c->d_vitems, c->d_vreport);
+             c->frame_gap, c->d_vitems, c->d_vreport);
    ZH_CHECK(c, hipEventRecord(c->ev_verify[1], st));
    ZH_CHECK(c, hipMemcpyAsync(c->h_vreport, c->d_vreport, sizeof(zh_verify_report_t), hipMemcpyDeviceToHost, st));
    ZH_CHECK(c, hipStreamSynchronize(st));

@@ -97,7 +97,7 @@ struct zh_scan_out_t {
    uint32_t nsubs;
    uint64_t table_end[8];     // end_bit for each of the eight start phases of the batch (start bit = the phase)
    uint32_t table_failed;     // bit p: start phase p overflows a max-block buffer
-   uint32_t pad;
+   uint32_t oversize;         // files form with member_max: a max-block's input, or its member (head + stream + tail), exceeds member_max bytes — nothing is written then
 };
 
 
@@ -184,7 +184,7 @@ __device__ __forceinline__ void zh_stitch_one(uint32_t s, const zh_subblock_t *_
 __global__ void __launch_bounds__(ZH_STITCH_THREADS)
 zh_stitch(const zh_subblock_t *__restrict__ subs, const zh_stitch_item_t *__restrict__ items, const zh_block_t *__restrict__ blocks,
           const uint8_t *__restrict__ data, const uint8_t *__restrict__ payload, uint32_t *out, const zh_scan_out_t *__restrict__ scan, uint64_t stream_cap) {
-   if (scan->failed || ((scan->end_bit + 7) >> 3) + 8 > stream_cap) return;
+   if (scan->failed || scan->oversize || ((scan->end_bit + 7) >> 3) + 8 > stream_cap) return;
    const uint32_t nsubs = scan->nsubs;
    for (uint32_t s = blockIdx.x; s < nsubs; s += gridDim.x) zh_stitch_one(s, subs, items, blocks, data, payload, out);
 }
@@ -240,19 +240,25 @@ zh_compact_results(zh_runs_t R, const zh_subblock_t *__restrict__ results, const
 //   3  thread t walks its chunk again from its true start bit and writes the items: destination bit, stored or not, BFINAL.
 // files != 0: every max-block is a stream of its own (files mode): it starts on a byte boundary at phase 0, its last sub-block carries BFINAL;
 // file_off[b] = its first byte, file_off[nblocks] = the end.
+// head / tail (files form only, zh_frame.h): bytes left free in front of and behind every stream for a member's header and trailer — stream b starts head bytes
+// behind the end of stream b - 1's tail, the items' dst_bit and file_off say so, and member b is bytes file_off[b] - head .. file_off[b + 1] - head: file_off[nblocks]
+// is where a further stream would start, head bytes behind the last tail (end_bit is the end of that tail). Zero for both is the plain files form.
+// member_max != 0: out->oversize where a max-block's input or its member is larger (BGZF: 65536).
+// FRAMED = false compiles all of that away (head = tail = member_max = 0): the plain assembly runs the scan it ran before there were framed members.
 // Rounds 1-4 planned this serially on the host (zh_stitch_plan above, kept as the statement of the rule the tests hold this kernel to), between a
 // read-back of the descriptors and an upload of the items.
 #define ZH_SCAN_THREADS 1024
+template <bool FRAMED>
 __global__ void __launch_bounds__(ZH_SCAN_THREADS)
 zh_stitch_scan(const zh_subblock_t *__restrict__ subs, const uint32_t *__restrict__ nsubs_p, uint32_t nblocks, uint32_t phase, uint32_t max_block_size, int final_block, int files,
-               uint32_t *blk_start /* scratch, nblocks + 1 */, zh_stitch_item_t *items, uint64_t *file_off /* files: nblocks + 1 */, zh_scan_out_t *out) {
+               uint32_t head_, uint32_t tail_, uint32_t member_max_, uint32_t *blk_start /* scratch, nblocks + 1 */, zh_stitch_item_t *items, uint64_t *file_off /* files: nblocks + 1 */, zh_scan_out_t *out) {
    __shared__ uint32_t T[ZH_SCAN_THREADS][8];      // per chunk and start phase: bits added
    __shared__ uint32_t Tfail[ZH_SCAN_THREADS];     // ... bit p: the walk from phase p overflows
    __shared__ uint64_t Wv[ZH_SCAN_THREADS / 64][8];                                // the same per wave of chunks
    __shared__ uint32_t Wfail[ZH_SCAN_THREADS / 64];
    __shared__ uint64_t wave_start[ZH_SCAN_THREADS / 64 + 1];
    __shared__ uint64_t chunk_start[ZH_SCAN_THREADS];
-   __shared__ uint32_t s_failed, s_table_failed;
+   __shared__ uint32_t s_failed, s_table_failed, s_oversize;
    const uint32_t tid = threadIdx.x;
    const uint32_t nsubs = *nsubs_p;
    if (nsubs == 0xFFFFFFFFu) {   // (a void run in the batch, zh_compact_results: nothing to assemble — zh_stitch leaves at `failed`)
@@ -261,11 +267,14 @@ zh_stitch_scan(const zh_subblock_t *__restrict__ subs, const uint32_t *__restric
          out->failed = 1;
          out->nsubs = nsubs;
          out->table_failed = 0xffu;
+         out->oversize = 0;
       }
       return;
    }
    const uint64_t cap = zh_stitch_blockbuf_cap(max_block_size);
-   if (tid == 0) s_failed = s_table_failed = 0;
+   if (tid == 0) s_failed = s_table_failed = s_oversize = 0;
+   const uint32_t head = FRAMED ? head_ : 0u, tail = FRAMED ? tail_ : 0u, member_max = FRAMED ? member_max_ : 0u;
+   const uint64_t head_bits = 8ull * head, tail_bits = 8ull * tail;
    if (tid < ZH_SCAN_THREADS / 64) Wfail[tid] = 0;
    // ---- 0: where every max-block's sub-blocks start
    for (uint32_t k = tid; k < nsubs; k += ZH_SCAN_THREADS)
@@ -285,7 +294,7 @@ zh_stitch_scan(const zh_subblock_t *__restrict__ subs, const uint32_t *__restric
          const uint32_t k0 = blk_start[b], k1 = blk_start[b + 1];
 #pragma unroll
          for (uint32_t p = 0; p < 8; p++) {
-            if (files) bit[p] = (bit[p] + 7) & ~7ull;
+            if (files) bit[p] = ((bit[p] + 7) & ~7ull) + head_bits;
             base[p] = bit[p] >> 3;
          }
          for (uint32_t k = k0; k < k1; k++) {
@@ -296,6 +305,10 @@ zh_stitch_scan(const zh_subblock_t *__restrict__ subs, const uint32_t *__restric
                uint32_t stored;
                if (zh_stitch_step(&bit[p], base[p], size, nbits, failed, cap, &stored) != 0) fail |= 1u << p;
             }
+         }
+         if (FRAMED && files) {
+#pragma unroll
+            for (uint32_t p = 0; p < 8; p++) bit[p] = ((bit[p] + 7) & ~7ull) + tail_bits;   // (the pad alone changes nothing: the next stream pads again)
          }
       }
 #pragma unroll
@@ -362,10 +375,11 @@ zh_stitch_scan(const zh_subblock_t *__restrict__ subs, const uint32_t *__restric
       for (uint32_t b = B0; b < B1; b++) {
          const uint32_t k0 = blk_start[b], k1 = blk_start[b + 1];
          if (files) {
-            bit = (bit + 7) & ~7ull;
+            bit = ((bit + 7) & ~7ull) + head_bits;
             file_off[b] = bit >> 3;
          }
          const uint64_t base = bit >> 3;
+         uint32_t n_in = 0;
          for (uint32_t k = k0; k < k1; k++) {
             zh_stitch_item_t it;
             it.dst_bit = bit;
@@ -373,6 +387,11 @@ zh_stitch_scan(const zh_subblock_t *__restrict__ subs, const uint32_t *__restric
             it.stored = 0;
             if (zh_stitch_step(&bit, base, subs[k].size, subs[k].nbits, subs[k].failed, cap, &it.stored) != 0) fail = 1;
             items[k] = it;
+            if (FRAMED) n_in += subs[k].size;
+         }
+         if (FRAMED && files) {
+            bit = ((bit + 7) & ~7ull) + tail_bits;
+            if (member_max && (n_in > member_max || (bit >> 3) - base + head > member_max)) atomicOr(&s_oversize, 1u);
          }
       }
       if (fail) atomicOr(&s_failed, 1u);
@@ -382,11 +401,12 @@ zh_stitch_scan(const zh_subblock_t *__restrict__ subs, const uint32_t *__restric
       uint64_t end = wave_start[ZH_SCAN_THREADS / 64];
       if (files) {
          end = (end + 7) & ~7ull;
-         file_off[nblocks] = end >> 3;
+         file_off[nblocks] = (end >> 3) + head;
       }
       out->end_bit = end;
       out->failed = s_failed;
       out->table_failed = s_table_failed;
+      out->oversize = s_oversize;
       out->nsubs = nsubs;
    }
 }

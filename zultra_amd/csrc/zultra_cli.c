@@ -9,7 +9,10 @@
  *    zultra_amd_cli [-b <max block size>] [-f gzip|zlib|raw] [-k <chunk KiB>] [-d <device>] [-D <dictionary>] [-c] [-v] <infile> <outfile>
  *    zultra_amd_cli -x [-f gzip|zlib|raw] [-d <device>] [-D <dictionary>] [-v] <infile> <outfile>
  *    zultra_amd_cli -x -m [-f gzip] [-d <device>] [-v] <infile> <outfile>
+ *    zultra_amd_cli -f bgzf [-b <block size>] [-d <device>] [-c] [-v] <infile> <outfile>
  *
+ * -f bgzf: bgzip(1) — <infile> in blocks of -b bytes (default and at most 65280), every block a BGZF member written on the device, and BGZF's end marker
+ *     (zultra_memory_compress_bgzf); `-x -m -f gzip` is the way back. No dictionary: a member stands alone.
  * -D: a preset dictionary, loaded as the reference's tool loads it (zultra_dictionary_load: the last 32 KiB of the file; tool/zultra.c -D). Compressing,
  *     it is set before the first zultra_stream_compress (zultra_stream_set_dictionary: the history of the first max-block; a zlib header gets FDICT and
  *     the DICTID); with -x the stream is inflated against it (zultra_memory_decompress_dict: a zlib stream's DICTID must be this dictionary's).
@@ -33,6 +36,46 @@ static double now_s(void) {
    struct timespec ts;
    clock_gettime(CLOCK_MONOTONIC, &ts);
    return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec;
+}
+
+/* -f bgzf: the whole file through zultra_memory_compress_bgzf */
+static int write_bgzf(FILE *fin, FILE *fout, unsigned block, int verbose, int verify) {
+   size_t n = 0, cap = (size_t)1 << 20;
+   unsigned char *in = (unsigned char *)malloc(cap);
+   for (size_t got; in && (got = fread(in + n, 1, cap - n, fin)) > 0;) {
+      n += got;
+      if (n == cap) {
+         unsigned char *more = (unsigned char *)realloc(in, cap *= 2);
+         if (!more) free(in);
+         in = more;
+      }
+   }
+   const size_t room = zultra_memory_bound_bgzf(n, block);
+   unsigned char *out = in ? (unsigned char *)malloc(room) : NULL;
+   if (!out) {
+      fprintf(stderr, "out of memory\n");
+      free(in);
+      return 100;
+   }
+   const double t0 = now_s();
+   const size_t size = zultra_memory_compress_bgzf(in, n, out, room, block);
+   const double dt = now_s() - t0;
+   int rc = 0;
+   if (size == (size_t)-1) {
+      fprintf(stderr, "compression error (a failed verification, a device failure, or no HIP device: this library has no CPU path)\n");
+      rc = 100;
+   }
+   else if (fwrite(out, 1, size, fout) != size) {
+      fprintf(stderr, "write error\n");
+      rc = 100;
+   }
+   if (verbose && !rc)
+      fprintf(stdout, "%llu -> %llu bytes (%.2f %%), %.1f MB/s\n", (unsigned long long)n, (unsigned long long)size, n ? 100.0 * (double)size / (double)n : 0.0, dt > 0 ? (double)n / dt / 1e6 : 0.0);
+   if (verbose && verify && !rc) fprintf(stdout, "verified %llu bytes on the device\n", zultra_verified_bytes());
+   zultra_release_cached_contexts();
+   free(in);
+   free(out);
+   return rc;
 }
 
 /* -x: the whole file through zultra_memory_decompress. The output size is not known in advance (gzip's ISIZE is a hint, modulo 2^32): the buffer
@@ -92,7 +135,7 @@ static int extract(FILE *fin, FILE *fout, unsigned flags, int verbose, const voi
 int main(int argc, char **argv) {
    unsigned flags = ZULTRA_FLAG_GZIP_FRAMING, block = 0;
    size_t chunk = (size_t)8 << 20;
-   int verbose = 0, verify = 0, do_extract = 0, members = 0, device = 0, i = 1;
+   int verbose = 0, verify = 0, do_extract = 0, members = 0, device = 0, bgzf = 0, i = 1;
    const char *dict_name = NULL;
    if (getenv("ZULTRA_HIP_DEVICE")) device = atoi(getenv("ZULTRA_HIP_DEVICE"));   /* (the library's own default: -m sizes its buffer with an index call on the same device) */
    for (; i < argc && argv[i][0] == '-' && argv[i][1]; i++) {
@@ -104,7 +147,8 @@ int main(int argc, char **argv) {
          zultra_set_device(device = atoi(argv[++i]));
       else if (!strcmp(argv[i], "-f") && i + 1 < argc) {
          const char *f = argv[++i];
-         flags = !strcmp(f, "gzip") ? ZULTRA_FLAG_GZIP_FRAMING : !strcmp(f, "zlib") ? ZULTRA_FLAG_ZLIB_FRAMING : ZULTRA_FLAG_DEFLATE_FRAMING;
+         bgzf = !strcmp(f, "bgzf");
+         flags = !strcmp(f, "gzip") || bgzf ? ZULTRA_FLAG_GZIP_FRAMING : !strcmp(f, "zlib") ? ZULTRA_FLAG_ZLIB_FRAMING : ZULTRA_FLAG_DEFLATE_FRAMING;
       }
       else if (!strcmp(argv[i], "-D") && i + 1 < argc)
          dict_name = argv[++i];
@@ -121,10 +165,15 @@ int main(int argc, char **argv) {
       else
          break;
    }
-   if (argc - i != 2 || chunk == 0 || (members && (!do_extract || flags != ZULTRA_FLAG_GZIP_FRAMING || dict_name))) {
+   if (bgzf && !do_extract && block > ZULTRA_HIP_BGZF_BLOCK) {
+      fprintf(stderr, "-b %u: a BGZF block holds at most %u bytes of input\n", block, ZULTRA_HIP_BGZF_BLOCK);
+      return 100;
+   }
+   if (argc - i != 2 || chunk == 0 || (members && (!do_extract || flags != ZULTRA_FLAG_GZIP_FRAMING || dict_name)) || (bgzf && !do_extract && dict_name)) {
       fprintf(stderr, "usage: %s [-b <max block size>] [-f gzip|zlib|raw] [-k <chunk KiB>] [-d <device>] [-D <dictionary>] [-c] [-v] <infile> <outfile>\n"
                       "       %s -x [-f gzip|zlib|raw] [-d <device>] [-D <dictionary>] [-v] <infile> <outfile>\n"
-                      "       %s -x -m [-f gzip] [-d <device>] [-v] <infile> <outfile>   (any number of gzip members: BGZF, pigz -i, cat a.gz b.gz)\n", argv[0], argv[0], argv[0]);
+                      "       %s -x -m [-f gzip] [-d <device>] [-v] <infile> <outfile>   (any number of gzip members: BGZF, pigz -i, cat a.gz b.gz)\n"
+                      "       %s -f bgzf [-b <block size, at most 65280>] [-d <device>] [-c] [-v] <infile> <outfile>   (BGZF members and the end marker)\n", argv[0], argv[0], argv[0], argv[0]);
       return 100;
    }
    void *dict = NULL;
@@ -151,6 +200,12 @@ int main(int argc, char **argv) {
       fclose(fout);
       zultra_dictionary_free(&dict);
       return xrc;
+   }
+   if (bgzf) {
+      const int brc = write_bgzf(fin, fout, block, verbose, verify);
+      fclose(fin);
+      fclose(fout);
+      return brc;
    }
    unsigned char *in = (unsigned char *)malloc(chunk), *out = (unsigned char *)malloc(chunk);
    zultra_stream_t strm;

@@ -131,6 +131,11 @@ typedef struct zultra_hip_stats_s {
 } zultra_hip_stats_t;
 void zultra_hip_last_stats(const zultra_hip_ctx_t *ctx, zultra_hip_stats_t *out);
 
+/* Diagnostics: the matchfinder's chunk size in this context for a segment window of window_size bytes (history + block + look-ahead) — a bigram class of
+ * that many positions or more is refined through device memory by a kernel of its own, from a note —, and in *max_notes (may be NULL) how many such
+ * classes one segment's note table holds. 0 without a context. */
+uint32_t zultra_hip_mf_chunk(const zultra_hip_ctx_t *ctx, uint32_t window_size, uint32_t *max_notes);
+
 /* Diagnostics: with ZULTRA_HIP_CHAIN_TRACE=1 in the environment when the context is created, the chain kernels record per work
  * ticket {positions, start, end} on the device's 100 MHz clock; out = uint64[4 runs][4 passes][*slots][3]. Returns 0, or -1 when
  * tracing is off. */

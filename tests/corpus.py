@@ -174,6 +174,24 @@ def duplicated(size, seed=1, edit_gap=400):
     return np.concatenate(out)[:size]
 
 
+def phrase_edits(size, seed, period=64, gap=(40, 90), alphabet=None):
+    """One phrase of `period` DISTINCT byte values tiled to `size`, with one byte replaced every gap[0]..gap[1] positions by a value
+    outside the phrase: exactly `period` deep bigram classes and no byte runs, everything within reach of everything, matches that end
+    at the next edit (40 to 90 bytes: past the 16- and 32-byte steps of the matchfinder's extension). Between `periodic` (exact) and
+    `duplicated` (edits hundreds of bytes apart). alphabet: the byte values to draw phrase and edits from (default: all 256)."""
+    rs = np.random.RandomState(seed)
+    values = np.arange(256, dtype=np.uint8) if alphabet is None else np.unique(np.asarray(alphabet, dtype=np.uint8))
+    assert 0 < period < len(values), "the edits need a value outside the phrase"
+    values = rs.permutation(values)
+    phrase, outside = values[:period], values[period:]
+    d = np.resize(phrase, size)
+    at = int(rs.randint(gap[0], gap[1] + 1))
+    while at < size:
+        d[at] = outside[int(rs.randint(0, len(outside)))]
+        at += int(rs.randint(gap[0], gap[1] + 1))
+    return d
+
+
 def table_like(size, seed=1):
     """Lines of a generated table — a fixed frame around a counter, a code and a few words from a small vocabulary (the codec
     tables among the bench's Python sources look like this): medium matches overlap without a gap for thousands of positions,

@@ -110,7 +110,7 @@ EXPORTS = [
     "zultra_hip_stitch", "zultra_hip_stitch_finish",
     "zultra_hip_stitch_device", "zultra_hip_stitch_phase_table", "zultra_hip_stream_device", "zultra_hip_stream_read", "zultra_hip_block_crc32", "zultra_crc32_append", "zultra_crc32_append_many",
     "zultra_hip_create_files", "zultra_hip_compress_files", "zultra_hip_stitch_files", "zultra_hip_staging",
-    "zultra_hip_block_adler32", "zultra_adler32_append", "zultra_hip_copy_bandwidth", "zultra_hip_last_stats",
+    "zultra_hip_block_adler32", "zultra_adler32_append", "zultra_hip_copy_bandwidth", "zultra_hip_last_stats", "zultra_hip_mf_chunk",
     "zultra_hip_ctx_info", "zultra_hip_context_bytes", "zultra_hip_context_bytes_on", "zultra_release_cached_contexts", "zultra_hip_chain_trace", "zultra_hip_cut_tasks", "zultra_hip_stitch_with_batch",
     # verification
     "zultra_set_verify", "zultra_verified_bytes", "zultra_hip_verify_device", "zultra_hip_last_verify_ms", "zultra_hip_stream_write",
@@ -599,6 +599,14 @@ class HipContext:
         self.lib.L.zultra_hip_last_stats.restype = None
         self.lib.L.zultra_hip_last_stats(self.h, C.byref(st))
         return {k: getattr(st, k) for k, _ in Stats._fields_}
+
+    def mf_chunk(self, window_size):
+        """-> (the matchfinder's chunk size for a segment window of window_size bytes, the notes a segment's table holds): zultra_hip_mf_chunk."""
+        notes = C.c_uint32(0)
+        self.lib.L.zultra_hip_mf_chunk.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
+        self.lib.L.zultra_hip_mf_chunk.restype = C.c_uint32
+        cap = self.lib.L.zultra_hip_mf_chunk(self.h, window_size, C.byref(notes))
+        return int(cap), int(notes.value)
 
     def matches(self, block):
         n = int(self._block_n[block])

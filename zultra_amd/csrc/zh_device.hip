@@ -7,7 +7,7 @@
 //   d_blocks   B * 16                max-block descriptors;  d_segs  B * S * 32  matchfinder segments
 //   d_sort_a/b B * S * Ws * 4  each  window positions in trigram / 4-gram-hash order (ping-pong of the radix sorts)
 //   d_prev3    B * S * Ws * 8        previous occurrence of the trigram, 4-gram and 5-gram at every window position
-//   d_runs     B * S * (Ws + 576) * 4  byte-run table of every segment window
+//   d_runs     B * S * (Ws + 576) * 4  byte-run table of every segment window, behind it the notes for zh_mf_group_big (more than 576 with a small ZULTRA_HIP_MF_CAP: zh_mf_run_stride)
 //   d_match    B * N * 32            match rows, 8 x {u16 length, u16 offset} per block position
 //   d_tok_pos  B * N * 4, d_tok_info B * N * 2   greedy token chain: position / packed symbols
 //   d_bars     B * N / 8             barrier bitmap of every max-block (zh_parse.h)
@@ -680,6 +680,9 @@ static int zh_env_lanes(void) {
    return streams > 0 ? min(streams, (int)ZH_MAX_RUNS) : 4;
 }
 
+// ZULTRA_HIP_MF_CAP: elements per chunk of zh_mf_group's refinement in LDS (zh_mf_group_lds.h), 16 at least (less is taken as 16)
+static uint32_t zh_env_mf_cap(void) { return (uint32_t)max((int)ZH_MFL_MINCAP, zh_env("ZULTRA_HIP_MF_CAP", (int)ZH_MFL_CAP_LIMIT)); }
+
 static int zh_create_buffers(zultra_hip_ctx_t *c) {
    const uint64_t B = c->max_blocks, N = c->max_block;
    ZH_CHECK(c, hipSetDevice(c->device));
@@ -732,7 +735,14 @@ static int zh_create_buffers(zultra_hip_ctx_t *c) {
       c->lane_bundles = zh_env("ZULTRA_HIP_LANE_BUNDLES", 1) != 0;     // 0: no bundle lists are kept, zh_parse_lanes takes consecutive tasks of the task list as it did before bundles (the A/B of the bundles)
       c->lane_tasks = (uint32_t)min(max(0, zh_env("ZULTRA_HIP_LANE_TASKS", 0)), (int)ZH_LP_TASKS);   // tasks per bundle; 0: by the run's size (zh_tasks_per_wave: one below a chip's worth of tasks)
       c->seg_wide = (uint32_t)zh_env("ZULTRA_HIP_SEG_WIDE", 1024);     // a run with at least this many segments parses them in the segment workgroups of zh_parse_lanes' launch
-      c->mf_lds_cap = (uint32_t)max(0, zh_env("ZULTRA_HIP_MF_CAP", (int)ZH_MFL_CAP_LIMIT));   // elements per chunk of zh_mf_group's refinement in LDS (zh_mf_group_lds.h)
+      // the chunk size of zh_mf_group, and the segments' note tables sized for it: every class the chunks cannot take has its note, whatever the value (with the
+      // default: 29 notes in run tables of sort_stride + 576 words; zh_mf_group_lds.h has the bound)
+      c->mf_lds_cap = zh_env_mf_cap();
+      c->run_stride = zh_mf_run_stride(c->sort_stride, c->mf_lds_cap);
+      if (zh_mfl_note_room(c->sort_stride, c->run_stride) < c->seg_W / zh_mfl_cap(c->seg_W, c->mf_lds_cap)) {
+         snprintf(c->err, sizeof(c->err), "matchfinder note table too small for chunks of %u", c->mf_lds_cap);
+         return -1;
+      }
       const int streams = zh_env("ZULTRA_HIP_STREAMS", 0);              // staggered runs per batch; not set: three, four for batches of 256 MiB and more
       c->nlanes = zh_env_lanes();
       c->auto_runs = streams > 0 ? 0 : 1;   // (measured with the stagger below, runs = 2 / 3 / 4 / 6: 100 MB of real text 49.8 / 49.6 / 51.2 / - ms; configuration 3
@@ -839,7 +849,7 @@ static zultra_hip_ctx_t *zh_create(int device, uint32_t max_block, uint32_t max_
       c->seg_W = ZH_SEG_WINDOW;
    }
    c->sort_stride = ((uint64_t)c->seg_W + 63) & ~63ull;
-   c->run_stride = c->sort_stride + 576;   // start[Q] length[Q] first[256] end[256] count, Q = W/4 + 1
+   // (run_stride — start[Q] length[Q] first[256] end[256] count, Q = W/4 + 1, and the notes for zh_mf_group_big — follows from the chunk size: zh_create_buffers)
    c->match_stride = (uint64_t)c->max_block * ZH_NMATCH;
    c->tok_stride = ((uint64_t)c->max_block + 63) & ~63ull;
    c->chunks_per_block = (c->max_block + ZH_TOK_CHUNK_SMALL - 1) / ZH_TOK_CHUNK_SMALL;   // (what the per-chunk arrays hold: the small chunks of a small batch)
@@ -899,7 +909,7 @@ extern "C" size_t zultra_hip_context_bytes_on(int device, uint32_t max_block_siz
    const uint64_t W = N + ZH_HISTORY;
    const uint64_t seg_W = W <= ZH_SEG_WINDOW ? W : (uint64_t)ZH_SEG_WINDOW;
    const uint64_t S = W <= ZH_SEG_WINDOW ? 1 : (N + ZH_SEG_POSITIONS - 1) / ZH_SEG_POSITIONS;
-   const uint64_t sort_stride = (seg_W + 63) & ~63ull, run_stride = sort_stride + 576, tok_stride = (N + 63) & ~63ull;
+   const uint64_t sort_stride = (seg_W + 63) & ~63ull, run_stride = zh_mf_run_stride(sort_stride, zh_env_mf_cap()), tok_stride = (N + 63) & ~63ull;
    const uint64_t slot_stride = ((N + 64 * ZH_MAX_SPLITS + 64) + 63) & ~63ull, cpb = (N + ZH_TOK_CHUNK_SMALL - 1) / ZH_TOK_CHUNK_SMALL;
    const uint64_t tasks = B * (N / ZH_TASK + ZH_MAX_SPLITS), subs = B * ZH_MAX_SPLITS;
    uint64_t bytes = 0;
@@ -1082,7 +1092,7 @@ static int zh_enqueue_run(zultra_hip_ctx_t *c, int k, uint32_t b0, uint32_t nb, 
       ZH_LAUNCH_LDS(zh_mf_group<true>, mf_grid, ZH_MF_THREADS, ZH_MF_GROUP_LDS, st, c->cur_data, sgs, sa, sb, p3, rn, c->sort_stride, c->run_stride, nsg, ctr + (size_t)nsg * 2 + 1, pay,
                     c->mf_lds_cap);
       // the bigram classes that fit no chunk of zh_mf_group, noted by it (zh_mf_group_lds.h): a kernel of their own (inputs of <= 4 KiB are one chunk: nothing is ever noted)
-      if (c->mf_lds_cap && c->seg_W > (files ? (uint32_t)ZH_MFL_MAXCAP : min((uint32_t)ZH_MFL_MAXCAP, max(c->mf_lds_cap, 16u))))
+      if (c->seg_W > zh_mfl_cap(c->seg_W, c->mf_lds_cap))   // (a smaller window's chunks are no smaller)
          ZH_LAUNCH_LDS(zh_mf_group_big, files ? min(mf_grid, 32u) : mf_grid, ZH_MF_THREADS, ZH_MF_GROUP_LDS, st, c->cur_data, sgs, sa, sb, p3, (const uint32_t *)rn, c->sort_stride, c->run_stride, nsg,
                        ctr + (size_t)nsg * 2 + 2, pay);
    }
@@ -1970,6 +1980,12 @@ extern "C" int zultra_hip_cut_tasks(zultra_hip_ctx_t *c, uint32_t run, uint32_t 
    const uint32_t n = min(cap, c->h_ntasks[(size_t)run * ZH_CNT_STRIDE + ZH_CNT_SEGTASKS]);
    if (out && n) ZH_CHECK(c, hipMemcpy(out, c->d_segtasks + (uint64_t)c->last_run_b0[run] * c->seg_tasks_per_block, (size_t)n * sizeof(uint4), hipMemcpyDeviceToHost));
    return (int)n;
+}
+
+extern "C" uint32_t zultra_hip_mf_chunk(const zultra_hip_ctx_t *c, uint32_t window_size, uint32_t *max_notes) {
+   if (!c) return 0;
+   if (max_notes) *max_notes = zh_mfl_note_room(c->sort_stride, c->run_stride);
+   return zh_mfl_cap(min(window_size, (uint32_t)ZH_SEG_WINDOW), c->mf_lds_cap);
 }
 
 extern "C" void zultra_hip_last_stats(const zultra_hip_ctx_t *c, zultra_hip_stats_t *out) {

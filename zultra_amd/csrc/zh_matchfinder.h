@@ -383,7 +383,8 @@ __device__ inline void zh_mf_sort_pass(const uint8_t *gwin, uint32_t M, const ui
 // of such positions is therefore computed from a table of the window's runs (zh_mf_frontier), not from the class scan.
 // Table layout per max-block (u32, Q = W/4 + 1): start[Q] grouped by byte value and ascending within a byte, length[Q]
 // in the same order, then first[256] / end[256] (slice of each byte value) and the run count; then the same runs in a second
-// order (zh_mf_build_runs): start | following byte << 24 [Q], length [Q]. 4 Q + 513 words <= the window size + 576.
+// order (zh_mf_build_runs): start | following byte << 24 [Q], length [Q]. 4 Q + 513 words <= the window size + 517 (ZH_MF_RUN_WORDS);
+// behind them, in the same run_stride words, the notes for zh_mf_group_big (zh_mf_group_lds.h: zh_mf_run_stride).
 #define ZH_RUN_MIN 4
 __device__ __forceinline__ uint32_t zh_runs_q(uint32_t W) { return W / 4 + 1; }
 
@@ -509,8 +510,8 @@ zh_mf_group(const uint8_t *__restrict__ data, const zh_seg_t *__restrict__ segs,
    uint2 *prev3 = prev_all + (uint64_t)seg * sort_stride;
    uint32_t *runs = runs_all + (uint64_t)seg * run_stride;
    if (LDS_WIN) zh_stage_window(lwin32, win, W);
-   zh_mf_group_body_lds(dyn_lds, W, blk.prev + blk.n, A, B, prev3, pay_all + (uint64_t)blockIdx.x * 3u * sort_stride, sort_stride, runs, runs + run_stride - ZH_MFL_NOTE_WORDS, hist, wave_tot,
-                        lds_cap);
+   zh_mf_group_body_lds(dyn_lds, W, blk.prev + blk.n, A, B, prev3, pay_all + (uint64_t)blockIdx.x * 3u * sort_stride, sort_stride, runs, runs + sort_stride + ZH_MF_RUN_WORDS,
+                        zh_mfl_note_room(sort_stride, run_stride), hist, wave_tot, lds_cap);
    }
 }
 
@@ -532,7 +533,7 @@ zh_mf_group_big(const uint8_t *__restrict__ data, const zh_seg_t *__restrict__ s
          uint32_t sg;
          do {
             sg = atomicAdd(ticket, 1u);
-         } while (sg < nsegs && (runs_all + (uint64_t)sg * run_stride + run_stride - ZH_MFL_NOTE_WORDS)[0] == 0);
+         } while (sg < nsegs && (runs_all + (uint64_t)sg * run_stride + sort_stride + ZH_MF_RUN_WORDS)[0] == 0);
          cur_seg = sg;
       }
       __syncthreads();
@@ -540,7 +541,7 @@ zh_mf_group_big(const uint8_t *__restrict__ data, const zh_seg_t *__restrict__ s
       if (seg >= nsegs) return;
       const zh_seg_t blk = segs[seg];
       const uint32_t W = blk.prev + blk.n + blk.tail;
-      const uint32_t *notes = runs_all + (uint64_t)seg * run_stride + run_stride - ZH_MFL_NOTE_WORDS;
+      const uint32_t *notes = runs_all + (uint64_t)seg * run_stride + sort_stride + ZH_MF_RUN_WORDS;
       zh_stage_window(lwin32, data + blk.win_off, W);
       const uint32_t nn = notes[0];
       for (uint32_t k = 0; k < nn; k++) {

@@ -28,12 +28,44 @@
 #ifndef ZH_MFL_CAP_LIMIT
 #define ZH_MFL_CAP_LIMIT ZH_MFL_MAXCAP   // (the emulator build takes a small one: several chunks and oversized classes in a window of a few KB)
 #endif
-#define ZH_MFL_NOTE_WORDS 59u        // the run table's slack: run_stride = sort_stride + 576 words, zh_mf_build_runs writes at most W + 517
-#define ZH_MFL_MAX_NOTES ((ZH_MFL_NOTE_WORDS - 1u) / 2u)   // 29: a class above `cap` (~3900 of at most 98304 entries) happens at most 25 times
+#define ZH_MFL_MINCAP 16u          // what the layout takes at least, whatever the caller's limit
 #define ZH_MF_LDS_TOTAL 163840u    // all of a CU's LDS: one workgroup per CU anyway (1024 threads)
 static_assert(ZH_SEG_WINDOW <= (1u << ZH_MFL_ID_SHIFT), "window positions must fit the element's position field");
 static_assert(ZH_MFL_MAXCAP <= (1u << (32 - ZH_MFL_ID_SHIFT)), "chunk ids must fit the element's id field");
 static_assert(ZH_MFL_MAXCAP <= ZH_MF_WAVES * 256u, "a wave takes at most four steps of 64 elements of a chunk");
+
+// words of dynamic LDS in front of a chunk's arrays next to a window of W bytes (zh_mfl_layout), and the elements those arrays then hold
+ZH_HD constexpr uint32_t zh_mfl_front_words(uint32_t W) { return (((W + 16u + 15u) >> 4) << 2) + ZH_MF_WAVES * 128u + 256u + 256u + 8u; }
+ZH_HD constexpr uint32_t zh_mfl_room(uint32_t W) { return (((ZH_MF_LDS_TOTAL / 4u - zh_mfl_front_words(W)) * 2u) / 7u) & ~15u; }   // X, Y, D34: a word each; D5: half a word
+// the chunk size of a window: what the layout leaves, the hardware's steps, and the caller's limit (ZULTRA_HIP_MF_CAP)
+ZH_HD constexpr uint32_t zh_mfl_cap(uint32_t W, uint32_t cap_limit) {
+   const uint32_t room = zh_mfl_room(W) < ZH_MFL_MAXCAP ? zh_mfl_room(W) : ZH_MFL_MAXCAP, lim = cap_limit > ZH_MFL_MINCAP ? cap_limit : ZH_MFL_MINCAP;
+   return room < lim ? room : lim;
+}
+
+// The notes for zh_mf_group_big. INVARIANT: every bigram class that zh_mf_group_body_lds does not refine itself — a class of `cap` entries or more, cap =
+// zh_mfl_cap(W, limit) — is noted and refined by zh_mf_group_big; none is dropped. A segment's notes lie behind its run table: zh_mf_build_runs writes at most
+// W + 517 words (4 Q + 513, Q = W / 4 + 1) and W <= sort_stride, so the note table starts at word sort_stride + ZH_MF_RUN_WORDS of the segment's run_stride words:
+// a count, then two words per note. How many notes a window can need: its bigram order has at most W <= ZH_SEG_WINDOW entries, so at most W / cap classes reach cap.
+//  - The limit does not bind (cap = the layout's room, which shrinks as W grows: zh_mfl_room(ZH_SEG_WINDOW) = 3936 at least): at most 98304 / 3936 = 24 classes.
+//    ZH_MFL_MIN_NOTES = 29 covers them (the static_assert below), in the 59 words that a run_stride of sort_stride + 576 leaves: the default configuration.
+//  - The limit binds (a small ZULTRA_HIP_MF_CAP; the emulator build's compiled 512): at most ZH_SEG_WINDOW / max(limit, 16) classes — 192 for 512, 6144 for 16.
+// zh_mfl_max_notes(limit) is the larger of the two; the context sizes run_stride by it when it is created (zh_mf_run_stride) and the kernels take the table's size from
+// the two strides (zh_mfl_note_room), so host and device cannot disagree. A note packs the class's start in the bigram order and where its entries go (17 bits each,
+// window positions) with its size (15 + 15 bits): nothing in it depends on how many notes there are.
+#define ZH_MF_RUN_WORDS 517u
+#define ZH_MFL_MIN_NOTES 29u
+ZH_HD constexpr uint32_t zh_mfl_max_notes(uint32_t cap_limit) {
+   const uint32_t lim = cap_limit > ZH_MFL_MINCAP ? cap_limit : ZH_MFL_MINCAP, n = ZH_SEG_WINDOW / lim;
+   return n > ZH_MFL_MIN_NOTES ? n : ZH_MFL_MIN_NOTES;
+}
+ZH_HD constexpr uint64_t zh_mf_run_stride(uint64_t sort_stride, uint32_t cap_limit) { return sort_stride + ZH_MF_RUN_WORDS + 1u + 2u * zh_mfl_max_notes(cap_limit); }
+ZH_HD constexpr uint32_t zh_mfl_note_room(uint64_t sort_stride, uint64_t run_stride) { return (uint32_t)((run_stride - sort_stride - ZH_MF_RUN_WORDS - 1u) / 2u); }
+static_assert(ZH_SEG_WINDOW / zh_mfl_cap(ZH_SEG_WINDOW, ZH_MFL_MAXCAP) <= ZH_MFL_MIN_NOTES, "a window's classes above the layout's own chunk size must fit the smallest note table");
+static_assert(zh_mfl_room(ZH_SEG_WINDOW) >= ZH_MFL_MINCAP, "the largest window must leave room for a chunk");
+static_assert(zh_mf_run_stride(0, ZH_MFL_MAXCAP) == 576u && zh_mfl_note_room(0, 576u) == ZH_MFL_MIN_NOTES, "the default configuration's run tables: sort_stride + 576 words, 29 notes");
+static_assert(zh_mfl_note_room(0, zh_mf_run_stride(0, ZH_MFL_MINCAP)) == ZH_SEG_WINDOW / ZH_MFL_MINCAP, "the note table of the smallest chunk size");
+static_assert(ZH_SEG_WINDOW <= (1u << 17) && ZH_SEG_WINDOW < (1u << 30), "a note's start, destination (17 bits) and size (30 bits)");
 
 struct zh_mfl_t {
    uint16_t *hist;   // [wave][256]: digit counts of the wave's stretch, then where its elements of that digit go
@@ -58,9 +90,7 @@ __device__ __forceinline__ zh_mfl_t zh_mfl_layout(uint32_t *dyn_lds, uint32_t W,
    p += 256;
    L.misc = p;
    p += 8;
-   const uint32_t avail = ZH_MF_LDS_TOTAL / 4u - (uint32_t)(p - dyn_lds);
-   uint32_t cap = ((avail * 2u) / 7u) & ~15u;   // X, Y, D34: a word each; D5: half a word
-   cap = min(cap, min((uint32_t)ZH_MFL_MAXCAP, max(cap_limit, 16u)));
+   const uint32_t cap = zh_mfl_cap(W, cap_limit);   // (p - dyn_lds = zh_mfl_front_words(W))
    L.cap = cap;
    L.X = p;
    p += cap;
@@ -257,7 +287,8 @@ __device__ inline uint32_t zh_mfl_oversized(const uint8_t *gwin, uint32_t W, uin
 
 // the window is staged in LDS at dyn_lds (W bytes); SA receives the 6-gram order, prev the distances next to it
 __device__ inline void zh_mf_group_body_lds(uint32_t *dyn_lds, uint32_t W, uint32_t Qn, uint32_t *SA, uint32_t *SB, uint2 *prev, uint32_t *pay,
-                                            uint64_t pay_stride, uint32_t *runs, uint32_t *notes /* ZH_MFL_NOTE_WORDS words behind the run table */, uint32_t *hist, uint32_t *wave_tot, uint32_t cap_limit) {
+                                            uint64_t pay_stride, uint32_t *runs, uint32_t *notes /* behind the run table: a count and room for max_notes notes */, uint32_t max_notes, uint32_t *hist, uint32_t *wave_tot,
+                                            uint32_t cap_limit) {
    const uint32_t *lwin32 = dyn_lds;
    const uint8_t *gwin = (const uint8_t *)dyn_lds;
    const uint32_t tid = threadIdx.x;
@@ -339,7 +370,9 @@ __device__ inline void zh_mf_group_body_lds(uint32_t *dyn_lds, uint32_t W, uint3
             uint32_t nv = n0;
             for (uint32_t pl = (W >= 5 ? W - 5 : 0u); pl < min(W, Qn); pl++)
                if (pl + 2u < W && (zh_load32_at(lwin32, pl) & 0xffffu) == big0 && !zh_mf_run_interior(gwin, pl, W)) nv--;
-            if (tid == 0 && nover < ZH_MFL_MAX_NOTES) {
+            // (max_notes >= W / cap by the context's sizing of the table, zh_mfl_max_notes: the bound never binds; it is kept so that a table that is too small
+            // anyhow — strides of another configuration — is not written past its end)
+            if (tid == 0 && nover < max_notes) {
                uint32_t *note = notes + 1u + 2u * nover;
                note[0] = s | (n0 << 17);            // start (17 bits) | low 15 bits of the size
                note[1] = out_base | ((n0 >> 15) << 17);   // where its entries go | the size's high bits
@@ -380,5 +413,5 @@ __device__ inline void zh_mf_group_body_lds(uint32_t *dyn_lds, uint32_t W, uint3
    __threadfence_block();
    __syncthreads();
    zh_mf_build_runs(gwin, W, Qn, pay, runs, hist, wave_tot);   // (scratch for the run starts: the workgroup's `pay` — SB still holds the bigram order of the classes noted for zh_mf_group_big)
-   if (tid == 0) notes[0] = min(nover, (uint32_t)ZH_MFL_MAX_NOTES);   // (behind what zh_mf_build_runs writes)
+   if (tid == 0) notes[0] = min(nover, max_notes);   // (behind what zh_mf_build_runs writes)
 }

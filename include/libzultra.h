@@ -187,6 +187,24 @@ size_t zultra_memory_compress_bgzf(const unsigned char *pIn, size_t nIn, unsigne
 size_t zultra_memory_compress_batch(const unsigned char *pIn, size_t nIn, const size_t *pInOff, const size_t *pInSize, size_t n,
                                     unsigned char *pOut, size_t nMaxOut, size_t *pOutOff /* n + 1, written */, const unsigned int nFlags /* 0, ZLIB, GZIP */);
 
+/* A complete ZIP archive of n named inputs: input i, pIn + pInOff[i] .. + pInSize[i], is the entry named pNames + pNameOff[i] .. pNameOff[i + 1] (1 .. 65535
+ * bytes of UTF-8, given as they are). The inputs are grouped into device batches exactly as zultra_memory_compress_batch groups them; local headers, names,
+ * streams and central directory records are laid out on the device (include/zultra_hip.h: zultra_hip_zip_members), a batch's local part is read to its place in
+ * pOut, the central parts follow the last batch, then the end records. Entry i's data is byte for byte zultra_memory_compress(input i,
+ * ZULTRA_FLAG_DEFLATE_FRAMING, a max-block size >= its size): method 8 always, also where stored would be a few bytes shorter. An input of size 0 is an EMPTY
+ * entry — a zero-length file, or a directory where its name ends in '/': method 0 — and is not refused. nDosDateTime: date << 16 | time for every entry,
+ * 0 = 1980-01-01 00:00:00. No extra fields, comments or attributes: the archive is a function of its inputs. Returns the bytes written, or (size_t)-1: bad
+ * arguments, an input above 2 MiB (ONE max-block), a name of 0 or above 65535 bytes, nMaxOut too small (zultra_memory_bound_zip is enough), an archive that
+ * reaches 0xFFFFFFFF bytes (ZIP64 fields per entry are not written), a device failure, no device. One device; with zultra_set_verify every batch is verified. */
+size_t zultra_memory_bound_zip(size_t nInTotal, size_t nNamesTotal, size_t n);
+size_t zultra_memory_compress_zip(const unsigned char *pIn, size_t nIn, const size_t *pInOff, const size_t *pInSize,
+                                  const char *pNames, const size_t *pNameOff /* n + 1 */, size_t n,
+                                  unsigned char *pOut, size_t nMaxOut, unsigned int nDosDateTime);
+/* The end of a ZIP archive, for callers who assemble one from the device layer's parts: the end of central directory record (22 bytes), and in front of it, with
+ * more than 65535 entries, the ZIP64 end record and its locator (98 bytes in all). Pure host code. Returns the bytes written, or (size_t)-1: nMaxOut too small,
+ * or nCentralOff or nCentralSize at or above 0xFFFFFFFF. */
+size_t zultra_zip_end_records(unsigned char *pOut, size_t nMaxOut, unsigned long long nEntries, unsigned long long nCentralOff, unsigned long long nCentralSize);
+
 #ifdef __cplusplus
 }
 #endif

@@ -383,6 +383,35 @@ int zultra_hip_frame_members(zultra_hip_ctx_t *ctx, unsigned int framing, int bg
  * HIP events on the context's stream — the scan with the clearing behind it, the bit mover, the frame kernel. */
 void zultra_hip_last_frame_ms(const zultra_hip_ctx_t *ctx, float *ms /* [3] */);
 
+/*
+ * A ZIP archive's entries: the max-blocks of the last batch of ANY context as entries of a ZIP archive, written on the device into a
+ * second, context-owned buffer (zultra_hip_zip_device / zultra_hip_zip_read) — a gather behind the plain files-form assembly. The buffer holds the LOCAL
+ * PART, per entry {30-byte local header, name, the raw deflate stream exactly as zultra_hip_stitch_files lays it out}, and behind it at a 16-byte aligned
+ * position (central_at) the CENTRAL PART, per entry {46-byte central header, name}. An archive is the local parts of its batches, their central parts,
+ * and the end records of zultra_zip_end_records (libzultra.h).
+ *   names, name_off : entry i is named names + name_off[i] .. name_off[i + 1], 1 .. 65535 bytes of UTF-8 (general purpose flag 0x0800 is set)
+ *   entry_block     : the max-block of entry i, or 0xFFFFFFFF for an EMPTY entry — a zero-length file or a directory: method 0, sizes 0, CRC 0, version
+ *                     needed 10. The max-blocks named are every max-block of the batch, once each, in increasing order. NULL: entry i is max-block i, n of them
+ *   base_off        : where this local part will stand in the archive: what the central headers' offsets and entries[].local_off count from
+ *   dos_datetime    : date << 16 | time for every entry; 0 = 1980-01-01 00:00:00 (0x00210000)
+ *   entries         : host, n, may be NULL: offset of the local header, sizes, CRC-32 and name length as written (as found where the call fails)
+ * Other entries are method 8, version needed 20; no extra fields, no comments, attributes 0. The stream buffer must hold the plain files form of the batch:
+ * a files context's batch brings it, zultra_hip_stitch_files makes it; where it is absent (no assembly yet, framed members since) the call runs that assembly
+ * first. Otherwise the stream buffer is not written: zultra_hip_verify_device, zultra_hip_stitch_files and zultra_hip_frame_members behave as before the call.
+ * Returns 0; -1 for bad arguments (no batch, a max-block with history, a name of length 0 or above 65535, an entry_block that is not the batch's max-blocks
+ * once each in increasing order) and HIP errors; -2 where the assembly fails as zultra_hip_stitch_files does, or base_off + local_bytes + central_bytes reaches
+ * 0xFFFFFFFF (sizes and offsets from there on need ZIP64 fields per entry, which are not written). A refused call writes nothing.
+ */
+typedef struct zultra_hip_zip_entry_s { uint64_t local_off; uint32_t comp_size, size, crc32, name_len; } zultra_hip_zip_entry_t;
+int zultra_hip_zip_members(zultra_hip_ctx_t *ctx, const void *names, const uint32_t *name_off /* n + 1, host */,
+                           const uint32_t *entry_block /* n, host; NULL: entry i = max-block i */, uint32_t n,
+                           uint64_t base_off, uint32_t dos_datetime /* date << 16 | time; 0 = 1980-01-01 00:00:00, i.e. 0x00210000 */,
+                           zultra_hip_zip_entry_t *entries /* host, n; may be NULL */, uint64_t *local_bytes, uint64_t *central_bytes);
+const void *zultra_hip_zip_device(const zultra_hip_ctx_t *ctx, uint64_t *central_at);   /* the buffer; where the central part starts in it */
+int zultra_hip_zip_read(zultra_hip_ctx_t *ctx, void *out, size_t offset, size_t nbytes);
+/* A measurement hook (tools/zip_time.py): device time of the last zultra_hip_zip_members' launches, milliseconds. */
+void zultra_hip_last_zip_ms(const zultra_hip_ctx_t *ctx, float *ms /* [3]: scan, records, copy */);
+
 /* CRC-32 of every max-block of the last batch, computed on the device while the blocks are compressed: out[b] is the
  * linear part (zero initial state, no final inversion). zultra_crc32_append() folds one block into a running gzip CRC
  * exactly as zultra_frame_update_checksum(crc, block, len, GZIP) would (reference src/frame.c:324-354,473-480). */

@@ -93,6 +93,8 @@ class IndexResult(C.Structure):
 
 MEMBER_DTYPE = [("off", "<u8"), ("size", "<u8"), ("check", "<u4"), ("flags", "<u4")]   # zultra_hip_member_t
 FRAME_BGZF = 4   # ZULTRA_HIP_FRAME_BGZF
+ZIP_ENTRY_DTYPE = [("local_off", "<u8"), ("comp_size", "<u4"), ("size", "<u4"), ("crc32", "<u4"), ("name_len", "<u4")]   # zultra_hip_zip_entry_t
+ZIP_EMPTY = 0xFFFFFFFF   # entry_block: an empty entry (a zero-length file or a directory)
 MEMBER_RESULT_DTYPE = [("reason", "<u4"), ("blocks", "<u4"), ("out_size", "<u8"), ("src_used", "<u8"), ("head_size", "<u4"), ("check", "<u4")]
 
 
@@ -120,6 +122,9 @@ EXPORTS = [
     "zultra_hip_index_members", "zultra_hip_inflate_file", "zultra_memory_decompress_members",
     # framed members
     "zultra_hip_frame_members", "zultra_hip_last_frame_ms", "zultra_memory_bound_bgzf", "zultra_memory_compress_bgzf", "zultra_memory_compress_batch",
+    # ZIP archives
+    "zultra_hip_zip_members", "zultra_hip_zip_device", "zultra_hip_zip_read", "zultra_hip_last_zip_ms",
+    "zultra_zip_end_records", "zultra_memory_bound_zip", "zultra_memory_compress_zip",
 ]
 
 
@@ -397,6 +402,41 @@ class Lib:
         if r == _SIZE_MAX:
             return None, None
         return out[:r].tobytes(), [int(v) for v in out_off]
+
+    def zip_end_records(self, entries, central_off, central_size, cap=98):
+        """zultra_zip_end_records -> the end records of a ZIP archive (22 bytes, 98 with more than 65535 entries), or None where the call returns (size_t)-1."""
+        out = np.empty(max(cap, 1), dtype=np.uint8)
+        f = self.L.zultra_zip_end_records
+        f.argtypes = [C.c_void_p, C.c_size_t, C.c_ulonglong, C.c_ulonglong, C.c_ulonglong]
+        f.restype = C.c_size_t
+        r = f(out.ctypes.data, cap, entries, central_off, central_size)
+        return None if r == _SIZE_MAX else out[:r].tobytes()
+
+    def memory_bound_zip(self, in_total, names_total, n):
+        f = self.L.zultra_memory_bound_zip
+        f.argtypes = [C.c_size_t, C.c_size_t, C.c_size_t]
+        f.restype = C.c_size_t
+        return int(f(in_total, names_total, n))
+
+    def memory_compress_zip(self, data, inputs, names, dos_datetime=0, cap=None):
+        """zultra_memory_compress_zip over the inputs [(offset, size)] of `data`, entry i named names[i] (bytes, or str encoded as UTF-8; size 0: an empty
+        entry). -> the archive's bytes, or None where the call returns (size_t)-1. cap: bytes of room, default the bound."""
+        data = _as_u8(data)
+        n = len(inputs)
+        names = [s.encode("utf-8") if isinstance(s, str) else bytes(s) for s in names]
+        assert len(names) == n
+        blob = _as_u8(b"".join(names) + b"\0")
+        name_off = np.concatenate([[0], np.cumsum([len(s) for s in names])]).astype(np.uintp)
+        in_off = np.array([m[0] for m in inputs], dtype=np.uintp)
+        in_size = np.array([m[1] for m in inputs], dtype=np.uintp)
+        if cap is None:
+            cap = self.memory_bound_zip(int(in_size.sum()), int(name_off[-1]), n)
+        out = np.empty(max(cap, 1), dtype=np.uint8)
+        f = self.L.zultra_memory_compress_zip
+        f.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint]
+        f.restype = C.c_size_t
+        r = f(data.ctypes.data if len(data) else None, len(data), in_off.ctypes.data, in_size.ctypes.data, blob.ctypes.data, name_off.ctypes.data, n, out.ctypes.data, cap, dos_datetime)
+        return None if r == _SIZE_MAX else out[:r].tobytes()
 
     def checksum(self, data, flags, start=None):
         data = _as_u8(data)
@@ -700,6 +740,50 @@ class HipContext:
         """Device time of the last frame_members' launches, milliseconds: (scan, mover, frame kernel)."""
         ms = (C.c_float * 3)()
         f = self.lib.L.zultra_hip_last_frame_ms
+        f.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+        f.restype = None
+        f(self.h, ms)
+        return [float(v) for v in ms]
+
+    def zip_members(self, names, entry_block=None, base_off=0, dos_datetime=0):
+        """zultra_hip_zip_members over the last batch: names[i] (bytes, or str encoded as UTF-8) names entry i, which is max-block entry_block[i] of the
+        batch or, for ZIP_EMPTY, an empty entry; None: entry i is max-block i. -> (rc, entries as a ZIP_ENTRY_DTYPE array, local_bytes, central_bytes,
+        central_at); rc 0, or -1 / -2 as the call returns them."""
+        names = [s.encode("utf-8") if isinstance(s, str) else bytes(s) for s in names]
+        n = len(names)
+        blob = _as_u8(b"".join(names) + b"\0")
+        name_off = np.concatenate([[0], np.cumsum([len(s) for s in names])]).astype(np.uint32)
+        eb = None if entry_block is None else np.ascontiguousarray(entry_block, dtype=np.uint32)
+        entries = np.zeros(max(n, 1), dtype=ZIP_ENTRY_DTYPE)
+        local, central = C.c_uint64(0), C.c_uint64(0)
+        f = self.lib.L.zultra_hip_zip_members
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        f.restype = C.c_int
+        rc = f(self.h, blob.ctypes.data, name_off.ctypes.data, None if eb is None else eb.ctypes.data, n, base_off, dos_datetime, entries.ctypes.data, C.byref(local), C.byref(central))
+        return rc, entries[:n], int(local.value), int(central.value), self.zip_ptr()[1]
+
+    def zip_ptr(self):
+        """zultra_hip_zip_device -> (the device pointer of the zip buffer, or None before the first zip_members; where the central part starts in it)."""
+        at = C.c_uint64(0)
+        f = self.lib.L.zultra_hip_zip_device
+        f.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+        f.restype = C.c_void_p
+        return f(self.h, C.byref(at)), int(at.value)
+
+    def zip_read(self, nbytes, offset=0):
+        """-> uint8 array of the zip buffer's bytes [offset, offset + nbytes) (zultra_hip_zip_read)."""
+        out = np.empty(max(nbytes, 1), dtype=np.uint8)
+        f = self.lib.L.zultra_hip_zip_read
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t]
+        f.restype = C.c_int
+        if f(self.h, out.ctypes.data, offset, nbytes) != 0:
+            raise ZultraError("zip_read")
+        return out[:nbytes]
+
+    def last_zip_ms(self):
+        """Device time of the last zip_members' launches, milliseconds: (scan, records, copy)."""
+        ms = (C.c_float * 3)()
+        f = self.lib.L.zultra_hip_last_zip_ms
         f.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
         f.restype = None
         f(self.h, ms)

@@ -1152,19 +1152,26 @@ extern "C" size_t zultra_memory_compress_bgzf(const unsigned char *pIn, size_t n
    return (size_t)-1;
 }
 
-// Consecutive inputs of one kind — below 8192 bytes: a files context; from there on: a context of max-blocks as large as the call's largest input — share
-// a batch, as many as the context takes; a batch's inputs are gathered into the context's pinned staging and its members read to where they belong in pOut.
-extern "C" size_t zultra_memory_compress_batch(const unsigned char *pIn, size_t nIn, const size_t *pInOff, const size_t *pInSize, size_t n, unsigned char *pOut, size_t nMaxOut,
-                                               size_t *pOutOff, const unsigned int nFlags) try {
+// The batches of n independent inputs, under zultra_memory_compress_batch and zultra_memory_compress_zip. Consecutive inputs of one kind — below 8192 bytes: a
+// files context; from there on: a context of max-blocks as large as the call's largest input — share a batch, as many as the context takes; a batch's inputs are
+// gathered into the context's pinned staging, max-block k at blocks[k].win_off, and per_batch(context, staging, bytes, blocks, i, j) does the rest for the inputs
+// i .. j - 1. An input of size 0 is refused unless allow_empty; then it is no max-block and rides with the batch it sits in or next to (behind, where there is
+// one): per_batch finds it by its size. A call of empty inputs only has no batch. Returns false where anything fails.
+template <typename F>
+static bool for_input_batches(const unsigned char *pIn, size_t nIn, const size_t *pInOff, const size_t *pInSize, size_t n, bool allow_empty, F per_batch) {
    const size_t small_limit = 8192;
-   if (!pIn || !pInOff || !pInSize || !n || !pOut || !pOutOff || (nFlags != 0 && nFlags != ZULTRA_FLAG_ZLIB_FRAMING && nFlags != ZULTRA_FLAG_GZIP_FRAMING) || zultra_hip_device_count() <= 0)
-      return (size_t)-1;
-   size_t largest = 0, nsmall = 0;
+   size_t largest = 0, nsmall = 0, nempty = 0;
    for (size_t i = 0; i < n; i++) {
-      if (!pInSize[i] || pInSize[i] > nIn || pInOff[i] > nIn - pInSize[i] || pInSize[i] > 2097152) return (size_t)-1;   // (an empty input is refused, as by zultra_memory_compress; a member is ONE max-block)
+      if (!pInSize[i] && allow_empty) {
+         nempty++;
+         continue;
+      }
+      if (!pInSize[i] || pInSize[i] > nIn || pInOff[i] > nIn - pInSize[i] || pInSize[i] > 2097152) return false;   // (an empty input is refused, as by zultra_memory_compress; a member is ONE max-block)
       largest = pInSize[i] > largest ? pInSize[i] : largest;
       nsmall += pInSize[i] < small_limit;
    }
+   if (nempty == n) return true;
+   const size_t nlarge = n - nempty - nsmall;
    const int dev = zh_pick_device();
    struct Ctxs {   // (the files context is this call's own: the cache keeps contexts of max-blocks)
       zultra_hip_ctx_t *files = NULL, *blocks = NULL;
@@ -1174,39 +1181,168 @@ extern "C" size_t zultra_memory_compress_batch(const unsigned char *pIn, size_t 
       }
    } C;
    uint32_t files_cap = (uint32_t)(nsmall < 65536 ? nsmall : 65536);
-   const uint32_t ctx_bs = zh_clamp_block((uint32_t)largest), blocks_cap = n - nsmall ? ctx_blocks(dev, ctx_bs, n - nsmall) : 0;
+   const uint32_t ctx_bs = zh_clamp_block((uint32_t)largest), blocks_cap = nlarge ? ctx_blocks(dev, ctx_bs, nlarge) : 0;
    // (a files context for fewer inputs per batch where the device has no room for the large one: down to 256, which is 10 MB or so)
    while (nsmall && !(C.files = zultra_hip_create_files(dev, (uint32_t)small_limit - 1, files_cap))) {
-      if (files_cap <= 256) return (size_t)-1;
+      if (files_cap <= 256) return false;
       files_cap = files_cap / 4 < 256 ? 256 : files_cap / 4;
    }
-   if (n - nsmall && !(C.blocks = ctx_acquire_on(dev, ctx_bs, blocks_cap))) return (size_t)-1;
+   if (nlarge && !(C.blocks = ctx_acquire_on(dev, ctx_bs, blocks_cap))) return false;
    std::vector<zultra_hip_block_t> blocks;
-   std::vector<zultra_hip_member_t> members;
-   size_t w = 0;
    for (size_t i = 0; i < n;) {
-      const bool small = pInSize[i] < small_limit;
+      size_t first = i;
+      while (!pInSize[first]) first++;   // (there is one: empty inputs at the end went with the batch in front of them)
+      const bool small = pInSize[first] < small_limit;
       zultra_hip_ctx_t *c = small ? C.files : C.blocks;
       const size_t max_count = small ? files_cap : blocks_cap, max_bytes = zultra_hip_data_capacity(c);
       size_t j = i, bytes = 0;
       blocks.clear();
-      for (; j < n && (pInSize[j] < small_limit) == small && j - i < max_count && bytes + pInSize[j] <= max_bytes; j++) {
+      for (; j < n; j++) {
+         if (!pInSize[j]) continue;
+         if ((pInSize[j] < small_limit) != small || blocks.size() >= max_count || bytes + pInSize[j] > max_bytes) break;
          blocks.push_back(zultra_hip_block_t{(uint64_t)bytes, 0, (uint32_t)pInSize[j]});
          bytes += pInSize[j];
       }
-      if (j == i) return (size_t)-1;
+      if (blocks.empty()) return false;
       uint8_t *stage = (uint8_t *)zultra_hip_staging(c, 0, bytes);
-      if (!stage) return (size_t)-1;
-      for (size_t k = i; k < j; k++) memcpy(stage + blocks[k - i].win_off, pIn + pInOff[k], pInSize[k]);
-      members.resize(j - i);
-      const size_t got = members_batch(c, stage, bytes, 0, blocks.data(), (uint32_t)(j - i), nFlags, 0, pOut + w, nMaxOut - w, members.data());
-      if (got == (size_t)-1) return got;
-      for (size_t k = i; k < j; k++) pOutOff[k] = w + (size_t)members[k - i].off;
-      w += got;
+      if (!stage) return false;
+      for (size_t k = i, b = 0; k < j; k++)
+         if (pInSize[k]) memcpy(stage + blocks[b++].win_off, pIn + pInOff[k], pInSize[k]);
+      if (!per_batch(c, stage, bytes, blocks, i, j)) return false;
       i = j;
    }
+   return true;
+}
+
+extern "C" size_t zultra_memory_compress_batch(const unsigned char *pIn, size_t nIn, const size_t *pInOff, const size_t *pInSize, size_t n, unsigned char *pOut, size_t nMaxOut,
+                                               size_t *pOutOff, const unsigned int nFlags) try {
+   if (!pIn || !pInOff || !pInSize || !n || !pOut || !pOutOff || (nFlags != 0 && nFlags != ZULTRA_FLAG_ZLIB_FRAMING && nFlags != ZULTRA_FLAG_GZIP_FRAMING) || zultra_hip_device_count() <= 0)
+      return (size_t)-1;
+   std::vector<zultra_hip_member_t> members;
+   size_t w = 0;
+   // a batch's members are read to where they belong in pOut
+   const bool ok = for_input_batches(pIn, nIn, pInOff, pInSize, n, false, [&](zultra_hip_ctx_t *c, const uint8_t *stage, size_t bytes, const std::vector<zultra_hip_block_t> &blocks, size_t i, size_t j) {
+      members.resize(j - i);
+      const size_t got = members_batch(c, stage, bytes, 0, blocks.data(), (uint32_t)(j - i), nFlags, 0, pOut + w, nMaxOut - w, members.data());
+      if (got == (size_t)-1) return false;
+      for (size_t k = i; k < j; k++) pOutOff[k] = w + (size_t)members[k - i].off;
+      w += got;
+      return true;
+   });
+   if (!ok) return (size_t)-1;
    pOutOff[n] = w;
    return w;
+} catch (...) {
+   return (size_t)-1;
+}
+
+// ---- ZIP archives: local records and the central directory written on the device (include/zultra_hip.h: zultra_hip_zip_members) -------------------------
+static void zip_put(unsigned char *&p, unsigned long long v, int nbytes) {
+   for (int k = 0; k < nbytes; k++) *p++ = (unsigned char)(v >> (8 * k));
+}
+
+extern "C" size_t zultra_zip_end_records(unsigned char *pOut, size_t nMaxOut, unsigned long long nEntries, unsigned long long nCentralOff, unsigned long long nCentralSize) {
+   const bool zip64 = nEntries > 65535;
+   if (!pOut || nMaxOut < (zip64 ? 98u : 22u) || nCentralOff >= 0xFFFFFFFFull || nCentralSize >= 0xFFFFFFFFull) return (size_t)-1;
+   unsigned char *p = pOut;
+   if (zip64) {
+      zip_put(p, 0x06064b50, 4);   // the ZIP64 end record: size of what follows, version made by, version needed, disks, entries twice, the central directory
+      zip_put(p, 44, 8);
+      zip_put(p, 45, 2);
+      zip_put(p, 45, 2);
+      zip_put(p, 0, 4);
+      zip_put(p, 0, 4);
+      zip_put(p, nEntries, 8);
+      zip_put(p, nEntries, 8);
+      zip_put(p, nCentralSize, 8);
+      zip_put(p, nCentralOff, 8);
+      zip_put(p, 0x07064b50, 4);   // its locator: disk, where the record stands, disks in all
+      zip_put(p, 0, 4);
+      zip_put(p, nCentralOff + nCentralSize, 8);
+      zip_put(p, 1, 4);
+   }
+   zip_put(p, 0x06054b50, 4);
+   zip_put(p, 0, 2);
+   zip_put(p, 0, 2);
+   zip_put(p, zip64 ? 0xFFFF : nEntries, 2);
+   zip_put(p, zip64 ? 0xFFFF : nEntries, 2);
+   zip_put(p, nCentralSize, 4);
+   zip_put(p, nCentralOff, 4);
+   zip_put(p, 0, 2);
+   return (size_t)(p - pOut);
+}
+
+// per entry: the two headers, and what zultra_memory_bound allows a max-block's stream beyond its input (64 sub-blocks, stored at worst); both copies of the names
+extern "C" size_t zultra_memory_bound_zip(size_t nInTotal, size_t nNamesTotal, size_t n) { return nInTotal + 2 * nNamesTotal + n * (30 + 46 + (1 + 4 + 1) * 64 + 8) + 98; }
+
+// The records of an archive of empty entries only, which has no batch for the device to hang them on: the layout of zh_zip_records for an empty entry.
+static void zip_empty_entry(unsigned char *&p, bool central, const char *name, size_t name_len, unsigned int dos, unsigned long long local_off) {
+   zip_put(p, central ? 0x02014b50 : 0x04034b50, 4);
+   if (central) zip_put(p, 20, 2);
+   zip_put(p, 10, 2);
+   zip_put(p, 0x0800, 2);
+   zip_put(p, 0, 2);
+   zip_put(p, dos, 4);
+   for (int k = 0; k < 3; k++) zip_put(p, 0, 4);   // CRC-32, sizes
+   zip_put(p, name_len, 2);
+   zip_put(p, 0, 2);
+   if (central) {
+      zip_put(p, 0, 6);   // comment, disk, internal attributes
+      zip_put(p, 0, 4);   // external attributes
+      zip_put(p, local_off, 4);
+   }
+   memcpy(p, name, name_len);
+   p += name_len;
+}
+
+extern "C" size_t zultra_memory_compress_zip(const unsigned char *pIn, size_t nIn, const size_t *pInOff, const size_t *pInSize, const char *pNames, const size_t *pNameOff, size_t n,
+                                             unsigned char *pOut, size_t nMaxOut, unsigned int nDosDateTime) try {
+   if (!pInOff || !pInSize || !pNames || !pNameOff || !n || !pOut) return (size_t)-1;
+   size_t nempty = 0;
+   for (size_t i = 0; i < n; i++) {
+      if (pNameOff[i + 1] <= pNameOff[i] || pNameOff[i + 1] - pNameOff[i] > 65535) return (size_t)-1;
+      nempty += !pInSize[i];
+   }
+   const size_t names_total = pNameOff[n] - pNameOff[0];
+   if (names_total >= 0xFFFFFFFFull || (nempty < n && (!pIn || zultra_hip_device_count() <= 0))) return (size_t)-1;
+   const unsigned int dos = nDosDateTime ? nDosDateTime : 0x00210000u;
+   std::vector<unsigned char> central;
+   size_t w = 0;
+   if (nempty == n) {
+      if ((30 + 46) * n + 2 * names_total + 98 > nMaxOut || 30 * n + names_total >= 0xFFFFFFFFull) return (size_t)-1;
+      central.resize(46 * n + names_total);
+      unsigned char *l = pOut, *c = central.data();
+      for (size_t i = 0; i < n; i++) {
+         zip_empty_entry(c, true, pNames + pNameOff[i], pNameOff[i + 1] - pNameOff[i], dos, (unsigned long long)(l - pOut));
+         zip_empty_entry(l, false, pNames + pNameOff[i], pNameOff[i + 1] - pNameOff[i], dos, 0);
+      }
+      w = (size_t)(l - pOut);
+   }
+   std::vector<uint32_t> name_off, entry_block;
+   std::vector<uint64_t> file_off;
+   const bool ok = for_input_batches(pIn, nIn, pInOff, pInSize, n, true, [&](zultra_hip_ctx_t *c, const uint8_t *stage, size_t bytes, const std::vector<zultra_hip_block_t> &blocks, size_t i, size_t j) {
+      if (zultra_hip_compress_blocks(c, stage, bytes, 0, blocks.data(), (uint32_t)blocks.size()) <= 0) return false;
+      if (zh_verify_on()) {   // (on the plain layout, which the gather leaves alone)
+         file_off.resize(blocks.size() + 1);
+         if (zultra_hip_stitch_files(c, file_off.data()) != 0 || !zh_verify_stitched(c)) return false;
+      }
+      name_off.resize(j - i + 1);
+      entry_block.resize(j - i);
+      for (size_t k = i; k <= j; k++) name_off[k - i] = (uint32_t)(pNameOff[k] - pNameOff[i]);
+      for (size_t k = i, b = 0; k < j; k++) entry_block[k - i] = pInSize[k] ? (uint32_t)b++ : 0xFFFFFFFFu;
+      uint64_t local = 0, cent = 0, central_at = 0;
+      if (zultra_hip_zip_members(c, pNames + pNameOff[i], name_off.data(), entry_block.data(), (uint32_t)(j - i), w, dos, NULL, &local, &cent) != 0) return false;
+      if (local > nMaxOut - w || zultra_hip_zip_read(c, pOut + w, 0, (size_t)local) != 0) return false;
+      (void)zultra_hip_zip_device(c, &central_at);
+      central.resize(central.size() + (size_t)cent);
+      if (zultra_hip_zip_read(c, central.data() + central.size() - (size_t)cent, (size_t)central_at, (size_t)cent) != 0) return false;
+      w += (size_t)local;
+      return true;
+   });
+   if (!ok || central.size() > nMaxOut - w) return (size_t)-1;
+   memcpy(pOut + w, central.data(), central.size());
+   const size_t end = zultra_zip_end_records(pOut + w + central.size(), nMaxOut - w - central.size(), n, w, central.size());
+   return end == (size_t)-1 ? end : w + central.size() + end;
 } catch (...) {
    return (size_t)-1;
 }

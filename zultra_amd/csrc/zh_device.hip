@@ -39,6 +39,7 @@
 #include "zh_split.h"
 #include "zh_stitch.h"
 #include "zh_frame.h"
+#include "zh_zip.h"
 #include "zh_verify.h"
 
 #define ZH_MAX_RUNS 8           // staggered runs of a batch (ZULTRA_HIP_STREAMS)
@@ -212,6 +213,18 @@ struct zultra_hip_ctx_s {
    uint32_t frame_gap;
    hipEvent_t ev_frame[4];    // around the scan, the mover and the frame kernel
    float frame_ms[3];
+   // a ZIP archive's entries (zh_zip.h, zultra_hip_zip_members): allocated by the first call, grown where a call needs more
+   uint8_t *d_zip;            // the local part, and at zip_central_at the central part
+   size_t zip_cap;
+   uint64_t zip_central_at;
+   uint32_t *d_zip_in;        // a call's name_off, entry_block and names
+   size_t zip_in_cap;
+   zh_zip_entry_t *d_zip_entries;
+   uint64_t *d_zip_src;
+   uint32_t zip_entries_cap;
+   zh_zip_report_t *d_zip_report, *h_zip_report;
+   hipEvent_t ev_zip[4];      // around the scan, the records and the copy
+   float zip_ms[3];
    uint32_t *d_crc, *d_crc_tables, *d_adler;
    uint32_t *h_adler;
    std::vector<uint32_t> adler;
@@ -581,6 +594,14 @@ extern "C" void zultra_hip_destroy(zultra_hip_ctx_t *c) {
    (void)hipFree(c->d_members);
    for (int i = 0; i < 4; i++)
       if (c->ev_frame[i]) (void)hipEventDestroy(c->ev_frame[i]);
+   (void)hipFree(c->d_zip);
+   (void)hipFree(c->d_zip_in);
+   (void)hipFree(c->d_zip_entries);
+   (void)hipFree(c->d_zip_src);
+   (void)hipFree(c->d_zip_report);
+   if (c->h_zip_report) (void)hipHostFree(c->h_zip_report);
+   for (int i = 0; i < 4; i++)
+      if (c->ev_zip[i]) (void)hipEventDestroy(c->ev_zip[i]);
    (void)hipFree(c->d_crc);
    (void)hipFree(c->d_adler);
    if (c->h_adler) (void)hipHostFree(c->h_adler);
@@ -1753,7 +1774,9 @@ static int zh_stitch_verdict(zultra_hip_ctx_t *c, bool scan_only) {
    return 0;
 }
 
-static int zh_stitch_on_device(zultra_hip_ctx_t *c, uint32_t phase, int final_block, int files, bool scan_only = false, const zh_frame_args_t *frame = NULL) {
+// A stitch of the last batch on the context's stream in two halves, so that a caller can put kernels of its own behind the assembly and wait once
+// (zultra_hip_zip_members): what is enqueued, and what the host makes of it after the synchronisation.
+static int zh_stitch_begin(zultra_hip_ctx_t *c, uint32_t phase, int final_block, int files, bool scan_only, const zh_frame_args_t *frame) {
    ZH_CHECK(c, hipSetDevice(c->device));
    hipStream_t st = c->stream;
    c->stitched_valid = 0;   // (the items and the scan's report are rewritten)
@@ -1762,9 +1785,9 @@ static int zh_stitch_on_device(zultra_hip_ctx_t *c, uint32_t phase, int final_bl
    c->frame_gap = 0;
    ZH_CHECK(c, hipEventRecord(c->ev_stitch[ZH_STITCH_EV_START], st));
    if (frame) ZH_CHECK(c, hipEventRecord(c->ev_frame[0], st));
-   if (zh_enqueue_stitch(c, st, phase, final_block, files, scan_only, true, frame) != 0) return -1;
-   ZH_CHECK(c, hipStreamSynchronize(st));
-   ZH_CHECK(c, hipGetLastError());
+   return zh_enqueue_stitch(c, st, phase, final_block, files, scan_only, true, frame);
+}
+static int zh_stitch_finish(zultra_hip_ctx_t *c, int files, bool scan_only, const zh_frame_args_t *frame) {
    if (!scan_only) (void)hipEventElapsedTime(&c->timing.stitch_ms, c->ev_stitch[ZH_STITCH_EV_START], c->ev_stitch[ZH_STITCH_EV_END]);
    if (frame)
       for (int i = 0; i < 3; i++) (void)hipEventElapsedTime(&c->frame_ms[i], c->ev_frame[i], c->ev_frame[i + 1]);
@@ -1784,6 +1807,12 @@ static int zh_stitch_on_device(zultra_hip_ctx_t *c, uint32_t phase, int final_bl
       if (frame) c->frame_gap = zh_frame_head(frame->framing) + zh_frame_tail(frame->framing);
    }
    return rc;
+}
+static int zh_stitch_on_device(zultra_hip_ctx_t *c, uint32_t phase, int final_block, int files, bool scan_only = false, const zh_frame_args_t *frame = NULL) {
+   if (zh_stitch_begin(c, phase, final_block, files, scan_only, frame) != 0) return -1;
+   ZH_CHECK(c, hipStreamSynchronize(c->stream));
+   ZH_CHECK(c, hipGetLastError());
+   return zh_stitch_finish(c, files, scan_only, frame);
 }
 
 // The next batch of max-blocks (zultra_hip_compress_blocks) is stitched at bit phase `phase` (final_block as for zultra_hip_stitch_device) BEHIND ITS LAST KERNEL,
@@ -1879,6 +1908,151 @@ extern "C" int zultra_hip_frame_members(zultra_hip_ctx_t *c, unsigned int framin
 }
 extern "C" void zultra_hip_last_frame_ms(const zultra_hip_ctx_t *c, float *ms /* [3]: scan, mover, frame kernel */) {
    for (int i = 0; c && ms && i < 3; i++) ms[i] = c->frame_ms[i];
+}
+
+// A ZIP archive's entries (zh_zip.h): a gather behind the plain files-form assembly of the last batch. The assembly is the one the stream buffer holds — a files
+// context's graph ran it, zultra_hip_stitch_files did — or is enqueued here, in front of the three kernels; one synchronisation either way. Everything the host can
+// refuse it refuses before anything is allocated or enqueued; what only the device knows (the assembly's failure, the 32-bit limit) zh_zip_scan reports, and the
+// two writing kernels leave at its flag.
+static_assert(sizeof(zultra_hip_zip_entry_t) == sizeof(zh_zip_entry_t), "zultra_hip_zip_entry_t is zh_zip_entry_t");
+template <typename T>
+static int zh_zip_grow(zultra_hip_ctx_t *c, T **p, size_t have, size_t want, bool keep) {   // (a grown buffer keeps its bytes where a refused call must find them again)
+   T *q = NULL;
+   ZH_CHECK(c, hipMalloc((void **)&q, want * sizeof(T)));
+   if (keep && *p && have) ZH_CHECK(c, hipMemcpy(q, *p, have * sizeof(T), hipMemcpyDeviceToDevice));
+   (void)hipFree(*p);
+   *p = q;
+   return 0;
+}
+extern "C" int zultra_hip_zip_members(zultra_hip_ctx_t *c, const void *names, const uint32_t *name_off, const uint32_t *entry_block, uint32_t n, uint64_t base_off,
+                                      uint32_t dos_datetime, zultra_hip_zip_entry_t *entries, uint64_t *local_bytes, uint64_t *central_bytes) {
+   ZH_EMU_SERIALIZE();
+   if (!c || !names || !name_off || !n || !local_bytes || !central_bytes || c->nsubs == 0) return -1;
+   for (uint32_t b = 0; b < c->nblocks; b++)
+      if (c->blocks[b].prev != 0) {
+         snprintf(c->err, sizeof(c->err), "max-block %u has history: an entry stands alone", b);
+         return -1;
+      }
+   uint32_t next = 0;
+   for (uint32_t i = 0; i < n; i++) {
+      if (name_off[i + 1] <= name_off[i] || name_off[i + 1] - name_off[i] > 65535u) {
+         snprintf(c->err, sizeof(c->err), "entry %u: a name has 1 .. 65535 bytes", i);
+         return -1;
+      }
+      const uint32_t b = entry_block ? entry_block[i] : i;
+      if (b != ZH_ZIP_EMPTY && b != next++) {
+         snprintf(c->err, sizeof(c->err), "entry %u names max-block %u: the entries take every max-block of the batch once, in increasing order", i, b);
+         return -1;
+      }
+   }
+   if (next != c->nblocks) {
+      snprintf(c->err, sizeof(c->err), "the entries name %u max-blocks, the batch has %u", next, c->nblocks);
+      return -1;
+   }
+   if (base_off >= ZH_ZIP_LIMIT) {
+      snprintf(c->err, sizeof(c->err), "the archive reaches 4 GiB: ZIP64 entries are not written");
+      return -2;
+   }
+   ZH_CHECK(c, hipSetDevice(c->device));
+   hipStream_t st = c->stream;
+   const bool assembled = c->stream_stitched == 2 && c->frame_gap == 0;   // (the plain files form is in the stream buffer, its offsets in d_file_off, its report in d_scan_out)
+   if (!c->d_file_off && zh_alloc(c, &c->d_file_off, (size_t)c->max_blocks + 1)) return -1;
+   // what the call brings: name_off, entry_block, names — one upload
+   const uint32_t names_bytes = name_off[n] - name_off[0];
+   const size_t in_words = (size_t)n + 1 + (entry_block ? n : 0) + ((size_t)names_bytes + 3) / 4;
+   if (in_words > c->zip_in_cap) {
+      if (zh_zip_grow(c, &c->d_zip_in, 0, in_words, false)) return -1;
+      c->zip_in_cap = in_words;
+   }
+   if (n > c->zip_entries_cap) {
+      if (zh_zip_grow(c, &c->d_zip_entries, 0, n, false) || zh_zip_grow(c, &c->d_zip_src, 0, n, false)) return -1;
+      c->zip_entries_cap = n;
+   }
+   if (!c->d_zip_report) {
+      if (zh_alloc(c, &c->d_zip_report, 1)) return -1;
+      ZH_CHECK(c, hipHostMalloc((void **)&c->h_zip_report, sizeof(zh_zip_report_t), 0));
+      for (int i = 0; i < 4; i++) ZH_CHECK(c, hipEventCreate(&c->ev_zip[i]));
+   }
+   // the buffer: the headers and names, and what the streams take — known where the assembly is, else at most what a stitch clears for this batch
+   const uint64_t streams = assembled ? (c->h_scan_out->end_bit + 7) >> 3 : (uint64_t)zh_stream_clear_bytes(c);
+   const uint64_t central_at = ((uint64_t)ZH_ZIP_LOCAL * n + names_bytes + streams + 15) & ~15ull;
+   const uint64_t want = central_at + (uint64_t)ZH_ZIP_CENTRAL * n + names_bytes + 16;
+   if (want > c->zip_cap) {
+      if (zh_zip_grow(c, &c->d_zip, c->zip_cap, (size_t)want, true)) return -1;
+      c->zip_cap = (size_t)want;
+   }
+   std::vector<uint32_t> in(in_words);
+   memcpy(in.data(), name_off, ((size_t)n + 1) * sizeof(uint32_t));
+   if (entry_block) memcpy(in.data() + n + 1, entry_block, (size_t)n * sizeof(uint32_t));
+   const size_t names_word = (size_t)n + 1 + (entry_block ? n : 0);
+   memcpy(in.data() + names_word, (const uint8_t *)names + name_off[0], names_bytes);
+   ZH_CHECK(c, hipMemcpyAsync(c->d_zip_in, in.data(), in_words * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+   const uint32_t *d_name_off = c->d_zip_in, *d_entry_block = entry_block ? c->d_zip_in + n + 1 : NULL;
+   const uint8_t *d_names = (const uint8_t *)(c->d_zip_in + names_word) - name_off[0];   // (name i is at d_names + name_off[i])
+
+   if (!assembled && zh_stitch_begin(c, 0, -1, 1, false, NULL) != 0) return -1;
+   ZH_CHECK(c, hipEventRecord(c->ev_zip[0], st));
+   ZH_LAUNCH(zh_zip_scan, 1, ZH_ZIP_SCAN_THREADS, st, d_name_off, d_entry_block, n, (const zh_block_t *)c->d_blocks, (const uint64_t *)c->d_file_off,
+             (const zh_scan_out_t *)c->d_scan_out, (uint64_t)c->stream_cap, base_off, c->d_zip_entries, c->d_zip_src, c->d_zip_report);
+   ZH_CHECK(c, hipEventRecord(c->ev_zip[1], st));
+   {
+      // one lane per entry; ZULTRA_HIP_GRID_CAP (tests) caps the LANES, as for zh_frame_members
+      uint32_t threads = ZH_ZIP_RECORD_THREADS, grid = (n + ZH_ZIP_RECORD_THREADS - 1) / ZH_ZIP_RECORD_THREADS;
+      if (c->grid_cap && (uint64_t)grid * threads > c->grid_cap) {
+         threads = min(threads, c->grid_cap);
+         grid = max(1u, c->grid_cap / threads);
+      }
+      ZH_LAUNCH(zh_zip_records, grid, threads, st, c->d_zip_entries, (const uint64_t *)c->d_zip_src, d_name_off, d_names, d_entry_block, (const uint32_t *)c->d_crc, n, base_off,
+                dos_datetime ? dos_datetime : 0x00210000u, central_at, (const zh_zip_report_t *)c->d_zip_report, c->d_zip);
+   }
+   ZH_CHECK(c, hipEventRecord(c->ev_zip[2], st));
+   {
+      // (entry, slice): as many slices side by side as the batch's largest input can have at its worst, stored; along the entries a few workgroups per CU. The cap
+      // of the tests caps the workgroups, so that a wave sees several entries and several slices
+      uint32_t largest = 0;
+      for (uint32_t b = 0; b < c->nblocks; b++) largest = max(largest, c->blocks[b].n);
+      const uint64_t worst = (uint64_t)largest + 5ull * (largest / 65535u + 1u) + 1;
+      uint32_t yslices = (uint32_t)zh_max64(1, zh_min64((worst + 16ull * ZH_ZIP_SLICE_CHUNKS - 1) / (16ull * ZH_ZIP_SLICE_CHUNKS), ZH_ZIP_MAX_YSLICES));
+      const uint32_t waves = ZH_ZIP_COPY_THREADS / 64;
+      uint32_t xdim = (uint32_t)zh_max64(1, zh_min64((n + waves - 1) / waves, 8ull * c->total_cus / yslices));
+      if (c->grid_cap && (uint64_t)xdim * yslices > c->grid_cap) {
+         yslices = min(yslices, max(1u, c->grid_cap / 2));
+         xdim = max(1u, c->grid_cap / yslices);
+      }
+      ZH_LAUNCH(zh_zip_copy, xdim * yslices, ZH_ZIP_COPY_THREADS, st, (const zh_zip_entry_t *)c->d_zip_entries, (const uint64_t *)c->d_zip_src, n, base_off, yslices,
+                (const uint8_t *)c->d_stream, (const zh_zip_report_t *)c->d_zip_report, c->d_zip);
+   }
+   ZH_CHECK(c, hipEventRecord(c->ev_zip[3], st));
+   ZH_CHECK(c, hipMemcpyAsync(c->h_zip_report, c->d_zip_report, sizeof(zh_zip_report_t), hipMemcpyDeviceToHost, st));
+   if (entries) ZH_CHECK(c, hipMemcpyAsync(entries, c->d_zip_entries, (size_t)n * sizeof(zh_zip_entry_t), hipMemcpyDeviceToHost, st));   // (as found where the call is refused)
+   ZH_CHECK(c, hipStreamSynchronize(st));
+   ZH_CHECK(c, hipGetLastError());
+   for (int i = 0; i < 3; i++) (void)hipEventElapsedTime(&c->zip_ms[i], c->ev_zip[i], c->ev_zip[i + 1]);
+   if (!assembled) {
+      const int rc = zh_stitch_finish(c, 1, false, NULL);
+      if (rc != 0) return rc;
+   }
+   if (c->h_zip_report->failed) {
+      snprintf(c->err, sizeof(c->err), c->h_zip_report->failed == 2 ? "the archive reaches 4 GiB: ZIP64 entries are not written" : "the stream assembly failed");
+      return -2;
+   }
+   c->zip_central_at = central_at;
+   *local_bytes = c->h_zip_report->local_bytes;
+   *central_bytes = c->h_zip_report->central_bytes;
+   return 0;
+}
+extern "C" const void *zultra_hip_zip_device(const zultra_hip_ctx_t *c, uint64_t *central_at) {
+   if (c && central_at) *central_at = c->zip_central_at;
+   return c ? c->d_zip : NULL;
+}
+extern "C" int zultra_hip_zip_read(zultra_hip_ctx_t *c, void *out, size_t offset, size_t nbytes) {
+   if (!c || !out || nbytes > c->zip_cap || offset > c->zip_cap - nbytes) return -1;
+   ZH_CHECK(c, hipSetDevice(c->device));
+   ZH_CHECK(c, hipMemcpy(out, c->d_zip + offset, nbytes, hipMemcpyDeviceToHost));
+   return 0;
+}
+extern "C" void zultra_hip_last_zip_ms(const zultra_hip_ctx_t *c, float *ms /* [3]: scan, records, copy */) {
+   for (int i = 0; c && ms && i < 3; i++) ms[i] = c->zip_ms[i];
 }
 
 extern "C" int zultra_hip_compress_files(zultra_hip_ctx_t *c, const void *data, size_t data_size, int data_on_device, const uint64_t *offsets,

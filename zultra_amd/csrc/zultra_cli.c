@@ -10,7 +10,10 @@
  *    zultra_amd_cli -x [-f gzip|zlib|raw] [-d <device>] [-D <dictionary>] [-v] <infile> <outfile>
  *    zultra_amd_cli -x -m [-f gzip] [-d <device>] [-v] <infile> <outfile>
  *    zultra_amd_cli -f bgzf [-b <block size>] [-d <device>] [-c] [-v] <infile> <outfile>
+ *    zultra_amd_cli -a <archive.zip> [-d <device>] [-c] [-v] <file>...
  *
+ * -a: a ZIP archive of the files named, every file an entry under its name as given, headers and central directory written on the device
+ *     (zultra_memory_compress_zip). A file is one max-block: at most 2 MiB; an empty file is an empty entry. No dictionary.
  * -f bgzf: bgzip(1) — <infile> in blocks of -b bytes (default and at most 65280), every block a BGZF member written on the device, and BGZF's end marker
  *     (zultra_memory_compress_bgzf); `-x -m -f gzip` is the way back. No dictionary: a member stands alone.
  * -D: a preset dictionary, loaded as the reference's tool loads it (zultra_dictionary_load: the last 32 KiB of the file; tool/zultra.c -D). Compressing,
@@ -78,6 +81,84 @@ static int write_bgzf(FILE *fin, FILE *fout, unsigned block, int verbose, int ve
    return rc;
 }
 
+/* -a: the files named through zultra_memory_compress_zip */
+static int write_zip(const char *archive, char **files, int n, int verbose, int verify) {
+   size_t *in_off = (size_t *)calloc((size_t)n, sizeof(size_t)), *in_size = (size_t *)calloc((size_t)n, sizeof(size_t)), *name_off = (size_t *)calloc((size_t)n + 1, sizeof(size_t));
+   size_t total = 0, cap = (size_t)1 << 20, names_total = 0;
+   unsigned char *in = (unsigned char *)malloc(cap), *out = NULL;
+   char *names = NULL;
+   int rc = in && in_off && in_size && name_off ? 0 : 100;
+   for (int k = 0; k < n && !rc; k++) {
+      FILE *f = fopen(files[k], "rb");
+      if (!f) {
+         fprintf(stderr, "error opening '%s' for reading\n", files[k]);
+         rc = 100;
+         break;
+      }
+      in_off[k] = total;
+      for (size_t got = 1; got > 0 && total - in_off[k] <= 2097152;) {
+         if (total == cap) {
+            unsigned char *more = (unsigned char *)realloc(in, cap *= 2);
+            if (!more) {
+               rc = 100;
+               break;
+            }
+            in = more;
+         }
+         total += got = fread(in + total, 1, cap - total, f);
+      }
+      fclose(f);
+      in_size[k] = total - in_off[k];
+      if (in_size[k] > 2097152) {
+         fprintf(stderr, "'%s' is larger than 2 MiB: an entry is one max-block\n", files[k]);
+         rc = 100;
+      }
+      name_off[k] = names_total;
+      names_total += strlen(files[k]);
+      name_off[k + 1] = names_total;
+   }
+   if (!rc) {
+      names = (char *)malloc(names_total + 1);
+      for (int k = 0; names && k < n; k++) memcpy(names + name_off[k], files[k], name_off[k + 1] - name_off[k]);
+      const size_t room = zultra_memory_bound_zip(total, names_total, (size_t)n);
+      out = (unsigned char *)malloc(room);
+      FILE *fout = names && out ? fopen(archive, "wb") : NULL;
+      if (!names || !out)
+         fprintf(stderr, "out of memory\n");
+      else if (!fout)
+         fprintf(stderr, "error opening '%s' for writing\n", archive);
+      rc = fout ? 0 : 100;
+      if (fout) {
+         const double t0 = now_s();
+         const size_t size = zultra_memory_compress_zip(in, total, in_off, in_size, names, name_off, (size_t)n, out, room, 0);
+         const double dt = now_s() - t0;
+         if (size == (size_t)-1) {
+            fprintf(stderr, "compression error (a failed verification, an empty or overlong name, a device failure, or no HIP device: this library has no CPU path)\n");
+            rc = 100;
+         }
+         else if (fwrite(out, 1, size, fout) != size) {
+            fprintf(stderr, "write error\n");
+            rc = 100;
+         }
+         if (verbose && !rc)
+            fprintf(stdout, "%d entries, %llu -> %llu bytes (%.2f %%), %.1f MB/s\n", n, (unsigned long long)total, (unsigned long long)size, total ? 100.0 * (double)size / (double)total : 0.0,
+                    dt > 0 ? (double)total / dt / 1e6 : 0.0);
+         if (verbose && verify && !rc) fprintf(stdout, "verified %llu bytes on the device\n", zultra_verified_bytes());
+         fclose(fout);
+      }
+   }
+   else if (!in || !in_off || !in_size || !name_off)
+      fprintf(stderr, "out of memory\n");
+   zultra_release_cached_contexts();
+   free(in);
+   free(out);
+   free(names);
+   free(in_off);
+   free(in_size);
+   free(name_off);
+   return rc;
+}
+
 /* -x: the whole file through zultra_memory_decompress. The output size is not known in advance (gzip's ISIZE is a hint, modulo 2^32): the buffer
  * grows until the call succeeds or the bound of the format is passed (a deflate stream expands at most 1032 : 1). */
 static int extract(FILE *fin, FILE *fout, unsigned flags, int verbose, const void *dict, int dict_size, int members, int device) {
@@ -136,7 +217,7 @@ int main(int argc, char **argv) {
    unsigned flags = ZULTRA_FLAG_GZIP_FRAMING, block = 0;
    size_t chunk = (size_t)8 << 20;
    int verbose = 0, verify = 0, do_extract = 0, members = 0, device = 0, bgzf = 0, i = 1;
-   const char *dict_name = NULL;
+   const char *dict_name = NULL, *archive = NULL;
    if (getenv("ZULTRA_HIP_DEVICE")) device = atoi(getenv("ZULTRA_HIP_DEVICE"));   /* (the library's own default: -m sizes its buffer with an index call on the same device) */
    for (; i < argc && argv[i][0] == '-' && argv[i][1]; i++) {
       if (!strcmp(argv[i], "-b") && i + 1 < argc)
@@ -152,6 +233,8 @@ int main(int argc, char **argv) {
       }
       else if (!strcmp(argv[i], "-D") && i + 1 < argc)
          dict_name = argv[++i];
+      else if (!strcmp(argv[i], "-a") && i + 1 < argc)
+         archive = argv[++i];
       else if (!strcmp(argv[i], "-v"))
          verbose = 1;
       else if (!strcmp(argv[i], "-x"))
@@ -169,13 +252,15 @@ int main(int argc, char **argv) {
       fprintf(stderr, "-b %u: a BGZF block holds at most %u bytes of input\n", block, ZULTRA_HIP_BGZF_BLOCK);
       return 100;
    }
-   if (argc - i != 2 || chunk == 0 || (members && (!do_extract || flags != ZULTRA_FLAG_GZIP_FRAMING || dict_name)) || (bgzf && !do_extract && dict_name)) {
+   if (archive ? (argc - i < 1 || do_extract || bgzf || dict_name) : argc - i != 2 || chunk == 0 || (members && (!do_extract || flags != ZULTRA_FLAG_GZIP_FRAMING || dict_name)) || (bgzf && !do_extract && dict_name)) {
       fprintf(stderr, "usage: %s [-b <max block size>] [-f gzip|zlib|raw] [-k <chunk KiB>] [-d <device>] [-D <dictionary>] [-c] [-v] <infile> <outfile>\n"
                       "       %s -x [-f gzip|zlib|raw] [-d <device>] [-D <dictionary>] [-v] <infile> <outfile>\n"
                       "       %s -x -m [-f gzip] [-d <device>] [-v] <infile> <outfile>   (any number of gzip members: BGZF, pigz -i, cat a.gz b.gz)\n"
-                      "       %s -f bgzf [-b <block size, at most 65280>] [-d <device>] [-c] [-v] <infile> <outfile>   (BGZF members and the end marker)\n", argv[0], argv[0], argv[0], argv[0]);
+                      "       %s -f bgzf [-b <block size, at most 65280>] [-d <device>] [-c] [-v] <infile> <outfile>   (BGZF members and the end marker)\n"
+                      "       %s -a <archive.zip> [-d <device>] [-c] [-v] <file>...   (a ZIP archive: every file, of at most 2 MiB, an entry under its name)\n", argv[0], argv[0], argv[0], argv[0], argv[0]);
       return 100;
    }
+   if (archive) return write_zip(archive, argv + i, argc - i, verbose, verify);
    void *dict = NULL;
    int dict_size = 0;
    if (dict_name && (zultra_dictionary_load(dict_name, &dict, &dict_size) != ZULTRA_OK || dict_size <= 0)) {

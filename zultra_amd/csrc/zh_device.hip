@@ -85,6 +85,38 @@ static void zh_graph_clear(zh_graph_set_t *G) {
    G->nblocks = 0;
 }
 
+// A stitch as it is enqueued (zh_enqueue_stitch): one stream from bit phase `phase` with BFINAL in max-block final_block (-1: left open), or every max-block a stream
+// of its own (files); scan_only: the scan's report and nothing else (zultra_hip_stitch_phase_table); framed (files form only, zultra_hip_frame_members): room for a
+// header and a trailer around every stream, and the kernel that fills it
+struct zh_frame_args_t { uint32_t framing, eof; };   // (eof: bytes of end marker behind the last member)
+struct zh_stitch_job_t {
+   uint32_t phase;
+   int final_block;
+   bool files, scan_only, framed;
+   zh_frame_args_t frame;   // (framed)
+};
+
+// What the stream buffer holds of the last batch — the one record every call that assembles writes and every call that reads the buffer asks (zh_assembly_*
+// below: nobody else touches the fields).
+//  * A new batch clears it. An armed stitch (zultra_hip_stitch_with_batch) is consumed by that batch, and armed again if the batch has to run again.
+//  * A batch of max-blocks with an armed stitch records {STREAM, phase, final_block, gap 0, with_batch, rc}; a files context's batch, whose graph holds the plain
+//    assembly, {FILES, gap 0, with_batch, rc}. A failed verdict is kept (rc != 0): the call that asks for that assembly returns the rc without launching, and
+//    nothing usable is there for verify and zip.
+//  * Every explicit assembly — zultra_hip_stitch_device with no matching with-batch result, zultra_hip_stitch_files, zultra_hip_frame_members,
+//    zultra_hip_stitch_phase_table, the one inside zultra_hip_zip_members — clears the record before it enqueues (the items and the scan's report are rewritten) and,
+//    if it succeeds and moved bits, records its layout with with_batch = false. A failed one and the phase table's scan leave NONE: verify refuses behind them.
+//  * Only a with-batch result is handed out without a launch; an explicit assembly asked for again is done again (a caller may have written the buffer,
+//    zultra_hip_stream_write). zultra_hip_zip_members gathers from whatever plain files form the buffer holds, with-batch or explicit.
+enum zh_layout_t { ZH_LAYOUT_NONE, ZH_LAYOUT_STREAM, ZH_LAYOUT_FILES };
+struct zh_assembly_t {
+   zh_layout_t layout;    // what d_stream / d_items / d_scan_out (and d_file_off) describe
+   uint32_t phase;        // STREAM: the phase it starts at
+   int final_block;       // STREAM: the final block it was stitched with
+   uint32_t gap;          // FILES: head + tail bytes between the streams (0: the plain form)
+   bool with_batch;       // it went out behind the batch's kernels (the armed stitch, a files context's graph)
+   int rc;                // zh_stitch_verdict of it: the buffer is usable iff layout != NONE && rc == 0
+};
+
 struct zultra_hip_ctx_s {
    int device;
    uint32_t num_cus;            // persistent kernels launch one workgroup per CU
@@ -109,9 +141,10 @@ struct zultra_hip_ctx_s {
    std::vector<zh_seg_t> segs;
    std::vector<uint32_t> seg_base;
    zh_match_t *d_match;
-   // a stitch enqueued with its batch (zultra_hip_stitch_with_batch): armed for the next batch; what the last batch was stitched with, if it was
-   int ab_armed, ab_final, stitched_valid, stitched_final, stitched_rc;
-   uint32_t ab_phase, stitched_phase;
+   zh_assembly_t held;          // what the stream buffer holds of the last batch (zh_assembly_*)
+   zh_stitch_job_t stitch_job;  // the stitch on the context's stream: what zh_stitch_begin enqueued, for zh_stitch_finish
+   zh_stitch_job_t armed_job;   // a stitch enqueued with its batch (zultra_hip_stitch_with_batch) ...
+   bool armed;                  // ... armed for the next batch
    // what the runs of the LAST batch of max-blocks listed for zh_parse_chain (their counters, read back with the batch's results): a context whose last batch had no chain
    // at all in run k enqueues run k of the next batch without chain kernels (zh_enqueue_run; zh_parse.h: zh_run_is_void)
    int chain_seen_runs;                  // runs of that batch (0: no batch yet)
@@ -198,19 +231,16 @@ struct zultra_hip_ctx_s {
    zh_scan_out_t *d_scan_out, *h_scan_out;
    uint64_t *d_file_off;      // files mode: first byte of every input's stream
    uint64_t *h_file_off;      // ... read back with the batch (the stitch of a files batch goes out with it, zh_enqueue_files_tail)
-   int files_stitched, files_stitch_rc;   // the last files batch was stitched with its kernels; zh_stitch_verdict of that
    uint32_t *d_task_prefix, *h_task_prefix;   // files mode: exclusive prefix of the inputs' task counts, computed by the host from the sizes it was handed (zh_plan_files); B + 1 entries
    uint32_t *d_stream;        // stitched deflate bits of the last batch
    size_t stream_cap;         // bytes
-   // verification (zh_verify.h, zultra_hip_verify_device): what is allocated on the first call, and whether the stream buffer holds a stitched batch
+   // verification (zh_verify.h, zultra_hip_verify_device): what is allocated on the first call (zh_need_verify)
    zh_verify_item_t *d_vitems;
    zh_verify_report_t *d_vreport, *h_vreport;
    hipEvent_t ev_verify[2];
-   int stream_stitched;       // 0: nothing to verify (no stitch yet, one that failed, a phase-table call since); 1: a stream; 2: one stream per max-block (files)
    float verify_ms;
-   // framed members (zh_frame.h, zultra_hip_frame_members): allocated by the first call; the head + tail bytes between the streams the buffer holds (0: none)
+   // framed members (zh_frame.h, zultra_hip_frame_members): allocated by the first call (zh_need_frame)
    zh_member_t *d_members;
-   uint32_t frame_gap;
    hipEvent_t ev_frame[4];    // around the scan, the mover and the frame kernel
    float frame_ms[3];
    // a ZIP archive's entries (zh_zip.h, zultra_hip_zip_members): allocated by the first call, grown where a call needs more
@@ -512,6 +542,33 @@ static int zh_alloc(zultra_hip_ctx_t *c, T **p, size_t count) {
    return 0;
 }
 
+// What a context holds only once a call has asked for it: each set is created here, by a caller that has set the device, and released in zultra_hip_destroy under
+// the function's name. The streams' offsets of the files form (a files context has them from its creation):
+static int zh_need_file_off(zultra_hip_ctx_t *c) { return c->d_file_off ? 0 : zh_alloc(c, &c->d_file_off, (size_t)c->max_blocks + 1); }
+// zultra_hip_verify_device: 24 bytes per sub-block, the batch report and its pinned mirror, two events
+static int zh_need_verify(zultra_hip_ctx_t *c) {
+   if (c->d_vitems) return 0;
+   if (zh_alloc(c, &c->d_vitems, (size_t)c->max_blocks * c->max_subs) || zh_alloc(c, &c->d_vreport, 1)) return -1;
+   ZH_CHECK(c, hipHostMalloc((void **)&c->h_vreport, sizeof(zh_verify_report_t), 0));
+   for (int i = 0; i < 2; i++) ZH_CHECK(c, hipEventCreate(&c->ev_verify[i]));
+   return 0;
+}
+// zultra_hip_frame_members: a record per member, four events
+static int zh_need_frame(zultra_hip_ctx_t *c) {
+   if (!c->d_members && zh_alloc(c, &c->d_members, (size_t)c->max_blocks)) return -1;
+   for (int i = 0; i < 4; i++)
+      if (!c->ev_frame[i]) ZH_CHECK(c, hipEventCreate(&c->ev_frame[i]));
+   return 0;
+}
+// zultra_hip_zip_members: the report of zh_zip_scan and its pinned mirror, four events (the buffers sized by a call's entries grow there, zh_zip_grow)
+static int zh_need_zip(zultra_hip_ctx_t *c) {
+   if (c->d_zip_report) return 0;
+   if (zh_alloc(c, &c->d_zip_report, 1)) return -1;
+   ZH_CHECK(c, hipHostMalloc((void **)&c->h_zip_report, sizeof(zh_zip_report_t), 0));
+   for (int i = 0; i < 4; i++) ZH_CHECK(c, hipEventCreate(&c->ev_zip[i]));
+   return 0;
+}
+
 extern "C" void zultra_hip_destroy(zultra_hip_ctx_t *c) {
    if (!c) return;
    (void)hipSetDevice(c->device);
@@ -546,7 +603,6 @@ extern "C" void zultra_hip_destroy(zultra_hip_ctx_t *c) {
    (void)hipFree(c->d_nsubs);
    (void)hipFree(c->d_blk_start);
    (void)hipFree(c->d_scan_out);
-   (void)hipFree(c->d_file_off);
    (void)hipFree(c->d_task_prefix);
    if (c->h_task_prefix) (void)hipHostFree(c->h_task_prefix);
    if (c->h_grids) (void)hipHostFree(c->h_grids);
@@ -586,22 +642,23 @@ extern "C" void zultra_hip_destroy(zultra_hip_ctx_t *c) {
    (void)hipFree(c->d_results_compact);
    (void)hipFree(c->d_items);
    (void)hipFree(c->d_stream);
-   (void)hipFree(c->d_vitems);
+   (void)hipFree(c->d_file_off);   // zh_need_file_off (or the creation of a files context)
+   (void)hipFree(c->d_vitems);     // zh_need_verify
    (void)hipFree(c->d_vreport);
    if (c->h_vreport) (void)hipHostFree(c->h_vreport);
    for (int i = 0; i < 2; i++)
       if (c->ev_verify[i]) (void)hipEventDestroy(c->ev_verify[i]);
-   (void)hipFree(c->d_members);
+   (void)hipFree(c->d_members);    // zh_need_frame
    for (int i = 0; i < 4; i++)
       if (c->ev_frame[i]) (void)hipEventDestroy(c->ev_frame[i]);
-   (void)hipFree(c->d_zip);
-   (void)hipFree(c->d_zip_in);
-   (void)hipFree(c->d_zip_entries);
-   (void)hipFree(c->d_zip_src);
-   (void)hipFree(c->d_zip_report);
+   (void)hipFree(c->d_zip_report); // zh_need_zip
    if (c->h_zip_report) (void)hipHostFree(c->h_zip_report);
    for (int i = 0; i < 4; i++)
       if (c->ev_zip[i]) (void)hipEventDestroy(c->ev_zip[i]);
+   (void)hipFree(c->d_zip);        // zh_zip_grow
+   (void)hipFree(c->d_zip_in);
+   (void)hipFree(c->d_zip_entries);
+   (void)hipFree(c->d_zip_src);
    (void)hipFree(c->d_crc);
    (void)hipFree(c->d_adler);
    if (c->h_adler) (void)hipHostFree(c->h_adler);
@@ -690,9 +747,33 @@ static int zh_spread_streams(zultra_hip_ctx_t *c) {
 }
 #endif
 
-struct zh_frame_args_t { uint32_t framing, eof; };   // (eof: bytes of end marker behind the last member)
-static int zh_enqueue_stitch(zultra_hip_ctx_t *c, hipStream_t st, uint32_t phase, int final_block, int files, bool scan_only, bool clear, const zh_frame_args_t *frame = NULL);
+// ---- the stitch jobs, and the record of what the stream buffer holds (zh_assembly_t) ----------------------------------------------------------------------
+static zh_stitch_job_t zh_job_stream(uint32_t phase, int final_block, bool scan_only = false) { return {phase & 7u, final_block, false, scan_only, false, {0, 0}}; }
+static zh_stitch_job_t zh_job_files(void) { return {0, -1, true, false, false, {0, 0}}; }   // (the plain files form)
+static zh_stitch_job_t zh_job_framed(uint32_t framing, uint32_t eof) { return {0, -1, true, false, true, {framing, eof}}; }
+static int zh_enqueue_stitch(zultra_hip_ctx_t *c, hipStream_t st, const zh_stitch_job_t &job, bool clear);
 static int zh_stitch_verdict(zultra_hip_ctx_t *c, bool scan_only);
+
+static void zh_assembly_clear(zultra_hip_ctx_t *c) { c->held = zh_assembly_t{}; }
+// `job` has been assembled and waited for, rc the verdict on it
+static void zh_assembly_record(zultra_hip_ctx_t *c, const zh_stitch_job_t &job, bool with_batch, int rc) {
+   zh_assembly_clear(c);
+   if (job.scan_only || (rc != 0 && !with_batch)) return;
+   const uint32_t gap = job.framed ? zh_frame_head(job.frame.framing) + zh_frame_tail(job.frame.framing) : 0u;
+   c->held = {job.files ? ZH_LAYOUT_FILES : ZH_LAYOUT_STREAM, job.phase, job.final_block, gap, with_batch, rc};
+}
+static bool zh_assembly_usable(const zultra_hip_ctx_t *c) { return c->held.layout != ZH_LAYOUT_NONE && c->held.rc == 0; }   // the buffer holds a sound assembly ...
+static bool zh_assembly_is_files(const zultra_hip_ctx_t *c) { return c->held.layout == ZH_LAYOUT_FILES; }                    // ... in the files form ...
+static uint32_t zh_assembly_gap(const zultra_hip_ctx_t *c) { return c->held.gap; }                                           // ... with this many bytes between the streams
+// ... in the plain files form: its offsets in d_file_off, its report in d_scan_out (zultra_hip_zip_members)
+static bool zh_assembly_plain_files(const zultra_hip_ctx_t *c) { return zh_assembly_usable(c) && zh_assembly_is_files(c) && zh_assembly_gap(c) == 0; }
+// The batch brought what `job` asks for: *rc is the verdict on it, and nothing needs to be launched
+static bool zh_assembly_brought(const zultra_hip_ctx_t *c, const zh_stitch_job_t &job, int *rc) {
+   const zh_assembly_t &h = c->held;
+   if (!h.with_batch || h.layout != (job.files ? ZH_LAYOUT_FILES : ZH_LAYOUT_STREAM) || (!job.files && (h.phase != job.phase || h.final_block != job.final_block))) return false;
+   *rc = h.rc;
+   return true;
+}
 
 // streams (and payload areas) a context holds for the staggered runs of a batch: ZULTRA_HIP_STREAMS, 0 or unset = auto = four (zh_create_buffers and
 // zultra_hip_context_bytes_on must agree: the host layer budgets batches with the latter)
@@ -1264,7 +1345,7 @@ static int zh_enqueue_files_tail(zultra_hip_ctx_t *c, uint32_t nblocks, hipStrea
    // back here. (Before: a second call, a second synchronisation, 0.4 ms between the two on 65 536-input batches.) The clearing covers the worst case of the batch's
    // input COUNT — a replayed graph sees other sizes.
    ZH_CHECK(c, hipMemsetAsync(c->d_stream, 0, (size_t)zh_min64((uint64_t)c->stream_cap + 16, ((uint64_t)nblocks * ((uint64_t)c->max_block + 16) + 16 + 3) & ~3ull), st0));
-   if (zh_enqueue_stitch(c, st0, 0, -1, 1, false, false) != 0) return -1;
+   if (zh_enqueue_stitch(c, st0, zh_job_files(), false) != 0) return -1;
    ZH_CHECK(c, hipMemcpyAsync(c->h_file_off, c->d_file_off, ((size_t)nblocks + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st0));
    return 0;
 }
@@ -1336,7 +1417,6 @@ static int zh_graph_capture(zultra_hip_ctx_t *c, zh_graph_set_t *G, int g, hipSt
 }
 #endif
 
-
 static int zh_run_files(zultra_hip_ctx_t *c, uint32_t nblocks) {
    hipStream_t st = c->lane_stream[0];
    {
@@ -1397,10 +1477,7 @@ static int zh_run_files(zultra_hip_ctx_t *c, uint32_t nblocks) {
    memcpy(c->crc.data(), c->h_crc, nblocks * sizeof(uint32_t));
    c->adler.assign(c->h_adler, c->h_adler + 2 * (size_t)nblocks);
    c->nsubs = nblocks;
-   c->files_stitch_rc = zh_stitch_verdict(c, false);
-   c->stream_stitched = c->files_stitch_rc == 0 ? 2 : 0;
-   c->frame_gap = 0;
-   c->files_stitched = 1;   // (no stitch_ms of its own: inside a captured graph an event is a node, not a time stamp; the batch's encode_ms covers the assembly)
+   zh_assembly_record(c, zh_job_files(), true, zh_stitch_verdict(c, false));   // (no stitch_ms of its own: inside a captured graph an event is a node, not a time stamp; the batch's encode_ms covers the assembly)
    (void)hipEventElapsedTime(&c->timing.h2d_ms, c->lane_ev[0][ZH_EV_START], c->ev_input);
    (void)hipEventElapsedTime(&c->timing.encode_ms, c->lane_ev[0][ZH_EV_INPUT], c->lane_ev[0][ZH_EV_READBACK]);   // the whole graph
    (void)hipEventElapsedTime(&c->timing.total_ms, c->lane_ev[0][ZH_EV_START], c->lane_ev[0][ZH_EV_READBACK]);
@@ -1561,7 +1638,7 @@ static int zh_read_back(zultra_hip_ctx_t *c, const uint32_t *run_b0, int lanes, 
       // the stitch behind the batch's last kernel (zultra_hip_stitch_with_batch): scan, bit mover and the scan's report before the host's one wait
       // (safe with void runs: zh_compact_results marks the batch, zh_stitch_scan and zh_stitch then write nothing)
       ZH_CHECK(c, hipEventRecord(c->ev_stitch[ZH_STITCH_EV_START], st0));
-      if (zh_enqueue_stitch(c, st0, c->ab_phase, c->ab_final, 0, false, false) != 0) return -1;
+      if (zh_enqueue_stitch(c, st0, c->armed_job, false) != 0) return -1;
    }
    ZH_CHECK(c, hipStreamSynchronize(st0));
    ZH_CHECK(c, hipGetLastError());
@@ -1589,14 +1666,7 @@ static int zh_read_back(zultra_hip_ctx_t *c, const uint32_t *run_b0, int lanes, 
    memcpy(c->crc.data(), c->h_crc, nblocks * sizeof(uint32_t));
    c->adler.assign(c->h_adler, c->h_adler + 2 * (size_t)nblocks);
    c->nsubs = nsubs;
-   if (stitch_now) {
-      c->stitched_rc = zh_stitch_verdict(c, false);
-      c->stream_stitched = c->stitched_rc == 0 ? 1 : 0;
-      c->frame_gap = 0;
-      c->stitched_phase = c->ab_phase;
-      c->stitched_final = c->ab_final;
-      c->stitched_valid = 1;
-   }
+   if (stitch_now) zh_assembly_record(c, c->armed_job, true, zh_stitch_verdict(c, false));
    return 0;
 }
 
@@ -1642,12 +1712,9 @@ extern "C" int zultra_hip_compress_blocks(zultra_hip_ctx_t *c, const void *data,
    ZH_EMU_SERIALIZE();
    if (zh_check_batch(c, data, data_size, data_on_device, blocks, nblocks) != 0) return -1;
    ZH_CHECK(c, hipSetDevice(c->device));
-   const bool stitch_now = c->ab_armed && !c->files_mode;   // (one batch only)
-   c->ab_armed = 0;
-   c->stitched_valid = 0;
-   c->files_stitched = 0;
-   c->stream_stitched = 0;
-   c->frame_gap = 0;   // (whatever assembles this batch — its own graph, a stitch armed with it — lays the plain layout)
+   const bool stitch_now = c->armed && !c->files_mode;   // (one batch only)
+   c->armed = false;
+   zh_assembly_clear(c);   // (whatever assembles this batch — its own graph, a stitch armed with it — lays the plain layout)
    c->nblocks = nblocks;
    c->nsubs = 0;
    c->blocks.assign((const zh_block_t *)blocks, (const zh_block_t *)blocks + nblocks);
@@ -1667,7 +1734,7 @@ extern "C" int zultra_hip_compress_blocks(zultra_hip_ctx_t *c, const void *data,
    bool again = false;
    if (zh_read_back(c, run_b0, lanes, stitch_now, &again) != 0) return -1;
    if (again) {
-      c->ab_armed = stitch_now ? 1 : 0;
+      c->armed = stitch_now;
       return zultra_hip_compress_blocks(c, data, data_size, data_on_device, blocks, nblocks);
    }
    zh_batch_timing(c, lanes, stitch_now);
@@ -1703,16 +1770,26 @@ extern "C" int zultra_hip_block_crc32(const zultra_hip_ctx_t *c, uint32_t *out) 
    return (int)c->nblocks;
 }
 
+// The grid of a kernel that gives every item a lane and strides: -> workgroups of *threads. ZULTRA_HIP_GRID_CAP (tests) caps the LANES here — an item (a member of
+// zh_frame_members, an entry of zh_zip_records) is one lane's work, and a cap on workgroups of 64 would need hundreds of items before a lane saw a second one
+static uint32_t zh_lane_grid(const zultra_hip_ctx_t *c, uint32_t items, uint32_t *threads) {
+   const uint32_t grid = (items + *threads - 1) / *threads;
+   if (!c->grid_cap || (uint64_t)grid * *threads <= c->grid_cap) return grid;
+   *threads = min(*threads, c->grid_cap);
+   return max(1u, c->grid_cap / *threads);
+}
+
 // The stream assembly of the last batch on the device: the scan that decides where every sub-block goes (zh_stitch_scan), then the kernel that puts
 // it there (zh_stitch). files: every max-block a stream of its own. One synchronisation, at the end, for the 80 bytes the scan reports.
 // The stitch of the batch whose descriptors zh_compact_results has laid out (or will have, on `st`): clears what the bits are ORed into — unless the caller
 // has (clear = false) —, the scan, the bit mover, the 80 bytes the scan reports. The grids need no count from the host: the scan is one workgroup, the mover strides
 // over scan->nsubs. Enqueues only.
-// frame (files form only, zultra_hip_frame_members): room for a header and a trailer around every stream, cleared with the rest, and zh_frame_members behind the mover to fill it.
-static int zh_enqueue_stitch(zultra_hip_ctx_t *c, hipStream_t st, uint32_t phase, int final_block, int files, bool scan_only, bool clear, const zh_frame_args_t *frame) {
+// A framed job: the room around every stream is cleared with the rest, and zh_frame_members behind the mover fills it.
+static int zh_enqueue_stitch(zultra_hip_ctx_t *c, hipStream_t st, const zh_stitch_job_t &job, bool clear) {
+   const zh_frame_args_t *frame = job.framed ? &job.frame : NULL;
    const uint32_t head = frame ? zh_frame_head(frame->framing) : 0u, tail = frame ? zh_frame_tail(frame->framing) : 0u, eof = frame ? frame->eof : 0u;
    const uint32_t member_max = frame && frame->framing == ZH_FRAME_BGZF ? ZH_BGZF_MEMBER_MAX : 0u;
-   if (!scan_only && clear && !frame) ZH_CHECK(c, hipMemsetAsync(c->d_stream, 0, zh_stream_clear_bytes(c), st));   // (zero where bits will be ORed in)
+   if (!job.scan_only && clear && !frame) ZH_CHECK(c, hipMemsetAsync(c->d_stream, 0, zh_stream_clear_bytes(c), st));   // (zero where bits will be ORed in)
    // (the inputs of a files context are smaller than any max-block: their streams are assembled with the buffer bound of the smallest)
    const uint32_t block_size = c->max_block < ZH_MIN_BLOCK ? (uint32_t)ZH_MIN_BLOCK : c->max_block;
    // (the scan's chunk tables are 32-bit: a chunk of ceil(nblocks / 1024) max-blocks must stay below 2^32 bits — only HBM capacity has ruled that out so far)
@@ -1721,11 +1798,11 @@ static int zh_enqueue_stitch(zultra_hip_ctx_t *c, hipStream_t st, uint32_t phase
       return -1;
    }
    if (frame)
-      ZH_LAUNCH(zh_stitch_scan<true>, 1, ZH_SCAN_THREADS, st, (const zh_subblock_t *)c->d_results_compact, (const uint32_t *)c->d_nsubs, c->nblocks, phase,
-                files ? block_size : c->max_block, final_block, files, head, tail, member_max, c->d_blk_start, c->d_items, c->d_file_off, c->d_scan_out);
+      ZH_LAUNCH(zh_stitch_scan<true>, 1, ZH_SCAN_THREADS, st, (const zh_subblock_t *)c->d_results_compact, (const uint32_t *)c->d_nsubs, c->nblocks, job.phase,
+                job.files ? block_size : c->max_block, job.final_block, (int)job.files, head, tail, member_max, c->d_blk_start, c->d_items, c->d_file_off, c->d_scan_out);
    else
-      ZH_LAUNCH(zh_stitch_scan<false>, 1, ZH_SCAN_THREADS, st, (const zh_subblock_t *)c->d_results_compact, (const uint32_t *)c->d_nsubs, c->nblocks, phase,
-                files ? block_size : c->max_block, final_block, files, 0u, 0u, 0u, c->d_blk_start, c->d_items, c->d_file_off, c->d_scan_out);
+      ZH_LAUNCH(zh_stitch_scan<false>, 1, ZH_SCAN_THREADS, st, (const zh_subblock_t *)c->d_results_compact, (const uint32_t *)c->d_nsubs, c->nblocks, job.phase,
+                job.files ? block_size : c->max_block, job.final_block, (int)job.files, 0u, 0u, 0u, c->d_blk_start, c->d_items, c->d_file_off, c->d_scan_out);
    if (frame) {
       // (a framed assembly clears behind its scan, which knows how much — and whether: a refused call writes nothing)
       const uint64_t worst = zh_stream_clear_bytes(c, (uint64_t)c->nblocks * (head + tail) + eof);
@@ -1733,19 +1810,15 @@ static int zh_enqueue_stitch(zultra_hip_ctx_t *c, hipStream_t st, uint32_t phase
                 (uint64_t)c->stream_cap - eof, eof, (uint4 *)c->d_stream);
       ZH_CHECK(c, hipEventRecord(c->ev_frame[1], st));
    }
-   if (!scan_only) {
+   if (!job.scan_only) {
       const uint32_t grid = (uint32_t)zh_min64((uint64_t)c->nblocks * c->max_subs, zh_max64(4ull * c->nblocks, 1024));
       ZH_LAUNCH(zh_stitch, grid, ZH_STITCH_THREADS, st, (const zh_subblock_t *)c->d_results_compact, (const zh_stitch_item_t *)c->d_items, (const zh_block_t *)c->d_blocks, c->cur_data,
                 (const uint8_t *)c->d_payload, c->d_stream, (const zh_scan_out_t *)c->d_scan_out, (uint64_t)c->stream_cap - eof);
    }
    if (frame) {
-      // one lane per member and one for the end marker, the kernel strides. ZULTRA_HIP_GRID_CAP (tests) caps the LANES here — a member is one lane's work, and
-      // a cap on workgroups of 64 would need hundreds of members before a lane saw a second one
-      uint32_t threads = ZH_FRAME_THREADS, grid = (c->nblocks + 1 + ZH_FRAME_THREADS - 1) / ZH_FRAME_THREADS;
-      if (c->grid_cap && (uint64_t)grid * threads > c->grid_cap) {
-         threads = min(threads, c->grid_cap);
-         grid = max(1u, c->grid_cap / threads);
-      }
+      // one lane per member and one for the end marker, the kernel strides
+      uint32_t threads = ZH_FRAME_THREADS;
+      const uint32_t grid = zh_lane_grid(c, c->nblocks + 1, &threads);
       ZH_CHECK(c, hipEventRecord(c->ev_frame[2], st));
       ZH_LAUNCH(zh_frame_members, grid, threads, st, (const zh_block_t *)c->d_blocks, c->nblocks, (const uint64_t *)c->d_file_off, (const uint32_t *)c->d_crc, (const uint32_t *)c->d_adler,
                 (const zh_scan_out_t *)c->d_scan_out, (uint64_t)c->stream_cap - eof, frame->framing, member_max, eof, (uint8_t *)c->d_stream, c->d_members);
@@ -1776,43 +1849,40 @@ static int zh_stitch_verdict(zultra_hip_ctx_t *c, bool scan_only) {
 
 // A stitch of the last batch on the context's stream in two halves, so that a caller can put kernels of its own behind the assembly and wait once
 // (zultra_hip_zip_members): what is enqueued, and what the host makes of it after the synchronisation.
-static int zh_stitch_begin(zultra_hip_ctx_t *c, uint32_t phase, int final_block, int files, bool scan_only, const zh_frame_args_t *frame) {
+// The job is kept in the context: the second half reads what the first was given.
+static int zh_stitch_begin(zultra_hip_ctx_t *c, const zh_stitch_job_t &job) {
    ZH_CHECK(c, hipSetDevice(c->device));
    hipStream_t st = c->stream;
-   c->stitched_valid = 0;   // (the items and the scan's report are rewritten)
-   c->files_stitched = 0;
-   c->stream_stitched = 0;
-   c->frame_gap = 0;
+   c->stitch_job = job;
+   zh_assembly_clear(c);   // (the items and the scan's report are rewritten)
    ZH_CHECK(c, hipEventRecord(c->ev_stitch[ZH_STITCH_EV_START], st));
-   if (frame) ZH_CHECK(c, hipEventRecord(c->ev_frame[0], st));
-   return zh_enqueue_stitch(c, st, phase, final_block, files, scan_only, true, frame);
+   if (job.framed) ZH_CHECK(c, hipEventRecord(c->ev_frame[0], st));
+   return zh_enqueue_stitch(c, st, job, true);
 }
-static int zh_stitch_finish(zultra_hip_ctx_t *c, int files, bool scan_only, const zh_frame_args_t *frame) {
-   if (!scan_only) (void)hipEventElapsedTime(&c->timing.stitch_ms, c->ev_stitch[ZH_STITCH_EV_START], c->ev_stitch[ZH_STITCH_EV_END]);
-   if (frame)
+static int zh_stitch_finish(zultra_hip_ctx_t *c) {
+   const zh_stitch_job_t &job = c->stitch_job;
+   if (!job.scan_only) (void)hipEventElapsedTime(&c->timing.stitch_ms, c->ev_stitch[ZH_STITCH_EV_START], c->ev_stitch[ZH_STITCH_EV_END]);
+   if (job.framed)
       for (int i = 0; i < 3; i++) (void)hipEventElapsedTime(&c->frame_ms[i], c->ev_frame[i], c->ev_frame[i + 1]);
-   int rc = zh_stitch_verdict(c, scan_only);
-   if (frame && c->h_scan_out->nsubs == c->nsubs && !c->h_scan_out->failed) {   // (what a framed assembly reports of its own; the end marker needs its room too)
+   int rc = zh_stitch_verdict(c, job.scan_only);
+   if (job.framed && c->h_scan_out->nsubs == c->nsubs && !c->h_scan_out->failed) {   // (what a framed assembly reports of its own; the end marker needs its room too)
       if (c->h_scan_out->oversize) {
          snprintf(c->err, sizeof(c->err), "a max-block, or its member, is larger than a BGZF member can be (%u bytes)", ZH_BGZF_MEMBER_MAX);
          rc = -3;
       }
-      else if (((c->h_scan_out->end_bit + 7) >> 3) + 8 + frame->eof > c->stream_cap) {
+      else if (((c->h_scan_out->end_bit + 7) >> 3) + 8 + job.frame.eof > c->stream_cap) {
          snprintf(c->err, sizeof(c->err), "the framed members do not fit the stream buffer");
          rc = -2;
       }
    }
-   if (!scan_only && rc == 0) {
-      c->stream_stitched = files ? 2 : 1;
-      if (frame) c->frame_gap = zh_frame_head(frame->framing) + zh_frame_tail(frame->framing);
-   }
+   zh_assembly_record(c, job, false, rc);
    return rc;
 }
-static int zh_stitch_on_device(zultra_hip_ctx_t *c, uint32_t phase, int final_block, int files, bool scan_only = false, const zh_frame_args_t *frame = NULL) {
-   if (zh_stitch_begin(c, phase, final_block, files, scan_only, frame) != 0) return -1;
+static int zh_stitch_on_device(zultra_hip_ctx_t *c, const zh_stitch_job_t &job) {
+   if (zh_stitch_begin(c, job) != 0) return -1;
    ZH_CHECK(c, hipStreamSynchronize(c->stream));
    ZH_CHECK(c, hipGetLastError());
-   return zh_stitch_finish(c, files, scan_only, frame);
+   return zh_stitch_finish(c);
 }
 
 // The next batch of max-blocks (zultra_hip_compress_blocks) is stitched at bit phase `phase` (final_block as for zultra_hip_stitch_device) BEHIND ITS LAST KERNEL,
@@ -1822,9 +1892,8 @@ static int zh_stitch_on_device(zultra_hip_ctx_t *c, uint32_t phase, int final_bl
 // stitches again as before. One batch only: the setting is consumed by the batch. Not for files contexts.
 extern "C" int zultra_hip_stitch_with_batch(zultra_hip_ctx_t *c, int enable, uint32_t phase, int final_block) {
    if (!c || c->files_mode) return -1;
-   c->ab_armed = enable ? 1 : 0;
-   c->ab_phase = phase & 7u;
-   c->ab_final = final_block;
+   c->armed = enable != 0;
+   c->armed_job = zh_job_stream(phase, final_block);
    return 0;
 }
 
@@ -1834,8 +1903,9 @@ extern "C" int zultra_hip_stitch_with_batch(zultra_hip_ctx_t *c, int enable, uin
 extern "C" int zultra_hip_stitch_device(zultra_hip_ctx_t *c, zultra_hip_bitstate_t *state, int final_block, uint64_t *end_bit) {
    ZH_EMU_SERIALIZE();
    if (!c || !state || !end_bit || c->nsubs == 0) return -1;
-   // (a stitch that went out with the batch, zultra_hip_stitch_with_batch: its result is at hand)
-   const int rc = (c->stitched_valid && c->stitched_phase == (state->nacc & 7u) && c->stitched_final == final_block) ? c->stitched_rc : zh_stitch_on_device(c, state->nacc & 7u, final_block, 0);
+   const zh_stitch_job_t job = zh_job_stream(state->nacc, final_block);
+   int rc;
+   if (!zh_assembly_brought(c, job, &rc)) rc = zh_stitch_on_device(c, job);   // (a stitch that went out with the batch, zultra_hip_stitch_with_batch: its result is at hand)
    if (rc != 0) return rc;
    const uint64_t eb = c->h_scan_out->end_bit;
    state->nacc = (uint32_t)(eb & 7);
@@ -1850,7 +1920,7 @@ extern "C" int zultra_hip_stitch_device(zultra_hip_ctx_t *c, zultra_hip_bitstate
 extern "C" int zultra_hip_stitch_phase_table(zultra_hip_ctx_t *c, uint64_t *end_bits /* 8 */, uint32_t *failed_mask) {
    ZH_EMU_SERIALIZE();
    if (!c || !end_bits || c->nsubs == 0 || c->files_mode) return -1;
-   const int rc = zh_stitch_on_device(c, 0, -1, 0, true);
+   const int rc = zh_stitch_on_device(c, zh_job_stream(0, -1, true));
    if (rc != 0) return rc;
    for (int p = 0; p < 8; p++) end_bits[p] = c->h_scan_out->table_end[p];
    if (failed_mask) *failed_mask = c->h_scan_out->table_failed;
@@ -1863,16 +1933,14 @@ extern "C" int zultra_hip_stitch_phase_table(zultra_hip_ctx_t *c, uint64_t *end_
 extern "C" int zultra_hip_stitch_files(zultra_hip_ctx_t *c, uint64_t *file_off /* nblocks + 1 */) {
    ZH_EMU_SERIALIZE();
    if (!c || !file_off || c->nsubs == 0) return -1;
-   if (!c->d_file_off) {   // (a context of max-blocks: allocated on first use)
-      ZH_CHECK(c, hipSetDevice(c->device));
-      if (zh_alloc(c, &c->d_file_off, (size_t)c->max_blocks + 1)) return -1;
+   ZH_CHECK(c, hipSetDevice(c->device));
+   if (zh_need_file_off(c)) return -1;
+   int rc;
+   if (zh_assembly_brought(c, zh_job_files(), &rc)) {   // (a files context's batch brings its assembly with it, zh_enqueue_files_tail)
+      if (rc == 0) memcpy(file_off, c->h_file_off, ((size_t)c->nblocks + 1) * sizeof(uint64_t));
+      return rc;
    }
-   if (c->files_mode && c->files_stitched) {   // (the batch brought its assembly with it, zh_enqueue_files_tail)
-      if (c->files_stitch_rc != 0) return c->files_stitch_rc;
-      memcpy(file_off, c->h_file_off, ((size_t)c->nblocks + 1) * sizeof(uint64_t));
-      return 0;
-   }
-   const int rc = zh_stitch_on_device(c, 0, -1, 1);
+   rc = zh_stitch_on_device(c, zh_job_files());
    if (rc != 0) return rc;
    ZH_CHECK(c, hipMemcpy(file_off, c->d_file_off, ((size_t)c->nblocks + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost));
    return 0;
@@ -1895,15 +1963,12 @@ extern "C" int zultra_hip_frame_members(zultra_hip_ctx_t *c, unsigned int framin
          return -1;
       }
    ZH_CHECK(c, hipSetDevice(c->device));
-   if (!c->d_file_off && zh_alloc(c, &c->d_file_off, (size_t)c->max_blocks + 1)) return -1;
-   if (!c->d_members && zh_alloc(c, &c->d_members, (size_t)c->max_blocks)) return -1;
-   for (int i = 0; i < 4; i++)
-      if (!c->ev_frame[i]) ZH_CHECK(c, hipEventCreate(&c->ev_frame[i]));
-   const zh_frame_args_t frame = {framing, (framing == ZH_FRAME_BGZF && bgzf_eof) ? ZH_BGZF_EOF_SIZE : 0u};
-   const int rc = zh_stitch_on_device(c, 0, -1, 1, false, &frame);
+   if (zh_need_file_off(c) || zh_need_frame(c)) return -1;
+   const zh_stitch_job_t job = zh_job_framed(framing, (framing == ZH_FRAME_BGZF && bgzf_eof) ? ZH_BGZF_EOF_SIZE : 0u);
+   const int rc = zh_stitch_on_device(c, job);
    if (rc != 0 && rc != -3) return rc;
    ZH_CHECK(c, hipMemcpy(members, c->d_members, (size_t)c->nblocks * sizeof(zh_member_t), hipMemcpyDeviceToHost));
-   if (rc == 0) *total_bytes = members[c->nblocks - 1].off + members[c->nblocks - 1].size + frame.eof;
+   if (rc == 0) *total_bytes = members[c->nblocks - 1].off + members[c->nblocks - 1].size + job.frame.eof;
    return rc;
 }
 extern "C" void zultra_hip_last_frame_ms(const zultra_hip_ctx_t *c, float *ms /* [3]: scan, mover, frame kernel */) {
@@ -1955,8 +2020,8 @@ extern "C" int zultra_hip_zip_members(zultra_hip_ctx_t *c, const void *names, co
    }
    ZH_CHECK(c, hipSetDevice(c->device));
    hipStream_t st = c->stream;
-   const bool assembled = c->stream_stitched == 2 && c->frame_gap == 0;   // (the plain files form is in the stream buffer, its offsets in d_file_off, its report in d_scan_out)
-   if (!c->d_file_off && zh_alloc(c, &c->d_file_off, (size_t)c->max_blocks + 1)) return -1;
+   const bool assembled = zh_assembly_plain_files(c);   // (the plain files form is in the stream buffer, its offsets in d_file_off, its report in d_scan_out)
+   if (zh_need_file_off(c) || zh_need_zip(c)) return -1;
    // what the call brings: name_off, entry_block, names — one upload
    const uint32_t names_bytes = name_off[n] - name_off[0];
    const size_t in_words = (size_t)n + 1 + (entry_block ? n : 0) + ((size_t)names_bytes + 3) / 4;
@@ -1967,11 +2032,6 @@ extern "C" int zultra_hip_zip_members(zultra_hip_ctx_t *c, const void *names, co
    if (n > c->zip_entries_cap) {
       if (zh_zip_grow(c, &c->d_zip_entries, 0, n, false) || zh_zip_grow(c, &c->d_zip_src, 0, n, false)) return -1;
       c->zip_entries_cap = n;
-   }
-   if (!c->d_zip_report) {
-      if (zh_alloc(c, &c->d_zip_report, 1)) return -1;
-      ZH_CHECK(c, hipHostMalloc((void **)&c->h_zip_report, sizeof(zh_zip_report_t), 0));
-      for (int i = 0; i < 4; i++) ZH_CHECK(c, hipEventCreate(&c->ev_zip[i]));
    }
    // the buffer: the headers and names, and what the streams take — known where the assembly is, else at most what a stitch clears for this batch
    const uint64_t streams = assembled ? (c->h_scan_out->end_bit + 7) >> 3 : (uint64_t)zh_stream_clear_bytes(c);
@@ -1990,18 +2050,14 @@ extern "C" int zultra_hip_zip_members(zultra_hip_ctx_t *c, const void *names, co
    const uint32_t *d_name_off = c->d_zip_in, *d_entry_block = entry_block ? c->d_zip_in + n + 1 : NULL;
    const uint8_t *d_names = (const uint8_t *)(c->d_zip_in + names_word) - name_off[0];   // (name i is at d_names + name_off[i])
 
-   if (!assembled && zh_stitch_begin(c, 0, -1, 1, false, NULL) != 0) return -1;
+   if (!assembled && zh_stitch_begin(c, zh_job_files()) != 0) return -1;
    ZH_CHECK(c, hipEventRecord(c->ev_zip[0], st));
    ZH_LAUNCH(zh_zip_scan, 1, ZH_ZIP_SCAN_THREADS, st, d_name_off, d_entry_block, n, (const zh_block_t *)c->d_blocks, (const uint64_t *)c->d_file_off,
              (const zh_scan_out_t *)c->d_scan_out, (uint64_t)c->stream_cap, base_off, c->d_zip_entries, c->d_zip_src, c->d_zip_report);
    ZH_CHECK(c, hipEventRecord(c->ev_zip[1], st));
    {
-      // one lane per entry; ZULTRA_HIP_GRID_CAP (tests) caps the LANES, as for zh_frame_members
-      uint32_t threads = ZH_ZIP_RECORD_THREADS, grid = (n + ZH_ZIP_RECORD_THREADS - 1) / ZH_ZIP_RECORD_THREADS;
-      if (c->grid_cap && (uint64_t)grid * threads > c->grid_cap) {
-         threads = min(threads, c->grid_cap);
-         grid = max(1u, c->grid_cap / threads);
-      }
+      uint32_t threads = ZH_ZIP_RECORD_THREADS;   // (one lane per entry)
+      const uint32_t grid = zh_lane_grid(c, n, &threads);
       ZH_LAUNCH(zh_zip_records, grid, threads, st, c->d_zip_entries, (const uint64_t *)c->d_zip_src, d_name_off, d_names, d_entry_block, (const uint32_t *)c->d_crc, n, base_off,
                 dos_datetime ? dos_datetime : 0x00210000u, central_at, (const zh_zip_report_t *)c->d_zip_report, c->d_zip);
    }
@@ -2029,7 +2085,7 @@ extern "C" int zultra_hip_zip_members(zultra_hip_ctx_t *c, const void *names, co
    ZH_CHECK(c, hipGetLastError());
    for (int i = 0; i < 3; i++) (void)hipEventElapsedTime(&c->zip_ms[i], c->ev_zip[i], c->ev_zip[i + 1]);
    if (!assembled) {
-      const int rc = zh_stitch_finish(c, 1, false, NULL);
+      const int rc = zh_stitch_finish(c);
       if (rc != 0) return rc;
    }
    if (c->h_zip_report->failed) {
@@ -2093,17 +2149,13 @@ extern "C" int zultra_hip_verify_device(zultra_hip_ctx_t *c, zultra_hip_verify_t
    if (!c || !report) return -1;
    memset(report, 0, sizeof(*report));
    report->first_bad = 0xFFFFFFFFu;
-   if (!c->stream_stitched || c->nsubs == 0) {
+   if (!zh_assembly_usable(c) || c->nsubs == 0) {
       snprintf(c->err, sizeof(c->err), "nothing to verify: the stream buffer holds no stitched batch");
       return -1;
    }
    ZH_CHECK(c, hipSetDevice(c->device));
-   if (!c->d_vitems) {
-      if (zh_alloc(c, &c->d_vitems, (size_t)c->max_blocks * c->max_subs) || zh_alloc(c, &c->d_vreport, 1)) return -1;
-      ZH_CHECK(c, hipHostMalloc((void **)&c->h_vreport, sizeof(zh_verify_report_t), 0));
-      for (int i = 0; i < 2; i++) ZH_CHECK(c, hipEventCreate(&c->ev_verify[i]));
-   }
-   const int files = c->stream_stitched == 2;
+   if (zh_need_verify(c)) return -1;
+   const int files = zh_assembly_is_files(c);
    hipStream_t st = c->stream;
    ZH_CHECK(c, hipMemsetAsync(c->d_vreport, 0, sizeof(zh_verify_report_t), st));
    ZH_CHECK(c, hipMemsetAsync(&c->d_vreport->first_bad, 0xff, sizeof(uint32_t), st));
@@ -2111,7 +2163,7 @@ extern "C" int zultra_hip_verify_device(zultra_hip_ctx_t *c, zultra_hip_verify_t
    const uint32_t grid = (uint32_t)zh_min64(c->nsubs, zh_max64(12ull * c->total_cus, 64));   // (one wave per workgroup, three to a SIMD — zh_verify.h: a CU holds 12; more would only queue)
    ZH_LAUNCH(zh_verify_subblocks, grid, ZH_VERIFY_THREADS, st, (const uint32_t *)c->d_stream, (uint64_t)c->stream_cap, (const zh_stitch_item_t *)c->d_items,
              (const zh_subblock_t *)c->d_results_compact, (const zh_block_t *)c->d_blocks, c->nblocks, c->cur_data, (const zh_scan_out_t *)c->d_scan_out, (const uint64_t *)c->d_file_off, files,
-             c->frame_gap, c->d_vitems, c->d_vreport);
+             zh_assembly_gap(c), c->d_vitems, c->d_vreport);
    ZH_CHECK(c, hipEventRecord(c->ev_verify[1], st));
    ZH_CHECK(c, hipMemcpyAsync(c->h_vreport, c->d_vreport, sizeof(zh_verify_report_t), hipMemcpyDeviceToHost, st));
    ZH_CHECK(c, hipStreamSynchronize(st));

@@ -11,6 +11,8 @@ CSRC = os.path.join(ROOT, "zultra_amd", "csrc")
 OUT = os.path.join(HERE, "_build", "libzultra_amd_emu.so")
 NOTES_MAIN = os.path.join(HERE, "mf_notes_main.cpp")
 NOTES_OUT = os.path.join(HERE, "_build", "mf_notes_main")
+LIFECYCLE_MAIN = os.path.join(HERE, "ctx_lifecycle_main.cpp")
+LIFECYCLE_OUT = os.path.join(HERE, "_build", "ctx_lifecycle_main")
 LSAN_SUPPRESSIONS = os.path.join(HERE, "lsan_suppressions.txt")
 
 # the emulator configuration: small chunks, cuts and matchfinder chunks, so that windows of a few KB take every path
@@ -40,19 +42,28 @@ def build(force=False):
     return OUT
 
 
-def build_notes_program(force=False):
-    """tests/emu/_build/mf_notes_main: mf_notes_main.cpp and the three emulator sources as ONE EXECUTABLE with AddressSanitizer and UBSan — run as a
-    process of its own (tests/test_mf_classes_emu.py), never loaded into Python. LeakSanitizer is told to pass over the emulator's fibre stacks, which
-    live as long as the process (lsan_suppressions.txt)."""
-    if not force and _fresh(NOTES_OUT, (NOTES_MAIN,)):
-        return NOTES_OUT
-    os.makedirs(os.path.dirname(NOTES_OUT), exist_ok=True)
+def _build_program(main, out, force):
+    """main and the three emulator sources as ONE EXECUTABLE with AddressSanitizer and UBSan — run as a process of its own, never loaded into Python.
+    LeakSanitizer is told to pass over the emulator's fibre stacks, which live as long as the process (lsan_suppressions.txt)."""
+    if not force and _fresh(out, (main,)):
+        return out
+    os.makedirs(os.path.dirname(out), exist_ok=True)
     # (the sanitizers' runtimes linked into the executable: it runs whatever else the process loads)
-    cmd = ["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-omit-frame-pointer", "-static-libasan", "-static-libubsan"] + WARNINGS + DEFINES + _sources() + [NOTES_MAIN, "-lpthread", "-o"]
-    tmp = "%s.%d.tmp" % (NOTES_OUT, os.getpid())
+    cmd = ["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-omit-frame-pointer", "-static-libasan", "-static-libubsan"] + WARNINGS + DEFINES + _sources() + [main, "-lpthread", "-o"]
+    tmp = "%s.%d.tmp" % (out, os.getpid())
     subprocess.run(cmd + [tmp], check=True)
-    os.replace(tmp, NOTES_OUT)
-    return NOTES_OUT
+    os.replace(tmp, out)
+    return out
+
+
+def build_notes_program(force=False):
+    """tests/emu/_build/mf_notes_main: zultra_memory_compress on a file (tests/test_mf_classes_emu.py)."""
+    return _build_program(NOTES_MAIN, NOTES_OUT, force)
+
+
+def build_lifecycle_program(force=False):
+    """tests/emu/_build/ctx_lifecycle_main: contexts created, used and destroyed (tests/test_context_layout_emu.py)."""
+    return _build_program(LIFECYCLE_MAIN, LIFECYCLE_OUT, force)
 
 
 if __name__ == "__main__":

@@ -634,16 +634,17 @@ def test_cached_contexts_are_released_on_request(gpu):
     g = gpu.L.zultra_hip_context_bytes
     g.argtypes = [C.c_uint32, C.c_uint32]
     g.restype = C.c_size_t
-    ctx = gpu.context(65536, 64)
-    try:
-        info = (C.c_int(), C.c_uint32(), C.c_uint32(), C.c_size_t())
-        gpu.L.zultra_hip_ctx_info.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_size_t)]
-        gpu.L.zultra_hip_ctx_info(ctx.h, *[C.byref(x) for x in info])
-        assert (info[1].value, info[2].value) == (65536, 64)
-        est = g(65536, 64)
-        assert 0.95 * info[3].value <= est <= 1.10 * info[3].value, (est, info[3].value)   # the estimate follows the real layout
-    finally:
-        ctx.close()
+    gpu.L.zultra_hip_ctx_info.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_size_t)]
+    for shape in ((65536, 64), (65536, 1), (1048576, 2)):
+        ctx = gpu.context(*shape)
+        try:
+            info = (C.c_int(), C.c_uint32(), C.c_uint32(), C.c_size_t())
+            gpu.L.zultra_hip_ctx_info(ctx.h, *[C.byref(x) for x in info])
+            assert (info[1].value, info[2].value) == shape
+            est = g(*shape)
+            assert est == info[3].value, (shape, est, info[3].value)   # the estimate is the sum over the list the creation allocates from
+        finally:
+            ctx.close()
 
 
 def test_api_state_machine_on_the_device(gpu, checker):

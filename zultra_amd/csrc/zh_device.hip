@@ -1,22 +1,6 @@
-// zh_device.hip — host side of the device layer: context, HBM layout, launches (C ABI of include/zultra_hip.h). The calls that need no context — batched
+// zh_device.hip — host side of the device layer: context, memory layout, launches (C ABI of include/zultra_hip.h). The calls that need no context — batched
 // inflate, the member index, a whole file — are in zh_inflate.hip; what both files' host code needs, in zh_host.h.
-//
-// HBM layout of one context (B = max_blocks, N = max_block_size; S = matchfinder segments per max-block, 1 up to 64 KiB,
-// Ws = segment window, <= 96 KiB: zh_common.h):
-//   d_data     N + 32768 + (B-1)*N   input bytes when the caller hands over host memory (read in place otherwise)
-//   d_blocks   B * 16                max-block descriptors;  d_segs  B * S * 32  matchfinder segments
-//   d_sort_a/b B * S * Ws * 4  each  window positions in trigram / 4-gram-hash order (ping-pong of the radix sorts)
-//   d_prev3    B * S * Ws * 8        previous occurrence of the trigram, 4-gram and 5-gram at every window position
-//   d_runs     B * S * (Ws + 576) * 4  byte-run table of every segment window, behind it the notes for zh_mf_group_big (more than 576 with a small ZULTRA_HIP_MF_CAP: zh_mf_run_stride)
-//   d_match    B * N * 32            match rows, 8 x {u16 length, u16 offset} per block position
-//   d_tok_pos  B * N * 4, d_tok_info B * N * 2   greedy token chain: position / packed symbols
-//   d_bars     B * N / 8             barrier bitmap of every max-block (zh_parse.h)
-//   d_best     B * N * 4             final parse per position
-//   d_payload  B * (N + 4224)        per-sub-block bit strings (slot of sub-block k of a block starts at its offset + 64k)
-//   d_states   B * 64 * 1.4 KB       per-sub-block coder state between the kernels of stage 3 (64 -> 1 in files mode)
-//   d_taskmap, d_hist_part, d_task_bits   per task (T = B * (N / 2048 + 64)): owner, 320-counter histogram, bit count
-//   d_stream   B * (N + ...)         stitched deflate bytes of the last batch;  d_crc / d_adler  per max-block checksums
-//   small: ntok, split boundaries, counts, work items, results (+ pinned host mirrors of everything the host reads)
+// The memory layout of a context is the list ZH_CTX_BUFFERS below: creation, release and the size estimate all walk it.
 #include <zh_platform.h>
 
 #include <stdio.h>
@@ -535,137 +519,200 @@ extern "C" int zultra_hip_device_count(void) {
    return n;
 }
 
-template <typename T>
-static int zh_alloc(zultra_hip_ctx_t *c, T **p, size_t count) {
-   ZH_CHECK(c, hipMalloc((void **)p, count * sizeof(T)));
-   c->device_bytes += count * sizeof(T);
+// ---- the context's buffers ---------------------------------------------------------------------------------------------------------------------------------
+// The shape of a context — everything that sizes a buffer — from what it is created for: the only place these formulas are. zh_create fills the context it then
+// allocates, zultra_hip_context_bytes_on a context-shaped value that it never allocates. (The CU count enters d_pay alone.)
+static void zh_shape(zultra_hip_ctx_t *c, uint32_t max_block, uint32_t max_blocks, int files_mode, uint32_t cus, int lanes, uint32_t mf_cap) {
+   const uint64_t N = max_block, B = max_blocks;
+   c->files_mode = files_mode;
+   c->max_block = max_block;
+   c->max_blocks = max_blocks;
+   c->total_cus = cus;
+   c->num_cus = cus;   // what the persistent kernels may fill (keeping 8..32 CUs free for the chain kernels was measured in round 3: +3 ms per 100 MB)
+   c->nlanes = lanes;
+   c->max_subs = files_mode ? 1u : (uint32_t)ZH_MAX_SPLITS;
+   c->W = N + (files_mode ? 0u : (uint32_t)ZH_HISTORY);
+   if (c->W <= ZH_SEG_WINDOW) {   // a max-block is one matchfinder segment
+      c->seg_n = max_block;
+      c->segs_per_block = 1;
+      c->seg_W = (uint32_t)c->W;
+   }
+   else {
+      c->seg_n = ZH_SEG_POSITIONS;
+      c->segs_per_block = (max_block + ZH_SEG_POSITIONS - 1) / ZH_SEG_POSITIONS;
+      c->seg_W = ZH_SEG_WINDOW;
+   }
+   c->sort_stride = ((uint64_t)c->seg_W + 63) & ~63ull;
+   // the chunk size of zh_mf_group, and the segments' run tables — start[Q] length[Q] first[256] end[256] count, Q = W/4 + 1 — with the note table sized for it: every
+   // class the chunks cannot take has its note, whatever the value (with the default: 29 notes in run tables of sort_stride + 576 words; zh_mf_group_lds.h has the bound)
+   c->mf_lds_cap = mf_cap;
+   c->run_stride = zh_mf_run_stride(c->sort_stride, mf_cap);
+   c->match_stride = N * ZH_NMATCH;
+   c->tok_stride = (N + 63) & ~63ull;
+   c->chunks_per_block = (max_block + ZH_TOK_CHUNK_SMALL - 1) / ZH_TOK_CHUNK_SMALL;   // (what the per-chunk arrays hold: the small chunks of a small batch)
+   c->best_stride = c->tok_stride;
+   c->bar_stride = c->tok_stride / 64;
+   c->slot_stride = ((N + 64 * c->max_subs + 64) + 63) & ~63ull;
+   c->max_tasks = B * (N / ZH_TASK + c->max_subs);
+   // a cut task has at least 2 * ZH_CUT_WARM positions (the floor of ZH_CUT_MIN) and lies inside one max-block
+   c->seg_tasks_per_block = files_mode ? 1 : N / (2u * ZH_CUT_WARM) + 1;
+   c->seg_items_per_block = files_mode ? 1 : N / ZH_CUT_WARM + ZH_CUT_ROWS * (N / (2u * ZH_CUT_WARM) + 1) + 2;   // a task of len positions has at most len / ZH_CUT_LEN + ZH_CUT_ROWS segments
+   c->data_cap = (size_t)c->W + (size_t)(max_blocks - 1) * max_block;
+   c->stream_cap = (size_t)(B * (N + 5 * (N / 65535 + 1) + 8 + ZH_FRAME_ROOM) + 64) & ~(size_t)3;   // (+ 64: slack, and BGZF's end marker)
+}
+
+// The sets a buffer can belong to: it is allocated with the first of its sets that is asked for. CORE, and FILES or BLOCKS by the kind of context, at creation — TRACE
+// too under ZULTRA_HIP_CHAIN_TRACE=1 (zh_creation_sets); the others by the first call that needs them (zh_need_*).
+enum { ZH_SET_CORE = 1, ZH_SET_FILES = 2, ZH_SET_BLOCKS = 4, ZH_SET_TRACE = 8, ZH_SET_FILE_OFF = 16, ZH_SET_VERIFY = 32, ZH_SET_FRAME = 64, ZH_SET_ZIP = 128, ZH_SET_ALL = 255 };
+#define ZH_TRACE_WORDS ((size_t)3 * ZH_TRACE_SLOTS * 4 * ZH_MAX_RUNS)   // (zultra_hip_chain_trace returns the first four runs)
+
+// Every buffer a context owns, stated once: X(sets, kind, field, count) — device (DEV) or pinned host (PIN) memory, the context field, whose own type gives the element
+// size, and the element count as an expression of the shape (B max-blocks, S segments and U sub-blocks of them, T tasks). Creation, the sets of first use, the size
+// estimate and zultra_hip_destroy all walk it (zh_buffers): a new buffer is one new line. Count 0: a buffer that its user grows (zh_zip_grow, zultra_hip_staging) and the
+// list only releases. The core entries stand in the order they are allocated in.
+#define ZH_CTX_BUFFERS(X)                                                                                                                                              \
+   X(ZH_SET_TRACE, DEV, d_chain_trace, ZH_TRACE_WORDS)          /* diagnostics: [run][pass][ticket] {positions, start, end} of the chain kernels */                     \
+   X(ZH_SET_CORE, DEV, d_results_compact, U)                    /* the runs' sub-block descriptors laid end to end (zh_stitch.h) */                                      \
+   X(ZH_SET_CORE, PIN, h_nsubs, 1 + ZH_MAX_RUNS)                /* mirror of d_nsubs */                                                                                  \
+   X(ZH_SET_CORE, PIN, h_scan_out, 1)                           /* mirror of d_scan_out, read after the one synchronisation of a stitch */                               \
+   X(ZH_SET_CORE, PIN, h_grids, 2 * ZH_MAX_RUNS)                /* what goes into the counters ZH_CNT_SBGRID, ZH_CNT_TASKGRID of runs without <true> forms */            \
+   X(ZH_SET_CORE, PIN, h_crc, B)                                /* mirror of d_crc */                                                                                    \
+   X(ZH_SET_CORE, PIN, h_blocks, B)                             /* staging of the batch's descriptors: an async copy from pageable memory is a blocking, staged one */   \
+   X(ZH_SET_FILES, PIN, h_task_prefix, B + 1)                   /* staging of d_task_prefix */                                                                           \
+   X(ZH_SET_FILES, PIN, h_file_off, B + 1)                      /* d_file_off, read back with the batch (zh_enqueue_files_tail) */                                       \
+   X(ZH_SET_CORE, PIN, h_segs, B * S)                           /* staging of d_segs */                                                                                  \
+   X(ZH_SET_CORE, PIN, h_ntasks, 2 * ZH_NCNT)                   /* a mirror of d_ntasks + per-run readbacks (zultra_hip_last_stats) */                                   \
+   X(ZH_SET_CORE, PIN, h_adler, 2 * B)                          /* mirror of d_adler */                                                                                  \
+   X(ZH_SET_CORE, PIN, h_results, U)                            /* mirror of d_results */                                                                                \
+   X(ZH_SET_CORE, DEV, d_bars, B * c->bar_stride)               /* barrier bitmap of every max-block (zh_parse.h) */                                                     \
+   X(ZH_SET_CORE, DEV, d_states, U)                             /* per sub-block: coder state between the kernels of stage 3 */                                          \
+   X(ZH_SET_CORE, DEV, d_taskmap, T)                            /* per task: its owner */                                                                                \
+   X(ZH_SET_CORE, DEV, d_taskinfo, T)                           /* per task: its range and whether zh_list_huge listed it (zh_parse_chain.h) */                          \
+   X(ZH_SET_CORE, DEV, d_nsubs, 1 + ZH_MAX_RUNS)                /* sub-blocks of the batch: total and per run */                                                         \
+   X(ZH_SET_CORE, DEV, d_blk_start, B + 1)                      /* the first sub-block of every max-block */                                                             \
+   X(ZH_SET_CORE, DEV, d_scan_out, 1)                           /* what the scan of a stitch reports */                                                                  \
+   X(ZH_SET_FILES | ZH_SET_FILE_OFF, DEV, d_file_off, B + 1)    /* files form: first byte of every max-block's stream */                                                 \
+   X(ZH_SET_FILES, DEV, d_task_prefix, B + 1)                   /* exclusive prefix of the inputs' task counts, from the host (zh_plan_files) */                         \
+   X(ZH_SET_CORE, DEV, d_prev3, B * S * c->sort_stride)         /* per window position: previous trigram occurrence | distances of the previous 4-gram / 5-gram one */   \
+   X(ZH_SET_CORE, DEV, d_runs, B * S * c->run_stride)           /* byte-run table of every segment window, behind it the notes for zh_mf_group_big */                    \
+   X(ZH_SET_CORE, DEV, d_segs, B * S)                           /* matchfinder segments (zh_common.h) */                                                                 \
+   X(ZH_SET_CORE, DEV, d_chunk_ctr, 2 * B * S + 3 * ZH_MAX_RUNS) /* per segment {next chunk to hand out, workgroups serving it}, then the runs' segment tickets */      \
+   X(ZH_SET_CORE, DEV, d_ntasks, ZH_NCNT)                       /* the runs' counters, ZH_CNT_STRIDE words per run (zh_parse.h) */                                       \
+   X(ZH_SET_CORE, DEV, d_hugelist, 4 * T)                       /* the tasks zh_list_huge lists for zh_parse_chain */                                                    \
+   X(ZH_SET_BLOCKS, DEV, d_lanelist, ZH_LANE_CLASSES * T)       /* the bundles of zh_parse_lanes by length class, ZH_LANE_CLASSES lists per run (zh_parse.h) */          \
+   X(ZH_SET_BLOCKS, DEV, d_lane_acc, T)                         /* ... and the word per task they are gathered in */                                                     \
+   X(ZH_SET_CORE, DEV, d_segtasks, B * c->seg_tasks_per_block)  /* tasks cut into speculative segments (zh_parse_chain.h) */                                             \
+   X(ZH_SET_CORE, DEV, d_segwaves, B * c->seg_items_per_block)  /* their segments as segment waves of zh_parse_lanes' launch (four segments each) */                     \
+   X(ZH_SET_CORE, DEV, d_segitems, B * c->seg_items_per_block)  /* ... or as jobs of zh_parse_chain */                                                                   \
+   X(ZH_SET_CORE, DEV, d_vecs, B * c->seg_items_per_block * 2 * ZH_VEC) /* two cost vectors per segment */                                                              \
+   X(ZH_SET_CORE, DEV, d_hist_part, T * ZH_NSYM)                /* per task: histogram of its symbols */                                                                 \
+   X(ZH_SET_CORE, DEV, d_task_bits, T)                          /* per task: bit count */                                                                                \
+   X(ZH_SET_CORE, DEV, d_data, c->data_cap + 64)                /* input bytes when the caller hands over host memory (read in place otherwise) */                       \
+   X(ZH_SET_CORE, DEV, d_blocks, B)                             /* max-block descriptors */                                                                              \
+   X(ZH_SET_CORE, DEV, d_sort_a, B * S * c->sort_stride)        /* window positions in trigram / 4-gram-hash order ... */                                                \
+   X(ZH_SET_CORE, DEV, d_sort_b, B * S * c->sort_stride)        /* ... ping-pong of the radix sorts */                                                                   \
+   X(ZH_SET_CORE, DEV, d_match, B * c->match_stride)            /* match rows, ZH_NMATCH x {u16 length, u16 offset} per block position */                                \
+   X(ZH_SET_CORE, DEV, d_pay, c->nlanes * zh_min64(c->total_cus, B * S) * 3 * c->sort_stride) /* zh_mf_group: payload of the refining sort passes, per run (their kernels may overlap) and workgroup */ \
+   X(ZH_SET_CORE, DEV, d_tok_pos, B * c->tok_stride)            /* greedy token chain: position ... */                                                                   \
+   X(ZH_SET_CORE, DEV, d_tok_info, B * c->tok_stride)           /* ... and packed symbols */                                                                             \
+   X(ZH_SET_CORE, DEV, d_ntok, B)                               /* tokens of every max-block */                                                                          \
+   X(ZH_SET_CORE, DEV, d_chunkmax, B * c->chunks_per_block)     /* per chunk of ZH_TOK_CHUNK positions (zh_split.h: barriers and token chain) ... */                     \
+   X(ZH_SET_CORE, DEV, d_spanstart, B * c->chunks_per_block)                                                                                                           \
+   X(ZH_SET_CORE, DEV, d_spancnt, B * c->chunks_per_block)                                                                                                             \
+   X(ZH_SET_CORE, DEV, d_split_tok, B * (ZH_MAX_SPLITS + 1))    /* split boundaries, in tokens */                                                                        \
+   X(ZH_SET_CORE, DEV, d_split_cnt, B)                          /* sub-blocks of every max-block */                                                                      \
+   X(ZH_SET_CORE, DEV, d_sub_base, B)                           /* ... and the first of them in the run */                                                               \
+   X(ZH_SET_CORE, DEV, d_best, B * c->best_stride)              /* final parse per position */                                                                           \
+   X(ZH_SET_CORE, DEV, d_cost, B * c->best_stride)              /* zh_parse_lanes: cost of every position from its piece's end */                                        \
+   X(ZH_SET_CORE, DEV, d_work, U)                               /* per sub-block: work item */                                                                           \
+   X(ZH_SET_CORE, DEV, d_results, U)                            /* per sub-block: the descriptor the caller gets */                                                      \
+   X(ZH_SET_CORE, DEV, d_payload, B * c->slot_stride)           /* per-sub-block bit strings (slot of sub-block k of a block starts at its offset + 64k) */              \
+   X(ZH_SET_CORE, DEV, d_items, U)                              /* per sub-block: where a stitch put it */                                                               \
+   X(ZH_SET_CORE, DEV, d_crc, B)                                /* per max-block CRC-32, linear part */                                                                  \
+   X(ZH_SET_CORE, DEV, d_adler, 2 * B)                          /* per max-block Adler-32 sums */                                                                        \
+   X(ZH_SET_CORE, DEV, d_crc_tables, 256 + 1024)                /* byte table of 0xEDB88320 and the 'append ZH_CRC_SLICE zero bytes' operator */                         \
+   X(ZH_SET_CORE, DEV, d_stream, c->stream_cap / 4 + 4)         /* stitched deflate bits of the last batch: stream_cap bytes and 16 behind them */                       \
+   X(ZH_SET_CORE, PIN, h_payload, B * c->slot_stride)           /* d_payload, copied lazily */                                                                           \
+   X(ZH_SET_CORE, PIN, h_stage[0], 0)                           /* staging for callers that hand over pageable host memory (zultra_hip_staging): input ... */            \
+   X(ZH_SET_CORE, PIN, h_stage[1], 0)                           /* ... and output */                                                                                     \
+   X(ZH_SET_VERIFY, DEV, d_vitems, U)                           /* zultra_hip_verify_device: 24 bytes per sub-block ... */                                               \
+   X(ZH_SET_VERIFY, DEV, d_vreport, 1)                          /* ... the batch report ... */                                                                           \
+   X(ZH_SET_VERIFY, PIN, h_vreport, 1)                          /* ... and its mirror */                                                                                 \
+   X(ZH_SET_FRAME, DEV, d_members, B)                           /* zultra_hip_frame_members: a record per member */                                                      \
+   X(ZH_SET_ZIP, DEV, d_zip_report, 1)                          /* zultra_hip_zip_members: the report of zh_zip_scan ... */                                              \
+   X(ZH_SET_ZIP, PIN, h_zip_report, 1)                          /* ... and its mirror */                                                                                 \
+   X(ZH_SET_ZIP, DEV, d_zip, 0)                                 /* the archive's local part, and at zip_central_at the central part */                                   \
+   X(ZH_SET_ZIP, DEV, d_zip_in, 0)                              /* a call's name_off, entry_block and names */                                                           \
+   X(ZH_SET_ZIP, DEV, d_zip_entries, 0)                         /* per entry: what was written ... */                                                                    \
+   X(ZH_SET_ZIP, DEV, d_zip_src, 0)                             /* ... and where its stream is */
+
+enum zh_buf_kind { DEV, PIN };
+enum zh_buf_op { ZH_BUF_ALLOC, ZH_BUF_SIZE, ZH_BUF_FREE };
+
+static int zh_buffer(zultra_hip_ctx_t *c, zh_buf_op op, zh_buf_kind kind, const char *name, void **p, size_t bytes) {
+   if (op == ZH_BUF_FREE) {
+      if (*p) (void)(kind == DEV ? hipFree(*p) : hipHostFree(*p));
+      *p = NULL;
+      return 0;
+   }
+   if (*p || !bytes) return 0;   // (it is there; or its user grows it)
+   if (op == ZH_BUF_ALLOC) {
+      const hipError_t e = kind == DEV ? hipMalloc(p, bytes) : hipHostMalloc(p, bytes, 0);
+      if (e != hipSuccess) {
+         snprintf(c->err, sizeof(c->err), "%s: allocating %zu bytes failed: %s", name, bytes, hipGetErrorString(e));
+         return -1;
+      }
+   }
+   if (kind == DEV) c->device_bytes += bytes;   // (zultra_hip_ctx_info; ZH_BUF_SIZE: what ZH_BUF_ALLOC would add)
    return 0;
 }
 
-// What a context holds only once a call has asked for it: each set is created here, by a caller that has set the device, and released in zultra_hip_destroy under
-// the function's name. The streams' offsets of the files form (a files context has them from its creation):
-static int zh_need_file_off(zultra_hip_ctx_t *c) { return c->d_file_off ? 0 : zh_alloc(c, &c->d_file_off, (size_t)c->max_blocks + 1); }
-// zultra_hip_verify_device: 24 bytes per sub-block, the batch report and its pinned mirror, two events
-static int zh_need_verify(zultra_hip_ctx_t *c) {
-   if (c->d_vitems) return 0;
-   if (zh_alloc(c, &c->d_vitems, (size_t)c->max_blocks * c->max_subs) || zh_alloc(c, &c->d_vreport, 1)) return -1;
-   ZH_CHECK(c, hipHostMalloc((void **)&c->h_vreport, sizeof(zh_verify_report_t), 0));
-   for (int i = 0; i < 2; i++) ZH_CHECK(c, hipEventCreate(&c->ev_verify[i]));
+// The buffers of `sets`: allocated where absent, counted into device_bytes without allocating, or released
+static int zh_buffers(zultra_hip_ctx_t *c, zh_buf_op op, uint32_t sets) {
+   const uint64_t B = c->max_blocks, S = c->segs_per_block, U = B * c->max_subs, T = c->max_tasks;
+#define X(sets_, kind_, field_, count_) \
+   if ((sets & (sets_)) && zh_buffer(c, op, kind_, #field_, (void **)&c->field_, (size_t)(count_) * sizeof(*c->field_))) return -1;
+   ZH_CTX_BUFFERS(X)
+#undef X
    return 0;
 }
-// zultra_hip_frame_members: a record per member, four events
-static int zh_need_frame(zultra_hip_ctx_t *c) {
-   if (!c->d_members && zh_alloc(c, &c->d_members, (size_t)c->max_blocks)) return -1;
-   for (int i = 0; i < 4; i++)
-      if (!c->ev_frame[i]) ZH_CHECK(c, hipEventCreate(&c->ev_frame[i]));
+static uint32_t zh_creation_sets(int files_mode) {
+   return ZH_SET_CORE | (files_mode ? ZH_SET_FILES : ZH_SET_BLOCKS) | (zh_env("ZULTRA_HIP_CHAIN_TRACE", 0) ? ZH_SET_TRACE : 0);
+}
+
+// What a context holds only once a call has asked for it: a set of the list and the events that go with it, created here by a caller that has set the device
+static int zh_need_file_off(zultra_hip_ctx_t *c) { return zh_buffers(c, ZH_BUF_ALLOC, ZH_SET_FILE_OFF); }   // (a files context has them from its creation)
+static int zh_need_events(zultra_hip_ctx_t *c, hipEvent_t *ev, int n) {
+   for (int i = 0; i < n; i++)
+      if (!ev[i]) ZH_CHECK(c, hipEventCreate(&ev[i]));
    return 0;
 }
-// zultra_hip_zip_members: the report of zh_zip_scan and its pinned mirror, four events (the buffers sized by a call's entries grow there, zh_zip_grow)
-static int zh_need_zip(zultra_hip_ctx_t *c) {
-   if (c->d_zip_report) return 0;
-   if (zh_alloc(c, &c->d_zip_report, 1)) return -1;
-   ZH_CHECK(c, hipHostMalloc((void **)&c->h_zip_report, sizeof(zh_zip_report_t), 0));
-   for (int i = 0; i < 4; i++) ZH_CHECK(c, hipEventCreate(&c->ev_zip[i]));
-   return 0;
+static int zh_need_verify(zultra_hip_ctx_t *c) { return zh_buffers(c, ZH_BUF_ALLOC, ZH_SET_VERIFY) || zh_need_events(c, c->ev_verify, 2); }
+static int zh_need_frame(zultra_hip_ctx_t *c) { return zh_buffers(c, ZH_BUF_ALLOC, ZH_SET_FRAME) || zh_need_events(c, c->ev_frame, 4); }
+static int zh_need_zip(zultra_hip_ctx_t *c) { return zh_buffers(c, ZH_BUF_ALLOC, ZH_SET_ZIP) || zh_need_events(c, c->ev_zip, 4); }   // (the buffers sized by a call's entries grow there, zh_zip_grow)
+static void zh_drop_events(hipEvent_t *ev, int n) {
+   for (int i = 0; i < n; i++)
+      if (ev[i]) (void)hipEventDestroy(ev[i]);
 }
 
 extern "C" void zultra_hip_destroy(zultra_hip_ctx_t *c) {
    if (!c) return;
    (void)hipSetDevice(c->device);
-   (void)hipFree(c->d_data);
-   (void)hipFree(c->d_blocks);
-   (void)hipFree(c->d_sort_a);
-   (void)hipFree(c->d_sort_b);
-   (void)hipFree(c->d_prev3);
-   (void)hipFree(c->d_runs);
-   (void)hipFree(c->d_segs);
-   (void)hipFree(c->d_chunk_ctr);
-   (void)hipFree(c->d_match);
-   (void)hipFree(c->d_pay);
-   (void)hipFree(c->d_tok_pos);
-   (void)hipFree(c->d_tok_info);
-   (void)hipFree(c->d_ntok);
-   (void)hipFree(c->d_chunkmax);
-   (void)hipFree(c->d_spanstart);
-   (void)hipFree(c->d_spancnt);
-   (void)hipFree(c->d_split_tok);
-   (void)hipFree(c->d_split_cnt);
-   (void)hipFree(c->d_sub_base);
-   (void)hipFree(c->d_best);
-   (void)hipFree(c->d_cost);
-   (void)hipFree(c->d_work);
-   (void)hipFree(c->d_results);
-   (void)hipFree(c->d_payload);
-   (void)hipFree(c->d_bars);
-   (void)hipFree(c->d_states);
-   (void)hipFree(c->d_taskmap);
-   (void)hipFree(c->d_taskinfo);
-   (void)hipFree(c->d_nsubs);
-   (void)hipFree(c->d_blk_start);
-   (void)hipFree(c->d_scan_out);
-   (void)hipFree(c->d_task_prefix);
-   if (c->h_task_prefix) (void)hipHostFree(c->h_task_prefix);
-   if (c->h_grids) (void)hipHostFree(c->h_grids);
-   if (c->h_file_off) (void)hipHostFree(c->h_file_off);
-   if (c->h_nsubs) (void)hipHostFree(c->h_nsubs);
-   if (c->h_scan_out) (void)hipHostFree(c->h_scan_out);
-   (void)hipFree(c->d_ntasks);
-   (void)hipFree(c->d_hugelist);
-   (void)hipFree(c->d_lanelist);
-   (void)hipFree(c->d_lane_acc);
-   (void)hipFree(c->d_segtasks);
-   (void)hipFree(c->d_segwaves);
-   (void)hipFree(c->d_segitems);
-   (void)hipFree(c->d_vecs);
-   (void)hipFree(c->d_chain_trace);
-   (void)hipFree(c->d_hist_part);
-   (void)hipFree(c->d_task_bits);
+   (void)zh_buffers(c, ZH_BUF_FREE, ZH_SET_ALL);
    for (int k = 0; k < ZH_MAX_RUNS; k++) {
-      for (int i = 0; i < ZH_RUN_EVENTS; i++)
-         if (c->lane_ev[k][i]) (void)hipEventDestroy(c->lane_ev[k][i]);
+      zh_drop_events(c->lane_ev[k], ZH_RUN_EVENTS);
       if (c->lane_stream[k]) (void)hipStreamDestroy(c->lane_stream[k]);
-      for (int i = 0; i < 8; i++)
-         if (c->side_ev[k][i]) (void)hipEventDestroy(c->side_ev[k][i]);
+      zh_drop_events(c->side_ev[k], 8);
       if (c->side_stream[k]) (void)hipStreamDestroy(c->side_stream[k]);
    }
-   if (c->ev_input) (void)hipEventDestroy(c->ev_input);
-   if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
+   zh_drop_events(&c->ev_input, 1);
+   zh_drop_events(&c->ev_fork, 1);
    zh_graph_clear(&c->batch_graph);
    for (int i = 0; i < 2; i++) zh_graph_clear(&c->run_graphs[i]);
-   for (int k = 0; k < 2; k++)
-      if (c->h_stage[k]) (void)hipHostFree(c->h_stage[k]);
-   if (c->h_crc) (void)hipHostFree(c->h_crc);
-   if (c->h_blocks) (void)hipHostFree(c->h_blocks);
-   if (c->h_segs) (void)hipHostFree(c->h_segs);
-   if (c->h_ntasks) (void)hipHostFree(c->h_ntasks);
-   if (c->h_results) (void)hipHostFree(c->h_results);
-   (void)hipFree(c->d_results_compact);
-   (void)hipFree(c->d_items);
-   (void)hipFree(c->d_stream);
-   (void)hipFree(c->d_file_off);   // zh_need_file_off (or the creation of a files context)
-   (void)hipFree(c->d_vitems);     // zh_need_verify
-   (void)hipFree(c->d_vreport);
-   if (c->h_vreport) (void)hipHostFree(c->h_vreport);
-   for (int i = 0; i < 2; i++)
-      if (c->ev_verify[i]) (void)hipEventDestroy(c->ev_verify[i]);
-   (void)hipFree(c->d_members);    // zh_need_frame
-   for (int i = 0; i < 4; i++)
-      if (c->ev_frame[i]) (void)hipEventDestroy(c->ev_frame[i]);
-   (void)hipFree(c->d_zip_report); // zh_need_zip
-   if (c->h_zip_report) (void)hipHostFree(c->h_zip_report);
-   for (int i = 0; i < 4; i++)
-      if (c->ev_zip[i]) (void)hipEventDestroy(c->ev_zip[i]);
-   (void)hipFree(c->d_zip);        // zh_zip_grow
-   (void)hipFree(c->d_zip_in);
-   (void)hipFree(c->d_zip_entries);
-   (void)hipFree(c->d_zip_src);
-   (void)hipFree(c->d_crc);
-   (void)hipFree(c->d_adler);
-   if (c->h_adler) (void)hipHostFree(c->h_adler);
-   (void)hipFree(c->d_crc_tables);
-   if (c->h_payload) (void)hipHostFree(c->h_payload);
-   for (int i = 0; i < ZH_STITCH_EVENTS; i++)
-      if (c->ev_stitch[i]) (void)hipEventDestroy(c->ev_stitch[i]);
+   zh_drop_events(c->ev_verify, 2);
+   zh_drop_events(c->ev_frame, 4);
+   zh_drop_events(c->ev_zip, 4);
+   zh_drop_events(c->ev_stitch, ZH_STITCH_EVENTS);
    if (c->stream) (void)hipStreamDestroy(c->stream);
    delete c;
 }
@@ -775,8 +822,7 @@ static bool zh_assembly_brought(const zultra_hip_ctx_t *c, const zh_stitch_job_t
    return true;
 }
 
-// streams (and payload areas) a context holds for the staggered runs of a batch: ZULTRA_HIP_STREAMS, 0 or unset = auto = four (zh_create_buffers and
-// zultra_hip_context_bytes_on must agree: the host layer budgets batches with the latter)
+// streams (and payload areas) a context holds for the staggered runs of a batch: ZULTRA_HIP_STREAMS, 0 or unset = auto = four
 static int zh_env_lanes(void) {
    const int streams = zh_env("ZULTRA_HIP_STREAMS", 0);
    return streams > 0 ? min(streams, (int)ZH_MAX_RUNS) : 4;
@@ -786,7 +832,6 @@ static int zh_env_lanes(void) {
 static uint32_t zh_env_mf_cap(void) { return (uint32_t)max((int)ZH_MFL_MINCAP, zh_env("ZULTRA_HIP_MF_CAP", (int)ZH_MFL_CAP_LIMIT)); }
 
 static int zh_create_buffers(zultra_hip_ctx_t *c) {
-   const uint64_t B = c->max_blocks, N = c->max_block;
    ZH_CHECK(c, hipSetDevice(c->device));
    {
       // once per device and process: the wave primitives and the LDS behaviour the kernels rely on (zh_selftest_kernel) — a device that
@@ -804,26 +849,16 @@ static int zh_create_buffers(zultra_hip_ctx_t *c) {
          checked_ok[dv >> 6] |= 1ull << (dv & 63u);
       }
    }
-   {
-      int n = 0;
-      if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess || n <= 0) n = 256;
-      c->total_cus = (uint32_t)n;
-      c->num_cus = c->total_cus;   // what the persistent kernels may fill (keeping 8..32 CUs free for the chain kernels was measured in round 3: +3 ms per 100 MB)
-      // the matchfinder kernels take all their LDS dynamically (zh_matchfinder.h): more than the 64 KiB default limit
-      ZH_CHECK(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&zh_mf_group<true>), hipFuncAttributeMaxDynamicSharedMemorySize, ZH_MF_GROUP_LDS));
-      ZH_CHECK(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&zh_mf_frontier<true>), hipFuncAttributeMaxDynamicSharedMemorySize, ZH_MF_FRONTIER_LDS));
-      ZH_CHECK(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&zh_mf_group_big), hipFuncAttributeMaxDynamicSharedMemorySize, ZH_MF_GROUP_LDS));
-   }
+   // the matchfinder kernels take all their LDS dynamically (zh_matchfinder.h): more than the 64 KiB default limit
+   ZH_CHECK(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&zh_mf_group<true>), hipFuncAttributeMaxDynamicSharedMemorySize, ZH_MF_GROUP_LDS));
+   ZH_CHECK(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&zh_mf_frontier<true>), hipFuncAttributeMaxDynamicSharedMemorySize, ZH_MF_FRONTIER_LDS));
+   ZH_CHECK(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&zh_mf_group_big), hipFuncAttributeMaxDynamicSharedMemorySize, ZH_MF_GROUP_LDS));
    ZH_CHECK(c, hipStreamCreate(&c->stream));
    for (int i = 0; i < ZH_STITCH_EVENTS; i++) ZH_CHECK(c, hipEventCreate(&c->ev_stitch[i]));
    ZH_CHECK(c, hipEventCreate(&c->ev_fork));
    {
       // ---- switches of the shipped library (INTEGRATION.md lists them): they pick between product paths that the size and kind of the data
       //      would otherwise pick, so that tests can force every path on small inputs; and one diagnostic
-      if (zh_env("ZULTRA_HIP_CHAIN_TRACE", 0)) {
-         if (zh_alloc(c, &c->d_chain_trace, (size_t)3 * ZH_TRACE_SLOTS * 4 * ZH_MAX_RUNS)) return -1;   // (the getter returns the first four runs)
-         ZH_CHECK(c, hipMemset(c->d_chain_trace, 0, (size_t)3 * ZH_TRACE_SLOTS * 4 * ZH_MAX_RUNS * sizeof(uint64_t)));
-      }
       c->demote_min = (uint32_t)zh_env("ZULTRA_HIP_DEMOTE", 2);        // a cut task with this many failed cuts in a pass becomes one chain (0: never)
       c->coop_small = (uint32_t)zh_env("ZULTRA_HIP_COOP_SMALL", 256);  // small runs: tasks with a barrier-free piece above this go to the chain kernel
       if (c->coop_small < 64u) c->coop_small = 64u;
@@ -837,20 +872,13 @@ static int zh_create_buffers(zultra_hip_ctx_t *c) {
       c->lane_bundles = zh_env("ZULTRA_HIP_LANE_BUNDLES", 1) != 0;     // 0: no bundle lists are kept, zh_parse_lanes takes consecutive tasks of the task list as it did before bundles (the A/B of the bundles)
       c->lane_tasks = (uint32_t)min(max(0, zh_env("ZULTRA_HIP_LANE_TASKS", 0)), (int)ZH_LP_TASKS);   // tasks per bundle; 0: by the run's size (zh_tasks_per_wave: one below a chip's worth of tasks)
       c->seg_wide = (uint32_t)zh_env("ZULTRA_HIP_SEG_WIDE", 1024);     // a run with at least this many segments parses them in the segment workgroups of zh_parse_lanes' launch
-      // the chunk size of zh_mf_group, and the segments' note tables sized for it: every class the chunks cannot take has its note, whatever the value (with the
-      // default: 29 notes in run tables of sort_stride + 576 words; zh_mf_group_lds.h has the bound)
-      c->mf_lds_cap = zh_env_mf_cap();
-      c->run_stride = zh_mf_run_stride(c->sort_stride, c->mf_lds_cap);
       if (zh_mfl_note_room(c->sort_stride, c->run_stride) < c->seg_W / zh_mfl_cap(c->seg_W, c->mf_lds_cap)) {
          snprintf(c->err, sizeof(c->err), "matchfinder note table too small for chunks of %u", c->mf_lds_cap);
          return -1;
       }
       const int streams = zh_env("ZULTRA_HIP_STREAMS", 0);              // staggered runs per batch; not set: three, four for batches of 256 MiB and more
-      c->nlanes = zh_env_lanes();
       c->auto_runs = streams > 0 ? 0 : 1;   // (measured with the stagger below, runs = 2 / 3 / 4 / 6: 100 MB of real text 49.8 / 49.6 / 51.2 / - ms; configuration 3
                                         // 31.0 / 29.1 / 29.5 / -; 1 GiB of configuration 4 910 / 883 / 789 / 812)
-      if (c->nlanes < 1) c->nlanes = 1;
-      if (c->nlanes > ZH_MAX_RUNS) c->nlanes = ZH_MAX_RUNS;
       c->files_run_graphs = zh_env("ZULTRA_HIP_FILES_RUN_GRAPHS", 1);  // files mode: 0 = several runs are launched kernel by kernel, and large batches stay one run
       for (int k = 0; k < c->nlanes; k++) {
          ZH_CHECK(c, hipStreamCreateWithFlags(&c->lane_stream[k], hipStreamNonBlocking));
@@ -867,47 +895,12 @@ static int zh_create_buffers(zultra_hip_ctx_t *c) {
 #ifndef ZH_EMU
       if (zh_spread_streams(c) != 0) return -1;
 #endif
-      if (zh_alloc(c, &c->d_results_compact, B * c->max_subs)) return -1;
-      ZH_CHECK(c, hipHostMalloc((void **)&c->h_nsubs, (1 + ZH_MAX_RUNS) * sizeof(uint32_t), 0));
-      ZH_CHECK(c, hipHostMalloc((void **)&c->h_scan_out, sizeof(zh_scan_out_t), 0));
-      ZH_CHECK(c, hipHostMalloc((void **)&c->h_grids, 2 * ZH_MAX_RUNS * sizeof(uint32_t), 0));
-      memset(c->h_nsubs, 0, (1 + ZH_MAX_RUNS) * sizeof(uint32_t));
-      ZH_CHECK(c, hipHostMalloc((void **)&c->h_crc, B * sizeof(uint32_t), 0));
-      ZH_CHECK(c, hipHostMalloc((void **)&c->h_blocks, B * sizeof(zh_block_t), 0));
-      if (c->files_mode) ZH_CHECK(c, hipHostMalloc((void **)&c->h_task_prefix, (B + 1) * sizeof(uint32_t), 0));
-      if (c->files_mode) ZH_CHECK(c, hipHostMalloc((void **)&c->h_file_off, (B + 1) * sizeof(uint64_t), 0));
-      ZH_CHECK(c, hipHostMalloc((void **)&c->h_segs, B * c->segs_per_block * sizeof(zh_seg_t), 0));
-      ZH_CHECK(c, hipHostMalloc((void **)&c->h_ntasks, 2 * ZH_NCNT * sizeof(uint32_t), 0));   // a mirror of d_ntasks + per-run readbacks
-      memset(c->h_ntasks, 0, 2 * ZH_NCNT * sizeof(uint32_t));
-      ZH_CHECK(c, hipHostMalloc((void **)&c->h_adler, 2 * B * sizeof(uint32_t), 0));
-      ZH_CHECK(c, hipHostMalloc((void **)&c->h_results, B * c->max_subs * sizeof(zh_subblock_t), 0));
    }
-   c->bar_stride = c->tok_stride / 64;
-   c->max_tasks = B * (N / ZH_TASK + c->max_subs);
-   // a cut task has at least 2 * ZH_CUT_WARM positions (the floor of ZH_CUT_MIN) and lies inside one max-block
-   c->seg_tasks_per_block = c->files_mode ? 1 : N / (2u * ZH_CUT_WARM) + 1;
-   c->seg_items_per_block = c->files_mode ? 1 : N / ZH_CUT_WARM + ZH_CUT_ROWS * (N / (2u * ZH_CUT_WARM) + 1) + 2;   // a task of len positions has at most len / ZH_CUT_LEN + ZH_CUT_ROWS segments
-   if (zh_alloc(c, &c->d_bars, B * c->bar_stride) || zh_alloc(c, &c->d_states, B * c->max_subs) || zh_alloc(c, &c->d_taskmap, c->max_tasks) || zh_alloc(c, &c->d_taskinfo, c->max_tasks) ||
-       zh_alloc(c, &c->d_nsubs, 1 + ZH_MAX_RUNS) || zh_alloc(c, &c->d_blk_start, B + 1) || zh_alloc(c, &c->d_scan_out, 1) || (c->files_mode && (zh_alloc(c, &c->d_file_off, B + 1) || zh_alloc(c, &c->d_task_prefix, B + 1))) ||
-       zh_alloc(c, &c->d_prev3, B * c->segs_per_block * c->sort_stride) || zh_alloc(c, &c->d_runs, B * c->segs_per_block * c->run_stride) ||
-       zh_alloc(c, &c->d_segs, B * c->segs_per_block) || zh_alloc(c, &c->d_chunk_ctr, 2 * B * c->segs_per_block + 3 * ZH_MAX_RUNS) || zh_alloc(c, &c->d_ntasks, ZH_NCNT) || zh_alloc(c, &c->d_hugelist, 4 * c->max_tasks) ||
-       (!c->files_mode && (zh_alloc(c, &c->d_lanelist, ZH_LANE_CLASSES * c->max_tasks) || zh_alloc(c, &c->d_lane_acc, c->max_tasks))) ||
-       zh_alloc(c, &c->d_segtasks, B * c->seg_tasks_per_block) || zh_alloc(c, &c->d_segwaves, B * c->seg_items_per_block) || zh_alloc(c, &c->d_segitems, B * c->seg_items_per_block) ||
-       zh_alloc(c, &c->d_vecs, B * c->seg_items_per_block * 2 * ZH_VEC) || zh_alloc(c, &c->d_hist_part, c->max_tasks * ZH_NSYM) || zh_alloc(c, &c->d_task_bits, c->max_tasks))
-      return -1;
-   if (zh_alloc(c, &c->d_data, c->data_cap + 64) || zh_alloc(c, &c->d_blocks, B) || zh_alloc(c, &c->d_sort_a, B * c->segs_per_block * c->sort_stride) ||
-       zh_alloc(c, &c->d_sort_b, B * c->segs_per_block * c->sort_stride) || zh_alloc(c, &c->d_match, B * c->match_stride) ||
-       zh_alloc(c, &c->d_pay, (size_t)c->nlanes * zh_min64(c->total_cus, B * c->segs_per_block) * 3 * c->sort_stride) ||   // (the runs' kernels may overlap)
-       zh_alloc(c, &c->d_tok_pos, B * c->tok_stride) || zh_alloc(c, &c->d_tok_info, B * c->tok_stride) ||
-       zh_alloc(c, &c->d_ntok, B) || zh_alloc(c, &c->d_chunkmax, B * c->chunks_per_block) || zh_alloc(c, &c->d_spanstart, B * c->chunks_per_block) ||
-       zh_alloc(c, &c->d_spancnt, B * c->chunks_per_block) || zh_alloc(c, &c->d_split_tok, B * (ZH_MAX_SPLITS + 1)) || zh_alloc(c, &c->d_split_cnt, B) ||
-       zh_alloc(c, &c->d_sub_base, B) || zh_alloc(c, &c->d_best, B * c->best_stride) || zh_alloc(c, &c->d_cost, B * c->best_stride) || zh_alloc(c, &c->d_work, B * c->max_subs) ||
-       zh_alloc(c, &c->d_results, B * c->max_subs) || zh_alloc(c, &c->d_payload, B * c->slot_stride) ||
-       zh_alloc(c, &c->d_items, B * c->max_subs) || zh_alloc(c, &c->d_crc, B) || zh_alloc(c, &c->d_adler, 2 * B) || zh_alloc(c, &c->d_crc_tables, 256 + 1024))
-      return -1;
+   if (zh_buffers(c, ZH_BUF_ALLOC, zh_creation_sets(c->files_mode))) return -1;
+   if (c->d_chain_trace) ZH_CHECK(c, hipMemset(c->d_chain_trace, 0, ZH_TRACE_WORDS * sizeof(uint64_t)));
+   memset(c->h_nsubs, 0, (1 + ZH_MAX_RUNS) * sizeof(uint32_t));
+   memset(c->h_ntasks, 0, 2 * ZH_NCNT * sizeof(uint32_t));
    ZH_CHECK(c, hipMemset(c->d_ntasks, 0, ZH_NCNT * sizeof(uint32_t)));
-   c->stream_cap = (size_t)(B * (N + 5 * (N / 65535 + 1) + 8 + ZH_FRAME_ROOM) + 64) & ~(size_t)3;   // (+ 64: slack, and BGZF's end marker)
-   ZH_CHECK(c, hipMalloc((void **)&c->d_stream, c->stream_cap + 16));
    {
       // CRC tables: byte table of 0xEDB88320 and the 'append ZH_CRC_SLICE zero bytes' operator, one table per state byte
       std::vector<uint32_t> t(256 + 1024);
@@ -924,8 +917,6 @@ static int zh_create_buffers(zultra_hip_ctx_t *c) {
          }
       ZH_CHECK(c, hipMemcpy(c->d_crc_tables, t.data(), t.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
    }
-   ZH_CHECK(c, hipHostMalloc((void **)&c->h_payload, B * c->slot_stride, 0));
-   (void)N;
    return 0;
 }
 
@@ -935,29 +926,7 @@ static zultra_hip_ctx_t *zh_create(int device, uint32_t max_block, uint32_t max_
    zultra_hip_ctx_t *c = new zultra_hip_ctx_s();
    memset((void *)&c->timing, 0, sizeof(c->timing));
    c->device = device;
-   c->files_mode = files_mode;
-   c->max_block = max_block;
-   c->max_blocks = max_blocks;
-   c->max_subs = files_mode ? 1u : (uint32_t)ZH_MAX_SPLITS;
-   c->W = (uint64_t)c->max_block + (files_mode ? 0u : (uint32_t)ZH_HISTORY);
-   if (c->W <= ZH_SEG_WINDOW) {   // a max-block is one matchfinder segment
-      c->seg_n = c->max_block;
-      c->segs_per_block = 1;
-      c->seg_W = (uint32_t)c->W;
-   }
-   else {
-      c->seg_n = ZH_SEG_POSITIONS;
-      c->segs_per_block = (c->max_block + ZH_SEG_POSITIONS - 1) / ZH_SEG_POSITIONS;
-      c->seg_W = ZH_SEG_WINDOW;
-   }
-   c->sort_stride = ((uint64_t)c->seg_W + 63) & ~63ull;
-   // (run_stride — start[Q] length[Q] first[256] end[256] count, Q = W/4 + 1, and the notes for zh_mf_group_big — follows from the chunk size: zh_create_buffers)
-   c->match_stride = (uint64_t)c->max_block * ZH_NMATCH;
-   c->tok_stride = ((uint64_t)c->max_block + 63) & ~63ull;
-   c->chunks_per_block = (c->max_block + ZH_TOK_CHUNK_SMALL - 1) / ZH_TOK_CHUNK_SMALL;   // (what the per-chunk arrays hold: the small chunks of a small batch)
-   c->best_stride = c->tok_stride;
-   c->slot_stride = (((uint64_t)c->max_block + 64 * c->max_subs + 64) + 63) & ~63ull;
-   c->data_cap = (size_t)c->W + (size_t)(max_blocks - 1) * c->max_block;
+   zh_shape(c, max_block, max_blocks, files_mode, zh_device_cus(device), zh_env_lanes(), zh_env_mf_cap());
    c->err[0] = 0;
    if (zh_create_buffers(c) != 0) {
       fprintf(stderr, "zultra_hip_create: %s\n", c->err);
@@ -1002,39 +971,13 @@ extern "C" void zultra_hip_ctx_info(const zultra_hip_ctx_t *c, int *device, uint
    if (device_bytes) *device_bytes = c->device_bytes;
 }
 
-// Device bytes a context on `device` for batches of `max_blocks` max-blocks of `max_block_size` bytes allocates: the strides and the list
-// of arrays of zh_create / zh_create_buffers (the layout comment at the top of this file) restated without allocating — a second
-// formula, held to the real layout by test_context_cache_and_size_estimate (-5 % .. +10 %); files mode (one sub-block per block)
-// allocates less than this. The device matters for one term only: the matchfinder's payload, per compute unit.
+// Device bytes a context on `device` for batches of `max_blocks` max-blocks of `max_block_size` bytes allocates at its creation: the device entries of the list, summed
+// over the same shape and the same sets as zh_create takes, on a context-shaped value that is never allocated. A files context (one sub-block per block) allocates less.
 extern "C" size_t zultra_hip_context_bytes_on(int device, uint32_t max_block_size, uint32_t max_blocks) {
-   const uint64_t N = zh_clamp_block(max_block_size), B = max_blocks;
-   const uint64_t W = N + ZH_HISTORY;
-   const uint64_t seg_W = W <= ZH_SEG_WINDOW ? W : (uint64_t)ZH_SEG_WINDOW;
-   const uint64_t S = W <= ZH_SEG_WINDOW ? 1 : (N + ZH_SEG_POSITIONS - 1) / ZH_SEG_POSITIONS;
-   const uint64_t sort_stride = (seg_W + 63) & ~63ull, run_stride = zh_mf_run_stride(sort_stride, zh_env_mf_cap()), tok_stride = (N + 63) & ~63ull;
-   const uint64_t slot_stride = ((N + 64 * ZH_MAX_SPLITS + 64) + 63) & ~63ull, cpb = (N + ZH_TOK_CHUNK_SMALL - 1) / ZH_TOK_CHUNK_SMALL;
-   const uint64_t tasks = B * (N / ZH_TASK + ZH_MAX_SPLITS), subs = B * ZH_MAX_SPLITS;
-   uint64_t bytes = 0;
-   bytes += W + (B - 1) * N + 64;                                    // d_data
-   bytes += B * S * sort_stride * (4 + 4 + 8) + B * S * run_stride * 4;   // sort ping-pong, prev records, run tables
-   bytes += B * N * ZH_NMATCH * sizeof(zh_match_t) + B * tok_stride * (4 + 2 + 4 + 2);   // rows, token chain, parse, costs
-   bytes += B * (tok_stride / 64) * 8;                               // barrier bitmap
-   bytes += B * slot_stride;                                         // payload slots
-   bytes += (B * (N + 5 * (N / 65535 + 1) + 8 + ZH_FRAME_ROOM) + 80);                // stitched stream
-   bytes += subs * (sizeof(zh_sbstate_t) + sizeof(zh_work_t) + 2 * sizeof(zh_subblock_t) + sizeof(zh_stitch_item_t));
-   bytes += tasks * (2 * sizeof(uint2) + 4 * 4 + 4 + ZH_NSYM * 4);   // task map and ranges, chain lists, bit counts, histograms
-   bytes += B * (S * (sizeof(zh_seg_t) + 8) + sizeof(zh_block_t) + cpb * 12 + (ZH_MAX_SPLITS + 1) * 4 + 6 * 4) + 8192;
-   {
-      // payload of the matchfinder's refining passes: per run (ZULTRA_HIP_STREAMS) and persistent workgroup (one per CU)
-      int cus = 0;
-      if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus <= 0) cus = 256;
-      const uint64_t lanes = (uint64_t)zh_env_lanes();   // (what zh_create_buffers allocates for: 0 or unset = four)
-      bytes += lanes * zh_min64((uint64_t)cus, B * S) * 3 * sort_stride * 4;
-      // cut tasks (zh_parse.h): lists and two cost vectors per segment
-      const uint64_t seg_tasks = N / (2u * ZH_CUT_WARM) + 1, seg_items = N / ZH_CUT_WARM + ZH_CUT_ROWS * (N / (2u * ZH_CUT_WARM) + 1) + 2;
-      bytes += B * (seg_tasks * sizeof(uint4) + seg_items * (2 * sizeof(uint2) + 2 * ZH_VEC * sizeof(int16_t)));
-   }
-   return (size_t)bytes;
+   zultra_hip_ctx_s shape = zultra_hip_ctx_s();
+   zh_shape(&shape, zh_clamp_block(max_block_size), max_blocks, 0, zh_device_cus(device), zh_env_lanes(), zh_env_mf_cap());
+   (void)zh_buffers(&shape, ZH_BUF_SIZE, zh_creation_sets(0));
+   return shape.device_bytes;
 }
 extern "C" size_t zultra_hip_context_bytes(uint32_t max_block_size, uint32_t max_blocks) {   // on the calling thread's current device
    int dev = 0;

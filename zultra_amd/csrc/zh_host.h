@@ -32,6 +32,7 @@ static inline uint64_t zh_env64(const char *name, uint64_t dflt) {   // (a byte 
 #define ZH_HIDDEN __attribute__((visibility("hidden")))
 ZH_HIDDEN uint32_t zh_clamp_block(uint32_t n);                                                // zh_device.hip: a caller's max-block size as the library takes it (libzultra.c:87-92)
 ZH_HIDDEN void zh_threaded_copy(uint8_t *dst, const uint8_t *src, size_t n, size_t piece);   // libzultra.cpp: a copy into pinned staging, over a few threads from 2 * piece bytes on
+ZH_HIDDEN uint32_t zh_device_cus(int device);                                                 // zh_inflate.hip: compute units of a device (256 where it does not say)
 extern "C" {
 ZH_HIDDEN void *zh_device_upload(int device, const void *host, size_t n);                     // zh_inflate.hip, for libzultra.cpp (which has no HIP of its own): a device copy of a host buffer
 ZH_HIDDEN void zh_device_release(void *p);

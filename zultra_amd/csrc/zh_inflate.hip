@@ -61,7 +61,7 @@ struct zh_inflate_call_t {
 template <typename T>
 static hipError_t zh_dalloc(T **p, size_t count) { return hipMalloc((void **)p, count * sizeof(T)); }
 // CUs of the device, 256 if it does not say
-static uint32_t zh_device_cus(int device) {
+ZH_HIDDEN uint32_t zh_device_cus(int device) {
    int cus = 0;
    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus <= 0) cus = 256;
    return (uint32_t)cus;

@@ -241,6 +241,42 @@ def test_chains_turn_up_after_a_batch_without_any(gpu, checker):
     _chains_after_none(gpu, checker, 13 << 20, 65536, "ppccpcpp")
 
 
+def _bets_run_by_run(lib, checker):
+    """Four batches on one context, every one cut into two runs of 64 max-blocks (8 MiB at 64 KiB, ZULTRA_HIP_STREAMS=2 — set by the caller): A = text | tables and
+    near-copies, B = the halves swapped; A, B, A, A. Returns, per batch, (batches_rerun so far, runs_without_chain_kernels, runs) — every batch's bytes are the checker's."""
+    n, bs = 4 << 20, 65536
+    text = corpus.text_like(n, 31)
+    mix = np.concatenate([corpus.table_like(n // 2, 9), corpus.duplicated(n - n // 2, 4, 900)])   # (the mixture of _chains_after_none)
+    data = {"A": np.concatenate([text, mix]), "B": np.concatenate([mix, text])}
+    want = {k: checker.memory_compress(d, 0, bs) for k, d in data.items()}
+    nb = 2 * n // bs
+    blocks = [(b * bs - (32768 if b else 0), 32768 if b else 0, bs) for b in range(nb)]
+    ctx = lib.context(bs, nb)
+    seen = []
+    try:
+        for k, name in enumerate("ABAA"):
+            ctx.compress_blocks(data[name], blocks)
+            st = ctx.stats()
+            end_bit, _ = ctx.stitch_device(nb - 1, phase=0)
+            assert ctx.stream_read((end_bit + 7) // 8).tobytes() == want[name], (k, name)
+            seen.append((st["batches_rerun"], st["runs_without_chain_kernels"], st["runs"]))
+    finally:
+        ctx.close()
+    return seen
+
+
+def test_a_bet_is_placed_and_settled_run_by_run(gpu, checker, monkeypatch):
+    """The bets of zh_run_is_void are per run, which test_chains_turn_up_after_a_batch_without_any does not pin ("a batch with chains may hold a run without any"): two
+    runs whose halves change kind from batch to batch. The first batch of a context bets nothing. B's first run lists chains against a no-chains bet: the batch is run
+    again, and in that rerun its second run — text, which listed no chain in the attempt just read back — already goes without chain kernels. A's second run then lists
+    chains against that bet: run again, now its first run without. The fourth batch repeats the third and wins its one bet."""
+    monkeypatch.setenv("ZULTRA_HIP_STREAMS", "2")
+    seen = _bets_run_by_run(gpu, checker)
+    assert [s[2] for s in seen] == [2, 2, 2, 2], seen
+    assert [s[0] for s in seen] == [0, 1, 2, 2], seen
+    assert [s[1] for s in seen] == [0, 1, 1, 1], seen
+
+
 @pytest.mark.parametrize("runs", ["1", "2", "3"])
 def test_a_run_needs_no_host_decision(gpu, checker, monkeypatch, runs):
     """Sub-block counts, task counts, chains and cut tasks are summed up on the device (zh_plan_subblocks, zh_list_huge) and every later kernel takes

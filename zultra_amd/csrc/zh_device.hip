@@ -101,6 +101,21 @@ struct zh_assembly_t {
    int rc;                // zh_stitch_verdict of it: the buffer is usable iff layout != NONE && rc == 0
 };
 
+// The bets of a context: run k of a batch is enqueued without chain kernels, or without the <true> overflow forms, where run k of the LAST batch of max-blocks needed
+// none (zh_parse.h, zh_run_is_void) — written by zh_bets_place / zh_bets_enqueue_* / zh_bets_settle alone.
+struct zh_bet_t {
+   uint32_t seen_chains, seen_nsubs, seen_ntasks;   // the last batch's run k: tasks listed for zh_parse_chain + cut tasks, sub-blocks, tasks (its counters, read back with its results)
+   bool no_chains, no_more;                         // this batch's run k went out without chain kernels / without <true> forms (its grids are h_grids[2k], [2k + 1])
+   uint32_t b0;                                     // ... and its first max-block (diagnostics: zultra_hip_cut_tasks)
+};
+struct zh_bets_t {
+   int on;               // ZULTRA_HIP_CHAIN_SKIP (default 1; 0: every run gets chain kernels and overflow forms)
+   int seen_runs;        // runs of the batch the seen_* are of (0: no batch yet): they say nothing to a batch cut into another number of runs
+   uint32_t reruns;      // batches run again because a run lost a bet
+   uint32_t *h_grids;    // pinned, two per run: what goes into the counters ZH_CNT_SBGRID, ZH_CNT_TASKGRID of a run without <true> forms
+   zh_bet_t run[ZH_MAX_RUNS];
+};
+
 struct zultra_hip_ctx_s {
    int device;
    uint32_t num_cus;            // persistent kernels launch one workgroup per CU
@@ -129,17 +144,7 @@ struct zultra_hip_ctx_s {
    zh_stitch_job_t stitch_job;  // the stitch on the context's stream: what zh_stitch_begin enqueued, for zh_stitch_finish
    zh_stitch_job_t armed_job;   // a stitch enqueued with its batch (zultra_hip_stitch_with_batch) ...
    bool armed;                  // ... armed for the next batch
-   // what the runs of the LAST batch of max-blocks listed for zh_parse_chain (their counters, read back with the batch's results): a context whose last batch had no chain
-   // at all in run k enqueues run k of the next batch without chain kernels (zh_enqueue_run; zh_parse.h: zh_run_is_void)
-   int chain_seen_runs;                  // runs of that batch (0: no batch yet)
-   uint32_t chain_redone;                // batches run again because a run without chain kernels listed chains
-   uint32_t chain_seen[ZH_MAX_RUNS];     // per run: tasks listed + cut tasks
-   int chain_skip;                       // ZULTRA_HIP_CHAIN_SKIP (default 1): such a run is enqueued without chain kernels (0: always with them)
-   uint32_t seen_nsubs[ZH_MAX_RUNS], seen_ntasks[ZH_MAX_RUNS];   // ... and how many sub-blocks and tasks they had: a run that stayed inside the <false> grids last time gets no <true> forms
-   bool run_nomore[ZH_MAX_RUNS];         // this batch: run k was enqueued without them (its grids are in its counters, zh_run_is_void)
-   uint32_t run_grids[ZH_MAX_RUNS][2];   // ... the grids (sub-blocks, tasks) of its <false> forms, as enqueued
-   uint32_t *h_grids;                    // pinned: what goes into the counters (ZH_CNT_SBGRID, ZH_CNT_TASKGRID) of such runs
-   bool run_nochains[ZH_MAX_RUNS];       // this batch: run k was enqueued without
+   zh_bets_t bets;              // "the last batch predicts this one", run by run (zh_bets_*)
    uint32_t streams_respread;   // streams replaced at creation because they shared a hardware queue with a more important one (zh_spread_streams)
    uint32_t grid_cap;           // ZULTRA_HIP_GRID_CAP (tests): the <false> grids of the per-sub-block / per-task kernels are capped here, so that the <true> forms behind them get work
    uint32_t mf_lds_cap;         // zh_mf_group: chunk size of the refinement in LDS (at least 16 are taken)
@@ -174,7 +179,6 @@ struct zultra_hip_ctx_s {
    uint32_t seg_whole;          // ... with fewer, zh_parse_chain takes the segments — and the cut tasks shorter than this whole (ZULTRA_HIP_SEG_WHOLE)
    int auto_runs;               // ZULTRA_HIP_STREAMS not set: the number of runs follows the batch size
    int last_runs;               // runs the last batch was cut into
-   uint32_t last_run_b0[ZH_MAX_RUNS];   // ... and the first max-block of each (diagnostics: zultra_hip_cut_tasks)
    uint32_t seg_wide;           // a run with at least this many segments parses them in the segment workgroups of zh_parse_lanes' launch (ZULTRA_HIP_SEG_WIDE)
    int16_t *d_vecs;             // two cost vectors per segment
    uint64_t seg_tasks_per_block, seg_items_per_block;
@@ -575,7 +579,7 @@ enum { ZH_SET_CORE = 1, ZH_SET_FILES = 2, ZH_SET_BLOCKS = 4, ZH_SET_TRACE = 8, Z
    X(ZH_SET_CORE, DEV, d_results_compact, U)                    /* the runs' sub-block descriptors laid end to end (zh_stitch.h) */                                      \
    X(ZH_SET_CORE, PIN, h_nsubs, 1 + ZH_MAX_RUNS)                /* mirror of d_nsubs */                                                                                  \
    X(ZH_SET_CORE, PIN, h_scan_out, 1)                           /* mirror of d_scan_out, read after the one synchronisation of a stitch */                               \
-   X(ZH_SET_CORE, PIN, h_grids, 2 * ZH_MAX_RUNS)                /* what goes into the counters ZH_CNT_SBGRID, ZH_CNT_TASKGRID of runs without <true> forms */            \
+   X(ZH_SET_CORE, PIN, bets.h_grids, 2 * ZH_MAX_RUNS)           /* what goes into the counters ZH_CNT_SBGRID, ZH_CNT_TASKGRID of runs without <true> forms */            \
    X(ZH_SET_CORE, PIN, h_crc, B)                                /* mirror of d_crc */                                                                                    \
    X(ZH_SET_CORE, PIN, h_blocks, B)                             /* staging of the batch's descriptors: an async copy from pageable memory is a blocking, staged one */   \
    X(ZH_SET_FILES, PIN, h_task_prefix, B + 1)                   /* staging of d_task_prefix */                                                                           \
@@ -864,8 +868,8 @@ static int zh_create_buffers(zultra_hip_ctx_t *c) {
       if (c->coop_small < 64u) c->coop_small = 64u;
       if (c->coop_small > ZH_COOP_MIN) c->coop_small = ZH_COOP_MIN;
       c->seg_whole = (uint32_t)zh_env("ZULTRA_HIP_SEG_WHOLE", 16384);  // cut tasks shorter than this are parsed whole when zh_parse_chain takes the segments
-      c->chain_skip = zh_env("ZULTRA_HIP_CHAIN_SKIP", 1);   // 1: a run whose counterpart in the context's last batch listed no chain is enqueued without chain kernels (0: always with them)
-      c->chain_seen_runs = 0;
+      c->bets.on = zh_env("ZULTRA_HIP_CHAIN_SKIP", 1);   // 1: a run whose counterpart in the context's last batch listed no chain is enqueued without chain kernels (0: always with them)
+      c->bets.seen_runs = 0;
       c->grid_cap = (uint32_t)max(0, zh_env("ZULTRA_HIP_GRID_CAP", 0));   // tests: cap of the <false> grids of zh_sb_init / zh_sb_build / zh_list_huge / zh_post_tasks / zh_emit_tasks (0: none) — the
                                                                           // <true> forms that stride over what lies beyond a grid are otherwise reached by heavily splitting data only
       c->lane_order = zh_env("ZULTRA_HIP_LANE_ORDER", 1) != 0;         // 1: zh_parse_lanes takes its bundles longest class first; 0: as zh_list_huge completed them (the A/B of the order)
@@ -1031,26 +1035,6 @@ static uint32_t zh_tasks_per_wave(const zultra_hip_ctx_t *c, uint32_t ntasks) {
    return max(1u, min((uint32_t)ZH_LP_TASKS, (ntasks + slots - 1) / slots));
 }
 
-// barrier bitmap and greedy token chain of `nb` max-blocks starting at batch block b0, in chunks (zh_split.h)
-static int zh_enqueue_tokenize(zultra_hip_ctx_t *c, hipStream_t st, const zh_block_t *blk, uint32_t b0, uint32_t nb) {
-   // (chunks of an eighth for a BATCH of a few max-blocks — all its runs alike: they share the per-chunk arrays, which are sized for the small chunks; files mode:
-   // an input is one chunk)
-   const uint32_t chunk = (!c->files_mode && c->nblocks <= ZH_TOK_SMALL_BATCH) ? (uint32_t)ZH_TOK_CHUNK_SMALL : (uint32_t)ZH_TOK_CHUNK;
-   const uint32_t cpb = (c->max_block + chunk - 1) / chunk;
-   const uint32_t *match = (const uint32_t *)(c->d_match + (uint64_t)b0 * c->match_stride);   // slot 0 of a position's row = its longest match
-   uint64_t *bars = c->d_bars + (uint64_t)b0 * c->bar_stride;
-   uint32_t *tp = c->d_tok_pos + (uint64_t)b0 * c->tok_stride;
-   uint16_t *ti = c->d_tok_info + (uint64_t)b0 * c->tok_stride;
-   uint32_t *cmax = c->d_chunkmax + (uint64_t)b0 * cpb, *sstart = c->d_spanstart + (uint64_t)b0 * cpb, *scnt = c->d_spancnt + (uint64_t)b0 * cpb;
-   uint32_t *slot0 = c->d_best + (uint64_t)b0 * c->best_stride;   // (free until the run's first parse pass: zh_split.h)
-   ZH_LAUNCH(zh_barriers, nb * cpb, 64, st, blk, match, c->match_stride, bars, c->bar_stride, cmax, cpb, chunk, slot0, c->best_stride);
-   if (cpb > 1) ZH_LAUNCH(zh_barriers_fix, (nb + 63) / 64, 64, st, blk, nb, bars, c->bar_stride, (const uint32_t *)cmax, cpb, chunk);
-   ZH_LAUNCH(zh_tokenize_spans, nb * cpb, 64, st, c->cur_data, blk, (const uint32_t *)slot0, c->best_stride, tp, ti, c->tok_stride, (const uint64_t *)bars, c->bar_stride, sstart, scnt,
-             cpb, chunk);
-   ZH_LAUNCH(zh_tokens_compact, nb, ZH_COMPACT_THREADS, st, blk, tp, ti, c->tok_stride, (const uint32_t *)sstart, (const uint32_t *)scnt, cpb, chunk, c->d_ntok + b0);
-   return 0;
-}
-
 // files mode: what zh_split would report for an input below its 8192-byte threshold — one sub-block spanning all tokens
 __global__ void zh_nosplit(uint32_t nblocks, const uint32_t *__restrict__ ntok, uint32_t *split_tok, uint32_t *split_cnt) {
    const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1060,31 +1044,27 @@ __global__ void zh_nosplit(uint32_t nblocks, const uint32_t *__restrict__ ntok, 
    split_cnt[b] = 1;
 }
 
-// The kernel sequence of one run of a batch — max-blocks b0 .. b0 + nb with `total_n` input bytes, matchfinder segments sg0 .. sg0 + nsg — with
-// NO HOST DECISION in it: run k on stream st, its chains on `side` (a cut task's segments, when a run has many, in the first workgroups of zh_parse_lanes' grid; not in files
-// mode: inputs below 8192 bytes are never cut). Everything the splitter decides — how many sub-blocks, hence how many tasks, chains, segments — stays on the device: zh_plan_subblocks
-// sums it up into the run's counters, every later kernel takes its bounds from there, and the grids here are sized from the input bytes alone, as
-// bounded grids that stride over what there is (rounds 1-4 read the counts back twice per run, in the middle of the pipeline: 0.8-2.2 ms each on the
-// 100 MB step, profiles/r04_timeline_c2.txt). Per-block buffers are addressed as base + block * stride, so a run sees the base pointers advanced to its
-// first max-block; sub-block and task indices are local to the run (zh_compact_results shifts the descriptors).
-// part: 0 the whole run; 1 only up to the end of its first matchfinder kernel (where the next run's matchfinder may start), 2 only what follows — the two
-// halves of a files-mode run captured as graphs of their own (zh_run_files).
-// A kernel whose item count only the device knows (sub-blocks, tasks, segment waves of a run): the <false> form over `grid_` workgroups, one item each (what data
-// usually gives; surplus workgroups leave at once), then the <true> form, ZH_MORE_GRID workgroups striding over what lies beyond grid_ — nearly always nothing.
-// (bound_: what the item count cannot exceed — a grid that covers it needs no second launch: a call on a few max-blocks is a matter of launches)
-#define ZH_MORE_GRID 256u
-#define ZH_LAUNCH_BOTH(kernel_, grid_, bound_, stream_, ...)                                                                  \
-   do {                                                                                                                       \
-      ZH_LAUNCH(kernel_<false>, (grid_), 64, stream_, __VA_ARGS__, 0u);                                                       \
-      if ((uint64_t)(grid_) < (uint64_t)(bound_) && !no_more) ZH_LAUNCH(kernel_<true>, ZH_MORE_GRID, 64, stream_, __VA_ARGS__, (uint32_t)(grid_)); \
-   } while (0)
+// ---- one run of a batch: its view of the context, its bets, its kernel sequence -------------------------------------------------------------------
 
-static int zh_enqueue_run(zultra_hip_ctx_t *c, int k, uint32_t b0, uint32_t nb, uint64_t total_n, uint32_t max_n, uint32_t sg0, uint32_t nsg, hipStream_t st, hipStream_t side, int part) {
-   const bool files = c->files_mode != 0;
-   hipEvent_t *ev = c->lane_ev[k];
+// A run of a batch as its kernels see it — run k: max-blocks b0 .. b0 + nb with `total_n` input bytes (the largest block max_n), matchfinder segments sg0 .. sg0 + nsg.
+// Host only: its constructor fills it — every member from those before it, in the order they stand in —, the stage functions (zh_run_*) take everything of the run from it.
+// Per-block buffers are addressed as base + block * stride, so a run sees the base pointers advanced to its first max-block; sub-block and task indices are local to the run
+// (zh_compact_results shifts the descriptors). What files mode does differently — inputs below 8192 bytes are never cut and keep no bundle lists, events would be nodes of a
+// captured graph — is resolved here, once.
+struct zh_run_t {
+   zultra_hip_ctx_t *c;
+   int k;
+   uint32_t b0, nb, sg0, nsg, max_n;
+   uint64_t total_n;
+   zh_run_t(zultra_hip_ctx_t *c_, int k_, uint32_t b0_, uint32_t nb_, uint64_t total_n_, uint32_t max_n_, uint32_t sg0_, uint32_t nsg_)
+       : c(c_), k(k_), b0(b0_), nb(nb_), sg0(sg0_), nsg(nsg_), max_n(max_n_), total_n(total_n_) {
+      if (c->grid_cap) task_grid = max(1u, min(task_grid, c->grid_cap)), sb_grid = max(1u, min(sb_grid, c->grid_cap));   // (tests: everything beyond the cap goes through the <true> forms)
+   }
+   bool files = c->files_mode != 0;
+   hipStream_t st = c->lane_stream[k], side = c->side_stream[k];   // the run's kernels; its chains (zh_parse_chain next to zh_parse_lanes) and what needs the input only
+   hipEvent_t *ev = c->lane_ev[k], *side_ev = c->side_ev[k];       // ev: indexed by enum zh_run_event; side_ev: per pass, fork and join
    const zh_block_t *blk = c->d_blocks + b0;
-   const uint64_t tasks_per_block = c->max_tasks / c->max_blocks;
-   const uint64_t s0 = (uint64_t)b0 * c->max_subs, t0 = (uint64_t)b0 * tasks_per_block;   // per-sub-block and per-task buffers of the run start at its worst-case offset
+   uint64_t tasks_per_block = c->max_tasks / c->max_blocks, s0 = (uint64_t)b0 * c->max_subs, t0 = (uint64_t)b0 * tasks_per_block;   // per-sub-block and per-task buffers of the run start at its worst-case offset
    const zh_seg_t *sgs = c->d_segs + sg0;
    uint32_t *sa = c->d_sort_a + (uint64_t)sg0 * c->sort_stride, *sb = c->d_sort_b + (uint64_t)sg0 * c->sort_stride;
    uint2 *p3 = c->d_prev3 + (uint64_t)sg0 * c->sort_stride;
@@ -1092,163 +1072,232 @@ static int zh_enqueue_run(zultra_hip_ctx_t *c, int k, uint32_t b0, uint32_t nb, 
    uint32_t *ctr = c->d_chunk_ctr + (size_t)sg0 * 2 + 3 * (size_t)k;   // this run's counters: 2 per segment + the three tickets
    uint32_t *pay = c->d_pay + (size_t)k * zh_min64(c->total_cus, (uint64_t)c->max_blocks * c->segs_per_block) * 3 * c->sort_stride;
    uint32_t *cnt = c->d_ntasks + (size_t)k * ZH_CNT_STRIDE;   // the run's counters (ZH_CNT_*)
+   // (tokenizer: chunks of an eighth for a BATCH of a few max-blocks — all its runs alike: they share the per-chunk arrays, which are sized for the small chunks; files mode:
+   // an input is one chunk)
+   uint32_t tok_chunk = (!files && c->nblocks <= ZH_TOK_SMALL_BATCH) ? (uint32_t)ZH_TOK_CHUNK_SMALL : (uint32_t)ZH_TOK_CHUNK, cpb = (c->max_block + tok_chunk - 1) / tok_chunk;
+   uint32_t *chunkmax = c->d_chunkmax + (uint64_t)b0 * cpb, *spanstart = c->d_spanstart + (uint64_t)b0 * cpb, *spancnt = c->d_spancnt + (uint64_t)b0 * cpb;
+   uint32_t *tok_pos = c->d_tok_pos + (uint64_t)b0 * c->tok_stride, *ntok = c->d_ntok + b0;
+   uint32_t *split_tok = c->d_split_tok + (uint64_t)b0 * (ZH_MAX_SPLITS + 1), *split_cnt = c->d_split_cnt + b0, *sub_base = c->d_sub_base + b0;
+   const uint32_t *task_prefix = files ? c->d_task_prefix + b0 : (const uint32_t *)NULL;
    zh_work_t *work = c->d_work + s0;
    zh_sbstate_t *states = c->d_states + s0;
-   uint2 *taskmap = c->d_taskmap + t0;
-   uint2 *taskinfo = c->d_taskinfo + t0;
+   zh_subblock_t *results = c->d_results + s0;
+   uint2 *taskmap = c->d_taskmap + t0, *taskinfo = c->d_taskinfo + t0;   // taskinfo: per task, its range and whether zh_list_huge listed it
    uint32_t *hist_part = c->d_hist_part + t0 * ZH_NSYM, *task_bits = c->d_task_bits + t0;
    // the bundles of zh_parse_lanes (zh_parse.h): ZH_LANE_CLASSES lists of `cap` entries; files mode keeps none — its inputs are one sub-block of a task or two each
-   const bool bundles = !files && c->lane_bundles != 0;
+   bool bundles = !files && c->lane_bundles != 0;
    uint32_t *lanelist = bundles ? c->d_lanelist + ZH_LANE_CLASSES * t0 : (uint32_t *)NULL, *lane_acc = bundles ? c->d_lane_acc + t0 : (uint32_t *)NULL;
    uint32_t *hugelist = c->d_hugelist + 4 * t0;   // four lists of `cap` entries each: three by zh_list_huge, the cut tasks given up on by the segment workgroups
-   const uint32_t cap = (uint32_t)zh_min64((uint64_t)nb * tasks_per_block, 0xFFFFFFFFull);
+   uint32_t cap = (uint32_t)zh_min64((uint64_t)nb * tasks_per_block, 0xFFFFFFFFull);
    uint4 *segtasks = c->d_segtasks + (uint64_t)b0 * c->seg_tasks_per_block;
    uint2 *segwaves = c->d_segwaves + (uint64_t)b0 * c->seg_items_per_block, *segitems = c->d_segitems + (uint64_t)b0 * c->seg_items_per_block;
    int16_t *vecs = c->d_vecs + (uint64_t)b0 * c->seg_items_per_block * 2 * ZH_VEC;
    uint8_t *payload = c->d_payload + (uint64_t)b0 * c->slot_stride;
-   uint32_t *best = c->d_best + (uint64_t)b0 * c->best_stride;
-   uint16_t *cost = c->d_cost + (uint64_t)b0 * c->best_stride;
-   const uint64_t *bars = c->d_bars + (uint64_t)b0 * c->bar_stride;
+   uint32_t *best = c->d_best + (uint64_t)b0 * c->best_stride;   // (free until the run's first parse pass: slot 0 of the tokenizer, zh_split.h)
+   uint16_t *cost = c->d_cost + (uint64_t)b0 * c->best_stride, *tok_info = c->d_tok_info + (uint64_t)b0 * c->tok_stride;
+   uint64_t *bars = c->d_bars + (uint64_t)b0 * c->bar_stride;
    const zh_match_t *match = c->d_match + (uint64_t)b0 * c->match_stride;
-   const uint32_t mf_grid = min(nsg, c->num_cus);   // persistent workgroups, one per CU (zh_matchfinder.h)
-   // grids: bounded by what the input bytes allow, sized for what data usually gives; the kernels stride
-   const uint32_t est_tasks = (uint32_t)zh_min64(cap, total_n / ZH_TASK + 2ull * nb);                                   // tasks: ~ bytes / 2048 + one per sub-block
-   uint32_t task_grid = cap <= 2048u ? cap : (uint32_t)zh_min64(cap, total_n / ZH_TASK + 4ull * nb);               // one wave per task (zh_list_huge, zh_post_tasks, zh_emit_tasks)
-   const uint64_t sb_bound = (uint64_t)nb * c->max_subs;
-   uint32_t sb_grid = (uint32_t)zh_min64(sb_bound, zh_max64(4ull * nb, 1024));   // one wave per sub-block (zh_sb_init, zh_sb_build)
-   if (c->grid_cap) {   // (tests: everything beyond the cap goes through the <true> forms)
-      task_grid = max(1u, min(task_grid, c->grid_cap));
-      sb_grid = max(1u, min(sb_grid, c->grid_cap));
-   }
-   // no <true> overflow forms where the context's last batch stayed inside these grids (zh_parse.h, zh_run_is_void): the grids go into the run's counters, a run that
-   // outgrows them is void and the batch is run again with the forms
-   const bool no_more = !files && c->chain_skip && c->chain_seen_runs == c->last_runs && c->seen_nsubs[k] <= sb_grid && c->seen_ntasks[k] <= task_grid &&
-                        ((uint64_t)sb_grid < sb_bound || (uint64_t)task_grid < (uint64_t)cap);
-   c->run_nomore[k] = no_more;
-   c->run_grids[k][0] = sb_grid;
-   c->run_grids[k][1] = task_grid;
-   if (no_more) {
-      c->h_grids[2 * k] = sb_grid;
-      c->h_grids[2 * k + 1] = task_grid;
-      ZH_CHECK(c, hipMemcpyAsync(cnt + ZH_CNT_SBGRID, c->h_grids + 2 * k, 2 * sizeof(uint32_t), hipMemcpyHostToDevice, st));   // (behind the clearing of the run's counters, on this stream)
-   }
-   const uint64_t seg_bound = (uint64_t)nb * c->seg_items_per_block;                     // entries of segwaves (zh_list_huge)
-   if (part != 2) {
-      ZH_LAUNCH_LDS(zh_mf_group<true>, mf_grid, ZH_MF_THREADS, ZH_MF_GROUP_LDS, st, c->cur_data, sgs, sa, sb, p3, rn, c->sort_stride, c->run_stride, nsg, ctr + (size_t)nsg * 2 + 1, pay,
-                    c->mf_lds_cap);
-      // the bigram classes that fit no chunk of zh_mf_group, noted by it (zh_mf_group_lds.h): a kernel of their own (inputs of <= 4 KiB are one chunk: nothing is ever noted)
-      if (c->seg_W > zh_mfl_cap(c->seg_W, c->mf_lds_cap))   // (a smaller window's chunks are no smaller)
-         ZH_LAUNCH_LDS(zh_mf_group_big, files ? min(mf_grid, 32u) : mf_grid, ZH_MF_THREADS, ZH_MF_GROUP_LDS, st, c->cur_data, sgs, sa, sb, p3, (const uint32_t *)rn, c->sort_stride, c->run_stride, nsg,
-                       ctr + (size_t)nsg * 2 + 2, pay);
-   }
-   if (part == 1) return 0;
-   if (part == 0) ZH_CHECK(c, hipEventRecord(ev[ZH_EV_GROUP], st));   // the next run's matchfinder starts here (part 2: the caller records it between the two graphs)
-   // (segment descriptors carry batch-wide block indices: the rows go to d_match + block * match_stride)
+   uint32_t *crc = c->d_crc + b0, *adler = c->d_adler + 2 * (size_t)b0;
+   uint64_t *chain_trace = (c->d_chain_trace && !files) ? c->d_chain_trace + 3 * (uint64_t)ZH_TRACE_SLOTS * (4 * k) : (uint64_t *)NULL;   // diagnostics: the run's [pass][ticket] records
+   uint32_t mf_grid = min(nsg, c->num_cus), mf_big_grid = files ? min(mf_grid, 32u) : mf_grid;   // persistent workgroups, one per CU (zh_matchfinder.h): zh_mf_group, zh_mf_group_big
    // a run of fewer segments than CUs (one call on a few max-blocks: latency): the workgroups beyond one per segment find the tickets gone and help —
    // a segment of a 64 KiB max-block is ~1500 chunks, shared while a helper's share stays above ZH_MF_HELP_MIN of them (small inputs: nothing worth sharing)
-   const uint32_t fr_grid = files ? mf_grid : min(c->num_cus, mf_grid * 8u);
-   ZH_LAUNCH_LDS(zh_mf_frontier<true>, fr_grid, ZH_MF_THREADS, ZH_MF_FRONTIER_LDS, st, c->cur_data, sgs, (const uint32_t *)sa, (const uint2 *)p3, (const uint32_t *)rn, c->sort_stride,
-                 c->run_stride, c->d_match, c->match_stride, (uint32_t *)nullptr, c->tok_stride, ctr, nsg, files ? 0u : 1u);
-   if (!files) ZH_CHECK(c, hipEventRecord(ev[ZH_EV_FRONTIER], st));   // (timing marks)
-   if (zh_enqueue_tokenize(c, st, blk, b0, nb) != 0) return -1;
-   if (files)
-      ZH_LAUNCH(zh_nosplit, (nb + 255) / 256, 256, st, nb, (const uint32_t *)(c->d_ntok + b0), c->d_split_tok + (uint64_t)b0 * (ZH_MAX_SPLITS + 1), c->d_split_cnt + b0);
-   else {
-#define ZH_LAUNCH_SPLIT(W_)                                                                                                                                   \
-   ZH_LAUNCH(zh_split<W_>, nb, 64 * W_, st, blk, (const uint32_t *)(c->d_tok_pos + b0 * c->tok_stride), (const uint16_t *)(c->d_tok_info + b0 * c->tok_stride), \
-             c->tok_stride, (const uint32_t *)(c->d_ntok + b0), c->d_split_tok + (uint64_t)b0 * (ZH_MAX_SPLITS + 1), c->d_split_cnt + b0)
-      if (max_n > 131072)   // (by the run's largest max-block, not the context's limit)
-         ZH_LAUNCH_SPLIT(16);
-      else
-         ZH_LAUNCH_SPLIT(8);
-#undef ZH_LAUNCH_SPLIT
-   }
-   if (!files) ZH_CHECK(c, hipEventRecord(ev[ZH_EV_SPLIT], st));   // (timing marks)
-   // ---- stage 3: the sub-block coder, one kernel per step over the run (zh_encode.h) -----------------------------------------------------
-#define ZH_LAUNCH_PLAN(T_)                                                                                                                                                               \
-   ZH_LAUNCH(zh_plan_subblocks<T_>, 1, T_, st, blk, nb, (const uint32_t *)(c->d_tok_pos + (uint64_t)b0 * c->tok_stride), c->tok_stride, (const uint32_t *)(c->d_ntok + b0),              \
-             (const uint32_t *)(c->d_split_tok + (uint64_t)b0 * (ZH_MAX_SPLITS + 1)), (const uint32_t *)(c->d_split_cnt + b0), c->d_sub_base + b0, c->slot_stride, work, taskmap, cnt, lane_acc)
-   if (files)   // one sub-block per input, the task ranges from the sizes the host was handed (zh_plan_files)
-      ZH_LAUNCH(zh_plan_files, (nb + ZH_PLAN_FILES_THREADS - 1) / ZH_PLAN_FILES_THREADS, ZH_PLAN_FILES_THREADS, st, blk, nb, (const uint32_t *)(c->d_ntok + b0), (const uint32_t *)(c->d_task_prefix + b0),
-                c->d_sub_base + b0, c->slot_stride, work, taskmap, cnt);
-   else if (nb > 4096u)
-      ZH_LAUNCH_PLAN(1024u);
-   else
-      ZH_LAUNCH_PLAN(256u);
-#undef ZH_LAUNCH_PLAN
-   ZH_LAUNCH_BOTH(zh_sb_init, sb_grid, sb_bound, st, (const uint16_t *)(c->d_tok_info + (uint64_t)b0 * c->tok_stride), c->tok_stride, (const zh_work_t *)work, states, (const uint32_t *)cnt);
-   const uint32_t tpw = zh_tasks_per_wave(c, est_tasks);   // tasks per bundle of zh_parse_lanes: zh_list_huge lists the bundles
-   const zh_lane_order_t lane_lo = {lanelist, lane_acc, tpw, c->lane_order};
-   // (inputs of a files batch are never cut into speculative segments: seg_min = all ones; a run of at most as many tasks as CUs counts as small)
-   ZH_LAUNCH_BOTH(zh_list_huge, task_grid, cap, st, blk, bars, c->bar_stride, (const zh_work_t *)work, (const uint2 *)taskmap, (const uint32_t *)(c->d_match + (uint64_t)b0 * c->match_stride),
-             c->match_stride, hugelist, cap, segtasks, segitems, segwaves, files ? 0xFFFFFFFFu : (uint32_t)ZH_CUT_MIN, (uint32_t)ZH_CUT_LEN, cnt, taskinfo, (uint32_t)ZH_COOP_MIN,
-             files ? (uint32_t)ZH_COOP_MIN : c->coop_small, files ? 0u : c->num_cus, lane_lo);
-   if (!files) ZH_CHECK(c, hipEventRecord(ev[ZH_EV_INIT], st));   // (timing marks)
+   uint32_t fr_grid = files ? mf_grid : min(c->num_cus, mf_grid * 8u), mf_steal = files ? 0u : 1u;
+   // grids: bounded by what the input bytes allow, sized for what data usually gives; the kernels stride
+   uint32_t est_tasks = (uint32_t)zh_min64(cap, total_n / ZH_TASK + 2ull * nb);                                   // tasks: ~ bytes / 2048 + one per sub-block
+   uint32_t task_grid = cap <= 2048u ? cap : (uint32_t)zh_min64(cap, total_n / ZH_TASK + 4ull * nb);             // one wave per task (zh_list_huge, zh_post_tasks, zh_emit_tasks)
+   uint64_t sb_bound = (uint64_t)nb * c->max_subs, seg_bound = (uint64_t)nb * c->seg_items_per_block;   // seg_bound: entries of segwaves (zh_list_huge)
+   uint32_t sb_grid = (uint32_t)zh_min64(sb_bound, zh_max64(4ull * nb, 1024));   // one wave per sub-block (zh_sb_init, zh_sb_build)
+   uint32_t tpw = zh_tasks_per_wave(c, est_tasks);   // tasks per bundle of zh_parse_lanes: zh_list_huge lists the bundles
+   // (zh_list_huge: inputs of a files batch are never cut into speculative segments, seg_min = all ones; a run of at most as many tasks as CUs — list_cus — counts as small)
+   uint32_t seg_min = files ? 0xFFFFFFFFu : (uint32_t)ZH_CUT_MIN, coop_small = files ? (uint32_t)ZH_COOP_MIN : c->coop_small, list_cus = files ? 0u : c->num_cus;
    // Persistent workgroups of zh_parse_chain take the listed chains from a ticket (none listed: they leave at once); zh_parse_lanes takes the task
-   // list in groups, as a grid that fills the chip's wave slots — next to chains only ZH_LANE_WAVES per CU stay, so that the chain workgroups find
+   // list in groups, as a grid that fills the chip's wave slots — next to chains only ZH_LANE_WAVES per CU stay (lane_waves), so that the chain workgroups find
    // room the moment they are launched (the run's counters tell the kernel which); the first workgroups of zh_parse_lanes' grid take the cut tasks' segments when there are many.
-   const uint32_t lane_grid = max(1u, min((est_tasks + tpw - 1) / tpw, c->num_cus * 16u));
+   uint32_t lane_grid = max(1u, min((est_tasks + tpw - 1) / tpw, c->num_cus * 16u)), lane_waves = files ? 0xFFFFFFFFu : c->num_cus * ZH_LANE_WAVES;
    // (two chain workgroups fit a CU — 169 registers, four waves — and they are persistent: a third per CU would only queue behind them, find the tickets
    // gone and leave; and in a run without chains every workgroup of this grid has to find a slot among the quad kernel's waves before the pass can end)
    uint32_t chain_grid = files ? min(nb, (uint32_t)ZH_CHAIN_GRID) : (uint32_t)zh_min64(zh_min64(ZH_CHAIN_GRID, 2u * c->num_cus), total_n / 256u + nb);
-   // A stream without chains must not pay for them (round 6; zh_parse.h, zh_run_is_void): a run whose counterpart in the context's last batch listed nothing for
-   // zh_parse_chain gets no chain kernel at all — no fork, no grid to schedule among the quad kernels' waves, no join — and a mark in its counters that says so.
-   const bool chains_idle = !files && c->run_nochains[k];
-   if (chains_idle) ZH_CHECK(c, hipMemsetAsync(cnt + ZH_CNT_NOCHAINS, 1, sizeof(uint32_t), st));   // (non-zero: zh_run_is_void; the run's counters were cleared on this stream before)
-   const uint32_t seg_grid = (uint32_t)zh_min64(c->num_cus * 8u, zh_max64(1, seg_bound));
-   if (chains_idle) {
-      // what the side stream was given at the start of the batch (checksums, clearing the payload slots and the stream buffer) is otherwise joined with the chains
-      ZH_CHECK(c, hipEventRecord(c->side_ev[k][1], side));
-      ZH_CHECK(c, hipStreamWaitEvent(st, c->side_ev[k][1], 0));
+   uint32_t seg_grid = files ? 0u : (uint32_t)zh_min64(c->num_cus * 8u, zh_max64(1, seg_bound));
+};
+
+// The bets of run k (c->bets.run[k]; why, and what a lost one costs: zh_parse.h, zh_run_is_void). Where its counterpart in the context's last batch listed nothing for
+// zh_parse_chain the run gets no chain kernel at all — no fork, no grid to schedule among the quad kernels' waves, no join —, where that stayed inside this batch's <false>
+// grids, no <true> overflow forms; either is marked in the run's counters. These functions alone write the record: zh_bets_place decides, zh_bets_enqueue_* put the marks on
+// the run's stream, zh_bets_settle reads the device's verdict behind the batch. The stage functions and the diagnostics only read it.
+// (Placed whenever a run is enqueued — a files run too, once per captured part: it bets nothing, and nobody asks for its b0. Entries of runs this batch does not have keep what
+// an earlier batch left: nothing reads them.)
+static const zh_bet_t &zh_bets_place(zultra_hip_ctx_t *c, const zh_run_t &r) {
+   zh_bet_t &b = c->bets.run[r.k];
+   const bool known = !r.files && c->bets.on && c->bets.seen_runs == c->last_runs;   // (a batch cut into another number of runs says nothing about this one's)
+   b.no_chains = known && b.seen_chains == 0;
+   b.no_more = known && b.seen_nsubs <= r.sb_grid && b.seen_ntasks <= r.task_grid && ((uint64_t)r.sb_grid < r.sb_bound || (uint64_t)r.task_grid < (uint64_t)r.cap);
+   b.b0 = r.b0;
+   return b;
+}
+
+// The marks in the run's counters (non-zero words: zh_run_is_void), on the run's stream, which cleared them before. In front of the run's first kernel: the grids of a run
+// without <true> forms ...
+static int zh_bets_enqueue_grids(zultra_hip_ctx_t *c, const zh_run_t &r, const zh_bet_t &bet) {
+   uint32_t *grids = c->bets.h_grids + 2 * r.k;
+   if (!bet.no_more) return 0;
+   grids[0] = r.sb_grid, grids[1] = r.task_grid;
+   ZH_CHECK(c, hipMemcpyAsync(r.cnt + ZH_CNT_SBGRID, grids, 2 * sizeof(uint32_t), hipMemcpyHostToDevice, r.st));
+   return 0;
+}
+// ... behind zh_list_huge: no chain kernels — and what the side stream was given at the start of the batch (checksums, clearing the payload slots and the stream buffer),
+// otherwise joined with the chains
+static int zh_bets_enqueue_nochains(zultra_hip_ctx_t *c, const zh_run_t &r, const zh_bet_t &bet) {
+   if (!bet.no_chains) return 0;
+   ZH_CHECK(c, hipMemsetAsync(r.cnt + ZH_CNT_NOCHAINS, 1, sizeof(uint32_t), r.st));
+   ZH_CHECK(c, hipEventRecord(r.side_ev[1], r.side));
+   ZH_CHECK(c, hipStreamWaitEvent(r.st, r.side_ev[1], 0));
+   return 0;
+}
+
+// Behind the host's wait for a batch of `lanes` runs: what they listed is what the next batch bets against. True: a run is void — by the predicate its own kernels left
+// on, asked of the counters they read (h_ntasks mirrors them, the host's marks included) — and the batch runs again, every run with what these counts say it needs.
+static bool zh_bets_settle(zultra_hip_ctx_t *c, int lanes) {
+   bool again = false;
+   for (int k = 0; k < lanes; k++) {
+      const uint32_t *cnt = c->h_ntasks + (size_t)k * ZH_CNT_STRIDE;
+      zh_bet_t &b = c->bets.run[k];
+      b.seen_chains = cnt[ZH_CNT_VLONG] + cnt[ZH_CNT_LONG] + cnt[ZH_CNT_SHORT] + cnt[ZH_CNT_SEGTASKS];
+      b.seen_nsubs = cnt[ZH_CNT_NSUBS], b.seen_ntasks = cnt[ZH_CNT_TASKS];
+      again |= zh_run_is_void(cnt);
    }
-   for (int pass = 0; pass <= 3; pass++) {
-      // (a lambda: ZH_LAUNCH returns from the function it stands in)
-      auto launch_chain = [&](hipStream_t cs) -> int {
-         ZH_LAUNCH(zh_parse_chain, chain_grid, ZH_CHAIN_THREADS, cs, c->cur_data, blk, match, c->match_stride, bars, c->bar_stride, (const zh_work_t *)work, (const uint2 *)taskmap,
-                   (const uint32_t *)hugelist, cap, segtasks, (const uint2 *)segitems, vecs, c->seg_wide, c->seg_whole, cnt, (const zh_sbstate_t *)states, best, c->best_stride, hist_part, pass,
-                   cnt + ZH_CNT_CHAIN_TICKET + pass, (c->d_chain_trace && !files) ? c->d_chain_trace + 3 * (uint64_t)ZH_TRACE_SLOTS * (4 * k + pass) : (uint64_t *)NULL);
-         return 0;
-      };
-      if (!chains_idle) {
-         ZH_CHECK(c, hipEventRecord(c->side_ev[k][2 * pass], st));
-         ZH_CHECK(c, hipStreamWaitEvent(side, c->side_ev[k][2 * pass], 0));
-         if (launch_chain(side) != 0) return -1;
-         ZH_CHECK(c, hipEventRecord(c->side_ev[k][2 * pass + 1], side));
-      }
-      {
-         zh_seg_args_t sg;
-         sg.segtasks = segtasks;
-         sg.segwaves = (const uint2 *)segwaves;
-         sg.vecs = vecs;
-         sg.demote_list = hugelist + 3 * (size_t)cap;
-         sg.demote_min = c->demote_min;
-         sg.seg_wide_min = c->seg_wide;
-         sg.seg_grid = files ? 0u : seg_grid;
-         ZH_LAUNCH(zh_parse_lanes, sg.seg_grid + lane_grid, 64, st, c->cur_data, blk, match, c->match_stride, bars, c->bar_stride, (const zh_work_t *)work, (const uint2 *)taskmap, cnt,
-                   (const zh_sbstate_t *)states, best, c->best_stride, cost, hist_part, pass, cnt + ZH_CNT_TASK_TICKET + pass, (const uint2 *)taskinfo, tpw,
-                   files ? 0xFFFFFFFFu : c->num_cus * ZH_LANE_WAVES, sg, (const uint32_t *)lanelist, cap);
-      }
-      if (!chains_idle) ZH_CHECK(c, hipStreamWaitEvent(st, c->side_ev[k][2 * pass + 1], 0));
-      if (!files) ZH_CHECK(c, hipEventRecord(ev[ZH_EV_PARSE0 + 2 * pass], st));   // (timing marks)
-      ZH_LAUNCH_BOTH(zh_sb_build, sb_grid, sb_bound, st, (const zh_work_t *)work, states, (const uint32_t *)hist_part, payload, pass, cnt);
-      if (!files) ZH_CHECK(c, hipEventRecord(ev[ZH_EV_BUILD0 + 2 * pass], st));   // (timing marks)
+   c->bets.seen_runs = lanes;
+   if (again) c->bets.reruns++;
+   return again;
+}
+
+// A kernel whose item count only the device knows (sub-blocks, tasks, segment waves of a run): the <false> form over `grid_` workgroups, one item each (what data
+// usually gives; surplus workgroups leave at once), then — unless the run bets that there is nothing (no_more_) — the <true> form, ZH_MORE_GRID workgroups striding over
+// what lies beyond grid_: nearly always nothing. (bound_: what the item count cannot exceed — a grid that covers it needs no second launch: a call on a few max-blocks is
+// a matter of launches)
+#define ZH_MORE_GRID 256u
+#define ZH_LAUNCH_BOTH(kernel_, grid_, bound_, no_more_, stream_, ...)                                                                                \
+   do {                                                                                                                                               \
+      ZH_LAUNCH(kernel_<false>, (grid_), 64, stream_, __VA_ARGS__, 0u);                                                                               \
+      if ((uint64_t)(grid_) < (uint64_t)(bound_) && !(no_more_)) ZH_LAUNCH(kernel_<true>, ZH_MORE_GRID, 64, stream_, __VA_ARGS__, (uint32_t)(grid_)); \
+   } while (0)
+
+static int zh_run_mark(zultra_hip_ctx_t *c, const zh_run_t &r, int e) {   // (timing marks: not in files mode, where they would be nodes of a captured graph)
+   if (!r.files) ZH_CHECK(c, hipEventRecord(r.ev[e], r.st));
+   return 0;
+}
+
+// the run's first matchfinder kernel: behind it the next run's matchfinder may start
+static void zh_run_group(const zultra_hip_ctx_t *c, const zh_run_t &r) {
+   ZH_LAUNCH_LDS(zh_mf_group<true>, r.mf_grid, ZH_MF_THREADS, ZH_MF_GROUP_LDS, r.st, c->cur_data, r.sgs, r.sa, r.sb, r.p3, r.rn, c->sort_stride, c->run_stride, r.nsg, r.ctr + (size_t)r.nsg * 2 + 1, r.pay, c->mf_lds_cap);
+   // the bigram classes that fit no chunk of zh_mf_group, noted by it (zh_mf_group_lds.h): a kernel of their own (inputs of <= 4 KiB are one chunk: nothing is ever noted)
+   if (c->seg_W > zh_mfl_cap(c->seg_W, c->mf_lds_cap))   // (a smaller window's chunks are no smaller)
+      ZH_LAUNCH_LDS(zh_mf_group_big, r.mf_big_grid, ZH_MF_THREADS, ZH_MF_GROUP_LDS, r.st, c->cur_data, r.sgs, r.sa, r.sb, r.p3, r.rn, c->sort_stride, c->run_stride, r.nsg, r.ctr + (size_t)r.nsg * 2 + 2, r.pay);
+}
+
+// (segment descriptors carry batch-wide block indices: the rows go to d_match + block * match_stride)
+static int zh_run_frontier(zultra_hip_ctx_t *c, const zh_run_t &r) {
+   ZH_LAUNCH_LDS(zh_mf_frontier<true>, r.fr_grid, ZH_MF_THREADS, ZH_MF_FRONTIER_LDS, r.st, c->cur_data, r.sgs, r.sa, r.p3, r.rn, c->sort_stride, c->run_stride, c->d_match, c->match_stride, (uint32_t *)nullptr,
+                 c->tok_stride, r.ctr, r.nsg, r.mf_steal);
+   return zh_run_mark(c, r, ZH_EV_FRONTIER);
+}
+
+// barrier bitmap and greedy token chain of the run's max-blocks, in chunks (zh_split.h)
+static void zh_run_tokenize(const zultra_hip_ctx_t *c, const zh_run_t &r) {
+   const uint32_t *match = (const uint32_t *)r.match;   // slot 0 of a position's row = its longest match
+   ZH_LAUNCH(zh_barriers, r.nb * r.cpb, 64, r.st, r.blk, match, c->match_stride, r.bars, c->bar_stride, r.chunkmax, r.cpb, r.tok_chunk, r.best, c->best_stride);
+   if (r.cpb > 1) ZH_LAUNCH(zh_barriers_fix, (r.nb + 63) / 64, 64, r.st, r.blk, r.nb, r.bars, c->bar_stride, r.chunkmax, r.cpb, r.tok_chunk);
+   ZH_LAUNCH(zh_tokenize_spans, r.nb * r.cpb, 64, r.st, c->cur_data, r.blk, r.best, c->best_stride, r.tok_pos, r.tok_info, c->tok_stride, r.bars, c->bar_stride, r.spanstart, r.spancnt, r.cpb, r.tok_chunk);
+   ZH_LAUNCH(zh_tokens_compact, r.nb, ZH_COMPACT_THREADS, r.st, r.blk, r.tok_pos, r.tok_info, c->tok_stride, r.spanstart, r.spancnt, r.cpb, r.tok_chunk, r.ntok);
+}
+
+static int zh_run_split(zultra_hip_ctx_t *c, const zh_run_t &r) {
+   if (r.files)
+      ZH_LAUNCH(zh_nosplit, (r.nb + 255) / 256, 256, r.st, r.nb, r.ntok, r.split_tok, r.split_cnt);
+   else if (r.max_n > 131072)   // (by the run's largest max-block, not the context's limit)
+      ZH_LAUNCH(zh_split<16>, r.nb, 64 * 16, r.st, r.blk, r.tok_pos, r.tok_info, c->tok_stride, r.ntok, r.split_tok, r.split_cnt);
+   else
+      ZH_LAUNCH(zh_split<8>, r.nb, 64 * 8, r.st, r.blk, r.tok_pos, r.tok_info, c->tok_stride, r.ntok, r.split_tok, r.split_cnt);
+   return zh_run_mark(c, r, ZH_EV_SPLIT);
+}
+
+// ---- stage 3: the sub-block coder, one kernel per step over the run (zh_encode.h) -----------------------------------------------------
+static void zh_run_plan(const zultra_hip_ctx_t *c, const zh_run_t &r) {
+   if (r.files)   // one sub-block per input, the task ranges from the sizes the host was handed (zh_plan_files)
+      ZH_LAUNCH(zh_plan_files, (r.nb + ZH_PLAN_FILES_THREADS - 1) / ZH_PLAN_FILES_THREADS, ZH_PLAN_FILES_THREADS, r.st, r.blk, r.nb, r.ntok, r.task_prefix, r.sub_base, c->slot_stride, r.work, r.taskmap, r.cnt);
+   else if (r.nb > 4096u)
+      ZH_LAUNCH(zh_plan_subblocks<1024u>, 1, 1024u, r.st, r.blk, r.nb, r.tok_pos, c->tok_stride, r.ntok, r.split_tok, r.split_cnt, r.sub_base, c->slot_stride, r.work, r.taskmap, r.cnt, r.lane_acc);
+   else
+      ZH_LAUNCH(zh_plan_subblocks<256u>, 1, 256u, r.st, r.blk, r.nb, r.tok_pos, c->tok_stride, r.ntok, r.split_tok, r.split_cnt, r.sub_base, c->slot_stride, r.work, r.taskmap, r.cnt, r.lane_acc);
+}
+
+// the sub-blocks' coder states; the tasks listed for zh_parse_chain, cut into segments, bundled for zh_parse_lanes
+static int zh_run_init(zultra_hip_ctx_t *c, const zh_run_t &r, const zh_bet_t &bet) {
+   const zh_lane_order_t lane_lo = {r.lanelist, r.lane_acc, r.tpw, c->lane_order};
+   ZH_LAUNCH_BOTH(zh_sb_init, r.sb_grid, r.sb_bound, bet.no_more, r.st, r.tok_info, c->tok_stride, r.work, r.states, r.cnt);
+   ZH_LAUNCH_BOTH(zh_list_huge, r.task_grid, r.cap, bet.no_more, r.st, r.blk, r.bars, c->bar_stride, r.work, r.taskmap, (const uint32_t *)r.match, c->match_stride, r.hugelist, r.cap, r.segtasks, r.segitems, r.segwaves,
+                  r.seg_min, (uint32_t)ZH_CUT_LEN, r.cnt, r.taskinfo, (uint32_t)ZH_COOP_MIN, r.coop_small, r.list_cus, lane_lo);
+   return zh_run_mark(c, r, ZH_EV_INIT);
+}
+
+// parse pass `pass` of four: the chains on the side stream (fork, zh_parse_chain, join) unless the run bets that it has none, the rest in zh_parse_lanes; then the sub-blocks' codes
+static int zh_run_pass(zultra_hip_ctx_t *c, const zh_run_t &r, const zh_bet_t &bet, int pass) {
+   if (!bet.no_chains) {
+      ZH_CHECK(c, hipEventRecord(r.side_ev[2 * pass], r.st));
+      ZH_CHECK(c, hipStreamWaitEvent(r.side, r.side_ev[2 * pass], 0));
+      ZH_LAUNCH(zh_parse_chain, r.chain_grid, ZH_CHAIN_THREADS, r.side, c->cur_data, r.blk, r.match, c->match_stride, r.bars, c->bar_stride, r.work, r.taskmap, r.hugelist, r.cap, r.segtasks, r.segitems, r.vecs,
+                c->seg_wide, c->seg_whole, r.cnt, r.states, r.best, c->best_stride, r.hist_part, pass, r.cnt + ZH_CNT_CHAIN_TICKET + pass,
+                r.chain_trace ? r.chain_trace + 3 * (uint64_t)ZH_TRACE_SLOTS * pass : (uint64_t *)NULL);
+      ZH_CHECK(c, hipEventRecord(r.side_ev[2 * pass + 1], r.side));
    }
-   ZH_LAUNCH_BOTH(zh_post_tasks, task_grid, cap, st, c->cur_data, blk, bars, c->bar_stride, (const zh_work_t *)work, (const uint2 *)taskmap, (const uint32_t *)cnt, (const zh_sbstate_t *)states, best,
-             c->best_stride, task_bits, (const uint2 *)taskinfo);
-   if (!files) ZH_CHECK(c, hipEventRecord(ev[ZH_EV_POST], st));   // (timing marks)
-   ZH_LAUNCH_BOTH(zh_emit_tasks, task_grid, cap, st, c->cur_data, blk, bars, c->bar_stride, (const zh_work_t *)work, (const uint2 *)taskmap, (const uint32_t *)cnt, (const zh_sbstate_t *)states,
-             (const uint32_t *)best, c->best_stride, (const uint32_t *)task_bits, payload, c->d_results + s0, (const uint2 *)taskinfo);
-   if (!files) ZH_CHECK(c, hipEventRecord(ev[ZH_EV_EMIT], st));   // (timing marks)
-   // per-max-block CRC-32 (linear part) and Adler-32 for the framing's footer (a batch of max-blocks computes them next to its matchfinder: zultra_hip_compress_blocks)
-   if (files) {
-      // (several inputs to a workgroup: zh_crc32_small)
-      uint32_t spg = 1;
-      while (spg < (c->max_block + ZH_CRC_SLICE - 1) / ZH_CRC_SLICE) spg <<= 1;
-      if (spg <= ZH_CRC_THREADS / 2)
-         ZH_LAUNCH(zh_crc32_small, (nb + ZH_CRC_THREADS / spg - 1) / (ZH_CRC_THREADS / spg), ZH_CRC_THREADS, st, c->cur_data, blk, nb, (const uint32_t *)c->d_crc_tables, c->d_crc + b0, c->d_adler + 2 * (size_t)b0, spg);
-      else
-         ZH_LAUNCH(zh_crc32_blocks, nb, ZH_CRC_THREADS, st, c->cur_data, blk, (const uint32_t *)c->d_crc_tables, c->d_crc + b0, c->d_adler + 2 * (size_t)b0);
-   }
+   const zh_seg_args_t sg = {r.segtasks, r.segwaves, r.vecs, r.hugelist + 3 * (size_t)r.cap, c->demote_min, c->seg_wide, r.seg_grid};   // (demote_list: the run's fourth chain list)
+   ZH_LAUNCH(zh_parse_lanes, sg.seg_grid + r.lane_grid, 64, r.st, c->cur_data, r.blk, r.match, c->match_stride, r.bars, c->bar_stride, r.work, r.taskmap, r.cnt, r.states, r.best, c->best_stride, r.cost,
+             r.hist_part, pass, r.cnt + ZH_CNT_TASK_TICKET + pass, r.taskinfo, r.tpw, r.lane_waves, sg, r.lanelist, r.cap);
+   if (!bet.no_chains) ZH_CHECK(c, hipStreamWaitEvent(r.st, r.side_ev[2 * pass + 1], 0));
+   if (zh_run_mark(c, r, ZH_EV_PARSE0 + 2 * pass) != 0) return -1;
+   ZH_LAUNCH_BOTH(zh_sb_build, r.sb_grid, r.sb_bound, bet.no_more, r.st, r.work, r.states, r.hist_part, r.payload, pass, r.cnt);
+   return zh_run_mark(c, r, ZH_EV_BUILD0 + 2 * pass);
+}
+
+// literals for what the last pass left short and the tasks' bit counts; then the tokens into the payload slots, and the descriptors
+static int zh_run_post_emit(zultra_hip_ctx_t *c, const zh_run_t &r, const zh_bet_t &bet) {
+   ZH_LAUNCH_BOTH(zh_post_tasks, r.task_grid, r.cap, bet.no_more, r.st, c->cur_data, r.blk, r.bars, c->bar_stride, r.work, r.taskmap, r.cnt, r.states, r.best, c->best_stride, r.task_bits, r.taskinfo);
+   if (zh_run_mark(c, r, ZH_EV_POST) != 0) return -1;
+   ZH_LAUNCH_BOTH(zh_emit_tasks, r.task_grid, r.cap, bet.no_more, r.st, c->cur_data, r.blk, r.bars, c->bar_stride, r.work, r.taskmap, r.cnt, r.states, r.best, c->best_stride, r.task_bits, r.payload, r.results, r.taskinfo);
+   return zh_run_mark(c, r, ZH_EV_EMIT);
+}
+
+// files mode: per-input CRC-32 (linear part) and Adler-32 for the framing's footer, several inputs to a workgroup where they are small (zh_crc32_small). (A batch of max-blocks
+// computes them next to its matchfinder: zh_enqueue_batch_run.)
+static void zh_run_checksums(const zultra_hip_ctx_t *c, const zh_run_t &r) {
+   uint32_t spg = 1;
+   while (spg < (c->max_block + ZH_CRC_SLICE - 1) / ZH_CRC_SLICE) spg <<= 1;
+   if (spg <= ZH_CRC_THREADS / 2)
+      ZH_LAUNCH(zh_crc32_small, (r.nb + ZH_CRC_THREADS / spg - 1) / (ZH_CRC_THREADS / spg), ZH_CRC_THREADS, r.st, c->cur_data, r.blk, r.nb, c->d_crc_tables, r.crc, r.adler, spg);
+   else
+      ZH_LAUNCH(zh_crc32_blocks, r.nb, ZH_CRC_THREADS, r.st, c->cur_data, r.blk, c->d_crc_tables, r.crc, r.adler);
+}
+
+// The kernel sequence of one run of a batch, with NO HOST DECISION in it: everything the splitter decides — how many sub-blocks, hence how many tasks, chains, segments —
+// stays on the device: zh_plan_subblocks sums it up into the run's counters, every later kernel takes its bounds from there, and the grids are bounded grids that stride
+// over what there is (rounds 1-4 read the counts back twice per run, in the middle of the pipeline: 0.8-2.2 ms each on the 100 MB step, profiles/r04_timeline_c2.txt).
+// part: 0 the whole run; 1 only up to the end of its first matchfinder kernel (where the next run's matchfinder may start), 2 only what follows — the two
+// halves of a files-mode run captured as graphs of their own (zh_run_files).
+static int zh_enqueue_run(zultra_hip_ctx_t *c, const zh_run_t &r, int part) {
+   const zh_bet_t &bet = zh_bets_place(c, r);
+   if (zh_bets_enqueue_grids(c, r, bet) != 0) return -1;
+   if (part != 2) zh_run_group(c, r);
+   if (part == 1) return 0;
+   if (part == 0) ZH_CHECK(c, hipEventRecord(r.ev[ZH_EV_GROUP], r.st));   // the next run's matchfinder starts here (part 2: the caller records it between the two graphs)
+   if (zh_run_frontier(c, r) != 0) return -1;
+   zh_run_tokenize(c, r);
+   if (zh_run_split(c, r) != 0) return -1;
+   zh_run_plan(c, r);
+   if (zh_run_init(c, r, bet) != 0 || zh_bets_enqueue_nochains(c, r, bet) != 0) return -1;
+   for (int pass = 0; pass <= 3; pass++)
+      if (zh_run_pass(c, r, bet, pass) != 0) return -1;
+   if (zh_run_post_emit(c, r, bet) != 0) return -1;
+   if (r.files) zh_run_checksums(c, r);
    return 0;
 }
 
@@ -1293,10 +1342,10 @@ static int zh_enqueue_files_tail(zultra_hip_ctx_t *c, uint32_t nblocks, hipStrea
    return 0;
 }
 
-// files mode, run k (blocks [b0, b1)) on stream st: part 0 the whole run, 1 / 2 its halves (zh_enqueue_run)
-static int zh_enqueue_files_run(zultra_hip_ctx_t *c, uint32_t nblocks, int k, hipStream_t st, int part) {
+// files mode, run k (blocks [b0, b1)) on its stream: part 0 the whole run, 1 / 2 its halves (zh_enqueue_run)
+static int zh_enqueue_files_run(zultra_hip_ctx_t *c, uint32_t nblocks, int k, int part) {
    const uint32_t b0 = zh_files_run_lo(c, nblocks, k), b1 = zh_files_run_lo(c, nblocks, k + 1);
-   return zh_enqueue_run(c, k, b0, b1 - b0, (uint64_t)(b1 - b0) * c->max_block, c->max_block, b0, b1 - b0, st, c->side_stream[k], part);
+   return zh_enqueue_run(c, zh_run_t(c, k, b0, b1 - b0, (uint64_t)(b1 - b0) * c->max_block, c->max_block, b0, b1 - b0), part);   // (an input is one segment)
 }
 
 // The runs of a files batch: what they need cleared, on the stream they fork from; every run's kernels — or, G, its two captured graphs — on its own
@@ -1320,7 +1369,7 @@ static int zh_enqueue_files(zultra_hip_ctx_t *c, uint32_t nblocks, hipStream_t s
          ZH_CHECK(c, hipGraphLaunch(G->exec[2 * k + 1], st));
 #endif
       }
-      else if (zh_enqueue_files_run(c, nblocks, k, st, 0) != 0)
+      else if (zh_enqueue_files_run(c, nblocks, k, 0) != 0)
          return -1;
       if (k) ZH_CHECK(c, hipEventRecord(c->lane_ev[k][ZH_EV_JOIN], st));
    }
@@ -1385,7 +1434,7 @@ static int zh_run_files(zultra_hip_ctx_t *c, uint32_t nblocks) {
             hipStream_t sk = c->lane_stream[k];
             ZH_CHECK(c, hipStreamSynchronize(sk));
             for (int part = 1; part <= 2; part++)
-               if (zh_graph_capture(c, G, 2 * k + part - 1, sk, [&] { return zh_enqueue_files_run(c, nblocks, k, sk, part); }) != 0) return -1;
+               if (zh_graph_capture(c, G, 2 * k + part - 1, sk, [&] { return zh_enqueue_files_run(c, nblocks, k, part); }) != 0) return -1;
          }
       }
       zh_graph_use(c, G, nblocks);
@@ -1463,10 +1512,6 @@ static void zh_plan_runs(zultra_hip_ctx_t *c, const zultra_hip_block_t *blocks, 
    for (int k = 1; k < lanes; k++)
       run_b0[k] = k == 1 ? share : k == lanes - 1 ? nblocks - share : share + (uint32_t)((uint64_t)(nblocks - 2u * share) * (uint64_t)(k - 1) / (uint64_t)(lanes - 2));
    run_b0[lanes] = nblocks;
-   for (int k = 0; k < lanes; k++) c->last_run_b0[k] = run_b0[k];
-   // (a batch with runs enqueued without chain kernels may have to be run again — as may one with a run enqueued without its <true> overflow forms: zh_read_back)
-   for (int k = 0; k < ZH_MAX_RUNS; k++)
-      c->run_nochains[k] = !c->files_mode && c->chain_skip && k < lanes && c->chain_seen_runs == lanes && c->chain_seen[k] == 0;
 }
 
 // The batch's descriptors, segment list and (data_on_device == 0) input on the device, on run 0's stream. data_on_device == 2: pageable host memory, and the
@@ -1519,20 +1564,16 @@ static size_t zh_stream_clear_bytes(const zultra_hip_ctx_t *c, uint64_t framing_
 // Run k of a batch, start to finish — nothing in it waits for the host: staggered behind the run before it, its input staged, what it needs cleared,
 // the checksums on its side stream, its kernels (zh_enqueue_run), the copies of its checksums
 static int zh_enqueue_batch_run(zultra_hip_ctx_t *c, int k, const uint8_t *data, const zultra_hip_block_t *blocks, uint32_t b0, uint32_t b1, uint8_t *stage, bool stitch_now) {
-   hipStream_t st = c->lane_stream[k], side = c->side_stream[k];
-   hipEvent_t *ev = c->lane_ev[k];
-   const uint32_t nb = b1 - b0;
+   uint64_t total_n = 0;
+   uint32_t max_n = 0;
+   for (uint32_t b = b0; b < b1; b++) total_n += blocks[b].n, max_n = max(max_n, blocks[b].n);
+   const zh_run_t r(c, k, b0, b1 - b0, total_n, max_n, c->seg_base[b0], c->seg_base[b1] - c->seg_base[b0]);   // (with this run's matchfinder segments)
+   hipStream_t st = r.st, side = r.side;
    if (k) {
       ZH_CHECK(c, hipStreamWaitEvent(st, c->ev_input, 0));
       // stagger the runs by one stage: this run's wide matchfinder kernels start when the previous run reaches its
       // narrow ones (token chain, splitter), so narrow and wide kernels of different runs share the chip
       ZH_CHECK(c, hipStreamWaitEvent(st, c->lane_ev[k - 1][ZH_EV_GROUP], 0));
-   }
-   uint64_t total_n = 0;
-   uint32_t max_n = 0;
-   for (uint32_t b = b0; b < b1; b++) {
-      total_n += blocks[b].n;
-      max_n = max(max_n, blocks[b].n);
    }
    if (stage) {
       // this run's windows: from the first block's history to the last block's end (the 32 KiB in front of the run go up twice, with the run before it:
@@ -1545,30 +1586,27 @@ static int zh_enqueue_batch_run(zultra_hip_ctx_t *c, int k, const uint8_t *data,
       zh_threaded_copy(stage + lo, data + lo, (size_t)(hi - lo), 8u << 20);   // (a run of tens of MB: the host copy is split over a few threads)
       ZH_CHECK(c, hipMemcpyAsync(c->d_data + lo, stage + lo, (size_t)(hi - lo), hipMemcpyHostToDevice, st));
    }
-   ZH_CHECK(c, hipEventRecord(ev[ZH_EV_INPUT], st));
-   const uint32_t sg0 = c->seg_base[b0], nsg = c->seg_base[b1] - sg0;   // this run's matchfinder segments
-   ZH_CHECK(c, hipMemsetAsync(c->d_chunk_ctr + (size_t)sg0 * 2 + 3 * (size_t)k, 0, ((size_t)nsg * 2 + 3) * sizeof(uint32_t), st));
-   ZH_CHECK(c, hipMemsetAsync(c->d_ntasks + (size_t)k * ZH_CNT_STRIDE, 0, ZH_CNT_STRIDE * sizeof(uint32_t), st));   // the run's counters and tickets
+   ZH_CHECK(c, hipEventRecord(r.ev[ZH_EV_INPUT], st));
+   ZH_CHECK(c, hipMemsetAsync(r.ctr, 0, ((size_t)r.nsg * 2 + 3) * sizeof(uint32_t), st));
+   ZH_CHECK(c, hipMemsetAsync(r.cnt, 0, ZH_CNT_STRIDE * sizeof(uint32_t), st));   // the run's counters and tickets
    // per-max-block CRC-32 (linear part) and Adler-32 for the framing's footer need the input only: on the run's side stream, next to its matchfinder
    // (behind the run's last kernel they were the tail of the batch; behind its frontier, round 4, on the path to its first parse pass). The side
    // stream's later kernels — the chains of every pass — are joined by the run's stream: so is this one.
-   ZH_CHECK(c, hipStreamWaitEvent(side, ev[ZH_EV_INPUT], 0));
-   ZH_LAUNCH(zh_crc32_blocks, nb, ZH_CRC_THREADS, side, c->cur_data, (const zh_block_t *)(c->d_blocks + b0), (const uint32_t *)c->d_crc_tables, c->d_crc + b0, c->d_adler + 2 * (size_t)b0);
+   ZH_CHECK(c, hipStreamWaitEvent(side, r.ev[ZH_EV_INPUT], 0));
+   ZH_LAUNCH(zh_crc32_blocks, r.nb, ZH_CRC_THREADS, side, c->cur_data, r.blk, c->d_crc_tables, r.crc, r.adler);
    // token bits are ORed into the payload slots: cleared there too, long before stage 3 needs them
-   ZH_CHECK(c, hipMemsetAsync(c->d_payload + (uint64_t)b0 * c->slot_stride, 0, (size_t)nb * c->slot_stride, side));
+   ZH_CHECK(c, hipMemsetAsync(r.payload, 0, (size_t)r.nb * c->slot_stride, side));
    // ... and so is the stream buffer of a stitch that goes out with the batch (zh_enqueue_stitch): nobody reads it between two batches' stitches
    if (stitch_now && k == 0) ZH_CHECK(c, hipMemsetAsync(c->d_stream, 0, zh_stream_clear_bytes(c), side));
-   if (zh_enqueue_run(c, k, b0, nb, total_n, max_n, sg0, nsg, st, side, 0) != 0) return -1;
-   ZH_CHECK(c, hipMemcpyAsync(c->h_crc + b0, c->d_crc + b0, nb * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-   ZH_CHECK(c, hipMemcpyAsync(c->h_adler + 2 * (size_t)b0, c->d_adler + 2 * (size_t)b0, 2 * nb * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-   ZH_CHECK(c, hipEventRecord(ev[ZH_EV_READBACK], st));
+   if (zh_enqueue_run(c, r, 0) != 0) return -1;
+   ZH_CHECK(c, hipMemcpyAsync(c->h_crc + b0, r.crc, r.nb * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+   ZH_CHECK(c, hipMemcpyAsync(c->h_adler + 2 * (size_t)b0, r.adler, 2 * r.nb * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+   ZH_CHECK(c, hipEventRecord(r.ev[ZH_EV_READBACK], st));
    return 0;
 }
 
 // Behind the last run: the descriptors in stream order and batch coordinates, the counts, the stitch that goes out with the batch — then the host's one
-// wait. *again: a run enqueued without chain kernels listed chains after all, or one enqueued without its <true> overflow forms outgrew its grids
-// (zh_run_is_void: its kernels left at once) — the batch has to run again, every run with what the counts just taken say it needs: one batch's time,
-// once, where the stream's content changes.
+// wait. *again: a run lost a bet (zh_bets_settle) and the batch has to run again: one batch's time, once, where the stream's content changes.
 static int zh_read_back(zultra_hip_ctx_t *c, const uint32_t *run_b0, int lanes, bool stitch_now, bool *again) {
    hipStream_t st0 = c->lane_stream[0];
    const uint32_t nblocks = c->nblocks;
@@ -1585,20 +1623,8 @@ static int zh_read_back(zultra_hip_ctx_t *c, const uint32_t *run_b0, int lanes, 
    }
    ZH_CHECK(c, hipStreamSynchronize(st0));
    ZH_CHECK(c, hipGetLastError());
-   *again = false;
-   for (int k = 0; k < lanes; k++) {
-      const uint32_t *cnt = c->h_ntasks + (size_t)k * ZH_CNT_STRIDE;
-      c->chain_seen[k] = cnt[ZH_CNT_VLONG] + cnt[ZH_CNT_LONG] + cnt[ZH_CNT_SHORT] + cnt[ZH_CNT_SEGTASKS];
-      c->seen_nsubs[k] = cnt[ZH_CNT_NSUBS];
-      c->seen_ntasks[k] = cnt[ZH_CNT_TASKS];
-      const bool outgrown = c->run_nomore[k] && (c->seen_nsubs[k] > c->run_grids[k][0] || c->seen_ntasks[k] > c->run_grids[k][1]);
-      if ((c->run_nochains[k] && c->chain_seen[k] != 0) || outgrown) *again = true;
-   }
-   c->chain_seen_runs = lanes;
-   if (*again) {
-      c->chain_redone++;
-      return 0;
-   }
+   *again = zh_bets_settle(c, lanes);
+   if (*again) return 0;
    const uint32_t nsubs = c->h_nsubs[0];
    if (nsubs < nblocks || (uint64_t)nsubs > (uint64_t)nblocks * c->max_subs) {
       snprintf(c->err, sizeof(c->err), "the device reports %u sub-blocks for %u max-blocks", nsubs, nblocks);
@@ -2147,7 +2173,7 @@ extern "C" int zultra_hip_chain_trace(zultra_hip_ctx_t *c, uint64_t *out, uint32
 extern "C" int zultra_hip_cut_tasks(zultra_hip_ctx_t *c, uint32_t run, uint32_t *out, uint32_t cap) {
    if (!c || (int)run >= c->last_runs || c->files_mode) return -1;
    const uint32_t n = min(cap, c->h_ntasks[(size_t)run * ZH_CNT_STRIDE + ZH_CNT_SEGTASKS]);
-   if (out && n) ZH_CHECK(c, hipMemcpy(out, c->d_segtasks + (uint64_t)c->last_run_b0[run] * c->seg_tasks_per_block, (size_t)n * sizeof(uint4), hipMemcpyDeviceToHost));
+   if (out && n) ZH_CHECK(c, hipMemcpy(out, c->d_segtasks + (uint64_t)c->bets.run[run].b0 * c->seg_tasks_per_block, (size_t)n * sizeof(uint4), hipMemcpyDeviceToHost));
    return (int)n;
 }
 
@@ -2162,7 +2188,7 @@ extern "C" void zultra_hip_last_stats(const zultra_hip_ctx_t *c, zultra_hip_stat
    memset(out, 0, sizeof(*out));
    out->blocks = c->nblocks;
    out->subblocks = c->nsubs;
-   out->batches_rerun = c->chain_redone;
+   out->batches_rerun = c->bets.reruns;
    for (int k = 0; k < c->last_runs && k < ZH_MAX_RUNS; k++) {   // (a run's counters are cleared when it is launched: only the last batch's runs count)
       const uint32_t *cnt = c->h_ntasks + (size_t)k * ZH_CNT_STRIDE;
       out->tasks += cnt[ZH_CNT_TASKS];

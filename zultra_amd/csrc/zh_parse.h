@@ -143,7 +143,7 @@ static_assert(ZH_CNT_TASKS == 0, "zh_post_tasks / zh_emit_tasks take the run's c
 // grid, yet each is a launch whose workgroups must find room on a full chip before they can leave — zh_sb_init<true> (99 registers, 8 KB of LDS) 0.4 ms on average and up to
 // 1.7 ms, on every run's path to its first parse pass (profiles/r06_timeline_c2.txt). Where the context's last batch stayed inside this batch's grids the host does not launch
 // them and leaves the grids in the counters; a run that outgrows them is void like one that lists chains without chain kernels.
-__device__ __forceinline__ bool zh_run_is_void(const uint32_t *cnt) {
+__host__ __device__ __forceinline__ bool zh_run_is_void(const uint32_t *cnt) {   // (the host asks it of the counters it reads back: zh_device.hip, zh_bets_settle)
    const bool chains = cnt[ZH_CNT_NOCHAINS] != 0 && (cnt[ZH_CNT_VLONG] | cnt[ZH_CNT_LONG] | cnt[ZH_CNT_SHORT] | cnt[ZH_CNT_SEGTASKS]) != 0u;
    const bool outgrown = cnt[ZH_CNT_SBGRID] != 0 && (cnt[ZH_CNT_NSUBS] > cnt[ZH_CNT_SBGRID] || cnt[ZH_CNT_TASKS] > cnt[ZH_CNT_TASKGRID]);
    return chains || outgrown;

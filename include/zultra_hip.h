@@ -128,8 +128,17 @@ typedef struct zultra_hip_stats_s {
    uint32_t cut_demoted;               /* cut tasks that had several failed cuts in one pass and were parsed as one chain in the passes left */
    uint32_t runs_without_chain_kernels;   /* runs of the last batch enqueued without zh_parse_chain: their counterparts in the context's batch before it listed no chains (round 6) */
    uint32_t batches_rerun;                /* batches of this context run a second time because such a run listed chains after all (since the context was created) */
+   uint32_t runs_fitted;                  /* diagnostics, decides nothing: at its creation a context that picks the run count itself lets the streams of its runs (three at most) spin
+                                             side by side once; the largest number of runs, from the first, whose streams all had hardware queues of their own (1: not even two). A context
+                                             that does not look (files, ZULTRA_HIP_STREAMS set, a largest batch of one run) reports the runs it created streams for, three at most */
+   uint32_t stream_collisions;            /* ... and the pairs of those streams that shared a queue at that look (0: every run of a batch below 256 MiB can overlap the others) */
 } zultra_hip_stats_t;
 void zultra_hip_last_stats(const zultra_hip_ctx_t *ctx, zultra_hip_stats_t *out);
+
+/* The number of staggered runs a batch of nblocks max-blocks and batch_bytes input bytes is cut into (pure: no context, no device). streams_setting: ZULTRA_HIP_STREAMS
+ * (0: not set). A positive setting asks for that many runs, otherwise three, four from 256 MiB on; either way a run has at least four max-blocks and 4 MiB, and a batch
+ * at least one run. */
+uint32_t zultra_hip_runs_for(uint64_t batch_bytes, uint32_t nblocks, int streams_setting);
 
 /* Diagnostics: the matchfinder's chunk size in this context for a segment window of window_size bytes (history + block + look-ahead) — a bigram class of
  * that many positions or more is refined through device memory by a kernel of its own, from a note —, and in *max_notes (may be NULL) how many such

@@ -30,7 +30,7 @@ pin = torch.empty(size + (1 << 20), dtype=torch.uint8, pin_memory=True).numpy()
 torch.cuda.synchronize()
 ctxs = []
 for so in libs:
-    L = Lib(so, allow_missing=("zultra_hip_stitch_with_batch",))
+    L = Lib(so, allow_missing=("zultra_hip_stitch_with_batch", "zultra_hip_runs_for"))
     ctxs.append((so, L, L.context(bs, nb)))
 
 
@@ -59,5 +59,6 @@ for r in range(rounds):
         res[so].append((time.perf_counter() - t0) / 5 * 1e3)
         dev[so].append(ctx.timing()["total_ms"])
 for so, L, ctx in ctxs:
-    print("%-40s step ms: min %.2f med %.2f | device pipeline (last of each round) min %.2f med %.2f | %d bytes out" % (
-        os.path.basename(so), min(res[so]), float(np.median(res[so])), min(dev[so]), float(np.median(dev[so])), n))
+    st = ctx.stats()   # (runs_fitted, stream_collisions: 0 from a build that does not report them)
+    print("%-40s step ms: min %.2f med %.2f | device pipeline (last of each round) min %.2f med %.2f | %d bytes out | runs %d, runs_fitted %d, stream_collisions %d" % (
+        os.path.basename(so), min(res[so]), float(np.median(res[so])), min(dev[so]), float(np.median(dev[so])), n, st["runs"], st["runs_fitted"], st["stream_collisions"]))

@@ -58,7 +58,7 @@ class Stats(C.Structure):
     _fields_ = [("positions", C.c_uint64), ("huge_positions", C.c_uint64), ("blocks", C.c_uint32), ("subblocks", C.c_uint32),
                 ("tasks", C.c_uint32), ("huge_tasks", C.c_uint32), ("cut_tasks", C.c_uint32), ("cut_segments", C.c_uint32),
                 ("cut_redone", C.c_uint32), ("runs", C.c_uint32), ("settled_passes", C.c_uint32), ("settled_kib", C.c_uint32), ("cut_demoted", C.c_uint32),
-                ("runs_without_chain_kernels", C.c_uint32), ("batches_rerun", C.c_uint32)]
+                ("runs_without_chain_kernels", C.c_uint32), ("batches_rerun", C.c_uint32), ("runs_fitted", C.c_uint32), ("stream_collisions", C.c_uint32)]
 
 
 class BitState(C.Structure):
@@ -112,7 +112,7 @@ EXPORTS = [
     "zultra_hip_stitch", "zultra_hip_stitch_finish",
     "zultra_hip_stitch_device", "zultra_hip_stitch_phase_table", "zultra_hip_stream_device", "zultra_hip_stream_read", "zultra_hip_block_crc32", "zultra_crc32_append", "zultra_crc32_append_many",
     "zultra_hip_create_files", "zultra_hip_compress_files", "zultra_hip_stitch_files", "zultra_hip_staging",
-    "zultra_hip_block_adler32", "zultra_adler32_append", "zultra_hip_copy_bandwidth", "zultra_hip_last_stats", "zultra_hip_mf_chunk",
+    "zultra_hip_block_adler32", "zultra_adler32_append", "zultra_hip_copy_bandwidth", "zultra_hip_last_stats", "zultra_hip_runs_for", "zultra_hip_mf_chunk",
     "zultra_hip_ctx_info", "zultra_hip_context_bytes", "zultra_hip_context_bytes_on", "zultra_release_cached_contexts", "zultra_hip_chain_trace", "zultra_hip_cut_tasks", "zultra_hip_stitch_with_batch",
     # verification
     "zultra_set_verify", "zultra_verified_bytes", "zultra_hip_verify_device", "zultra_hip_last_verify_ms", "zultra_hip_stream_write",
@@ -196,6 +196,12 @@ class Lib:
     def traffic_probe(self, nbytes):
         self.L.zultra_hip_traffic_probe.argtypes = [C.c_size_t]
         return self.L.zultra_hip_traffic_probe(nbytes)
+
+    def runs_for(self, batch_bytes, nblocks, streams_setting=0):
+        """Staggered runs a batch is cut into (zultra_hip_runs_for: pure, no device)."""
+        self.L.zultra_hip_runs_for.argtypes = [C.c_uint64, C.c_uint32, C.c_int]
+        self.L.zultra_hip_runs_for.restype = C.c_uint32
+        return int(self.L.zultra_hip_runs_for(batch_bytes, nblocks, streams_setting))
 
     def copy_bandwidth(self, nbytes=1 << 30, iters=5):
         """Measured GB/s (read + written) of a 16 B/lane streaming copy: the roofline's second denominator."""

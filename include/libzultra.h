@@ -205,6 +205,37 @@ size_t zultra_memory_compress_zip(const unsigned char *pIn, size_t nIn, const si
  * or nCentralOff or nCentralSize at or above 0xFFFFFFFF. */
 size_t zultra_zip_end_records(unsigned char *pOut, size_t nMaxOut, unsigned long long nEntries, unsigned long long nCentralOff, unsigned long long nCentralSize);
 
+/* The reading counterpart: where an archive of nArchiveSize bytes keeps its central directory, from its last nTail bytes (65535 + 22 + 20 + 56 of them hold
+ * every end record there can be; fewer are fine where the archive is shorter). Pure host code. The end record is the LAST position p with 50 4b 05 06 whose
+ * comment length reaches the archive's end exactly (a signature inside the archive comment is passed over). Where the 20 bytes in front of it are a ZIP64 locator
+ * (50 4b 06 07, disk 0, one disk in all) the values come from the ZIP64 end record (50 4b 06 06) it points to — looked for at the offset the locator names and,
+ * for an archive behind a prefix, directly in front of the locator —, which must lie inside the tail. nPrefix = the position of the end record (the ZIP64 one
+ * where there is one) - nCentralSize - nCentralOff: the bytes in front of the archive proper, a self-extractor's stub, which Python's zipfile reads too; the
+ * directory starts at nPrefix + nCentralOff and a local header at nPrefix + its offset. Returns 0, or -1: no end record, a disk number other than 0, a size or
+ * an offset of 0xFFFFFFFF without a locator, a locator without its record, a negative prefix. An entry count of 0xFFFF without a locator is 65535 entries: what
+ * zultra_zip_end_records and zipfile write for exactly that many. */
+typedef struct zultra_zip_end_s {
+   unsigned long long nEntries, nCentralOff, nCentralSize, nPrefix;
+   int nZip64;
+} zultra_zip_end_t;
+int zultra_zip_find_end(const unsigned char *pTail, size_t nTail, unsigned long long nArchiveSize, zultra_zip_end_t *pEnd);
+
+/* unzip(1) in memory: pIn is a whole ZIP archive — this library's, zip(1)'s, Python's zipfile's —, entry i is decoded to pOut + pInfo[i].nOutOff, the entries
+ * back to back in the central directory's order. zultra_zip_find_end, one upload, then the directory index, the local headers, inflate / copy and the CRC-32
+ * checks on the device (include/zultra_hip.h: zultra_hip_unzip, with its reasons as nStatus). pInfo[i].nNameAt: where the entry's name (nNameLen bytes, as
+ * stored) lies in pIn. pOut == NULL with nMaxOut == 0 LISTS only: the directory index and the infos, returning the size the output needs. *pnEntries (may be
+ * NULL) = the directory's entries. Returns the bytes written, or (size_t)-1: no end records or a directory that does not end where they say, any entry with a
+ * reason, a deflated entry whose stream does not fill its comp_size, an entry count that differs from the end record's, more entries than nMaxInfo, more output
+ * than nMaxOut (known before a byte is decoded), no device. pInfo is filled as far as it is known. Stored and deflated entries only; no ZIP64 fields per entry,
+ * no encryption, one disk. */
+typedef struct zultra_zip_info_s {
+   unsigned long long nNameAt;
+   unsigned int nNameLen, nMethod, nFlags, nCrc32, nCompSize, nSize;
+   unsigned long long nOutOff;
+   unsigned int nStatus;   /* 0, or the reason of zultra_hip_unzip */
+} zultra_zip_info_t;
+size_t zultra_memory_decompress_zip(const unsigned char *pIn, size_t nIn, unsigned char *pOut, size_t nMaxOut, zultra_zip_info_t *pInfo, size_t nMaxInfo, size_t *pnEntries /* may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -421,6 +421,57 @@ int zultra_hip_zip_read(zultra_hip_ctx_t *ctx, void *out, size_t offset, size_t 
 /* A measurement hook (tools/zip_time.py): device time of the last zultra_hip_zip_members' launches, milliseconds. */
 void zultra_hip_last_zip_ms(const zultra_hip_ctx_t *ctx, float *ms /* [3]: scan, records, copy */);
 
+/*
+ * A ZIP archive READ: the central directory indexed on the device, then every entry checked against its local header, inflated or copied,
+ * and its CRC-32 taken and compared there. The caller names the directory — src[central_at .. central_at + central_size), from zultra_zip_find_end
+ * (libzultra.h) or from zultra_hip_zip_device —, the device finds the records: one starts at p when 46 bytes lie in front of the directory's end, src[p..p+4) =
+ * 50 4b 01 02 and, with n, m, k the le16 values at p + 28, p + 30, p + 32, p + 46 + n + m + k does not pass the directory's end; the next is behind it. The
+ * chain from central_at is walked in tiles of ZULTRA_HIP_INDEX_TILE bytes (default here: 16 KiB) as zultra_hip_index_members walks a gzip file, and equals the serial walk bit for bit.
+ *   dirent         : central_at (the record's position in src; the name lies at central_at + 46), local_off as the record names it, dst_off = the 64-bit
+ *                    sum of the `size` fields of the records in front, whatever becomes of those entries, and the record's fields
+ *   stop           : why the chain ended at central_at + dir_used — 0 the directory's end; 1 fewer than 46 bytes left, or no signature; 2 a record that runs
+ *                    past the end; and 4 = more entries than `cap`, or (zultra_hip_unzip) more output than dst_size: nothing was written, entries / out_size say
+ *                    how much room the archive needs. out_size is known before a byte is inflated: an archive cannot make the call write more than dst_size
+ *   tiles, tiles_rewalked : as for zultra_hip_index_members
+ * zultra_hip_zip_index: the index alone. dirents (host, cap) may be NULL with cap 0 to learn the counts. Returns 0; -1 for bad arguments (src NULL, src_size 0,
+ * a directory outside src, a bad device, dirents NULL with cap > 0), HIP errors and stop 4 (res filled, nothing written). kernel_ms: the index kernels.
+ * zultra_hip_unzip: entry i goes to dst + dirent[i].dst_off. local_delta: what is added to a record's local_off to find the local header in src — the size of
+ * whatever stands in front of the archive (a self-extractor's stub) for a file, -base_off for a local part standing in zultra_hip_zip_device. An entry's reason,
+ * in this order:
+ *   17 decided from the dirent alone: a method other than 0 (stored) and 8 (deflate); flag bit 0 or 6 (encrypted) or 5 (patched); comp_size, size or local_off
+ *      0xFFFFFFFF (the ZIP64 extra field is not read)
+ *   14 the local header: its 30 bytes do not lie in src, no 50 4b 03 04, its name (length or bytes) or its method differ from the central record's, the data
+ *      runs past src, a stored entry with comp_size != size. The local header's sizes and CRC, a data descriptor (flag bit 3) and a ZIP64 extra field there are
+ *      not looked at: the central record is the authority
+ *   1..13 the inflate kernel's own; its room is `size`, so more output than that is 13
+ *   16 out_size != size, then 15 the CRC-32 of the output differs from the record's (16 first, unlike gzip: a short output fails both, and 16 says more)
+ * results[i]: blocks, out_size as the inflate kernel left them (a stored entry: 0 and size); src_used the deflate bytes consumed (stored: comp_size), which a
+ * caller compares with comp_size; head_size = 30 + the local name and extra lengths; check the CRC-32 COMPUTED, whenever bytes were summed. dirents and results
+ * (host, cap entries each) may be NULL. Returns the number of entries whose reason is not 0; -1 for bad arguments, HIP errors, stop 4, and a stop of 1 or 2 —
+ * nothing is decoded from a directory that does not end where it should. src, dst, *_on_device as for zultra_hip_inflate_streams (of a host dst only the bytes
+ * entries wrote come back). kernel_ms (may be NULL): five — index, local headers, inflate, copy, check.
+ * Not read: ZIP64 fields per entry, encryption, methods other than 0 and 8, multi-disk archives, an archive without a central directory. One large entry
+ * decodes at the speed of one wave.
+ */
+#define ZULTRA_HIP_UNZIP_UNSUPPORTED 17
+typedef struct zultra_hip_zip_dirent_s {
+   uint64_t central_at, local_off, dst_off;
+   uint32_t comp_size, size, crc32, name_len;
+   uint16_t method, flags, extra_len, comment_len;
+} zultra_hip_zip_dirent_t;
+typedef struct zultra_hip_zip_index_result_s {
+   uint32_t entries, stop;          /* stop kinds 0..2 above; 4 = more entries than `cap` / more output than dst_size (nothing decoded) */
+   uint64_t out_size, dir_used;     /* sum of `size` of the indexed records; bytes of the directory the chain covers */
+   uint32_t tiles, tiles_rewalked;
+} zultra_hip_zip_index_result_t;
+int zultra_hip_zip_index(int device, const void *src, size_t src_size, int src_on_device, uint64_t central_at, uint64_t central_size,
+                         zultra_hip_zip_dirent_t *dirents /* host, cap; NULL with cap 0 */, uint32_t cap, zultra_hip_zip_index_result_t *res,
+                         float *kernel_ms /* may be NULL */);
+int zultra_hip_unzip(int device, const void *src, size_t src_size, int src_on_device, uint64_t central_at, uint64_t central_size, int64_t local_delta,
+                     void *dst, size_t dst_size, int dst_on_device, zultra_hip_zip_index_result_t *res,
+                     zultra_hip_zip_dirent_t *dirents /* host, cap; may be NULL */, zultra_hip_member_result_t *results /* host, cap; may be NULL */, uint32_t cap,
+                     float *kernel_ms /* [5]: index, locals, inflate, copy, check; may be NULL */);
+
 /* CRC-32 of every max-block of the last batch, computed on the device while the blocks are compressed: out[b] is the
  * linear part (zero initial state, no final inversion). zultra_crc32_append() folds one block into a running gzip CRC
  * exactly as zultra_frame_update_checksum(crc, block, len, GZIP) would (reference src/frame.c:324-354,473-480). */

@@ -91,10 +91,24 @@ class IndexResult(C.Structure):
     _fields_ = [("members", C.c_uint32), ("stop", C.c_uint32), ("out_size", C.c_uint64), ("src_used", C.c_uint64), ("tiles", C.c_uint32), ("tiles_rewalked", C.c_uint32)]
 
 
+class ZipIndexResult(C.Structure):
+    # zultra_hip_zip_index_result_t
+    _fields_ = [("entries", C.c_uint32), ("stop", C.c_uint32), ("out_size", C.c_uint64), ("dir_used", C.c_uint64), ("tiles", C.c_uint32), ("tiles_rewalked", C.c_uint32)]
+
+
+class ZipEnd(C.Structure):
+    # zultra_zip_end_t
+    _fields_ = [("nEntries", C.c_ulonglong), ("nCentralOff", C.c_ulonglong), ("nCentralSize", C.c_ulonglong), ("nPrefix", C.c_ulonglong), ("nZip64", C.c_int)]
+
+
 MEMBER_DTYPE = [("off", "<u8"), ("size", "<u8"), ("check", "<u4"), ("flags", "<u4")]   # zultra_hip_member_t
 FRAME_BGZF = 4   # ZULTRA_HIP_FRAME_BGZF
 ZIP_ENTRY_DTYPE = [("local_off", "<u8"), ("comp_size", "<u4"), ("size", "<u4"), ("crc32", "<u4"), ("name_len", "<u4")]   # zultra_hip_zip_entry_t
 ZIP_EMPTY = 0xFFFFFFFF   # entry_block: an empty entry (a zero-length file or a directory)
+ZIP_DIRENT_DTYPE = [("central_at", "<u8"), ("local_off", "<u8"), ("dst_off", "<u8"), ("comp_size", "<u4"), ("size", "<u4"), ("crc32", "<u4"), ("name_len", "<u4"),
+                    ("method", "<u2"), ("flags", "<u2"), ("extra_len", "<u2"), ("comment_len", "<u2")]   # zultra_hip_zip_dirent_t
+ZIP_INFO_DTYPE = np.dtype([("nNameAt", "<u8"), ("nNameLen", "<u4"), ("nMethod", "<u4"), ("nFlags", "<u4"), ("nCrc32", "<u4"), ("nCompSize", "<u4"), ("nSize", "<u4"),
+                           ("nOutOff", "<u8"), ("nStatus", "<u4")], align=True)   # zultra_zip_info_t
 MEMBER_RESULT_DTYPE = [("reason", "<u4"), ("blocks", "<u4"), ("out_size", "<u8"), ("src_used", "<u8"), ("head_size", "<u4"), ("check", "<u4")]
 
 
@@ -125,6 +139,7 @@ EXPORTS = [
     # ZIP archives
     "zultra_hip_zip_members", "zultra_hip_zip_device", "zultra_hip_zip_read", "zultra_hip_last_zip_ms",
     "zultra_zip_end_records", "zultra_memory_bound_zip", "zultra_memory_compress_zip",
+    "zultra_hip_zip_index", "zultra_hip_unzip", "zultra_zip_find_end", "zultra_memory_decompress_zip",
 ]
 
 
@@ -443,6 +458,67 @@ class Lib:
         f.restype = C.c_size_t
         r = f(data.ctypes.data if len(data) else None, len(data), in_off.ctypes.data, in_size.ctypes.data, blob.ctypes.data, name_off.ctypes.data, n, out.ctypes.data, cap, dos_datetime)
         return None if r == _SIZE_MAX else out[:r].tobytes()
+
+    def zip_index(self, src, src_size, central_at, central_size, cap, device=0):
+        """zultra_hip_zip_index. src: a uint8 array (host memory, staged by the call) or an integer device pointer; cap: room for that many dirents, 0 to
+        pass dirents = NULL. -> (rc, ZipIndexResult, dirents (ZIP_DIRENT_DTYPE), kernel_ms)."""
+        dirents = np.zeros(cap, dtype=ZIP_DIRENT_DTYPE)
+        assert dirents.itemsize == 48
+        res = ZipIndexResult()
+        src_dev = not isinstance(src, np.ndarray)
+        ms = C.c_float(0)
+        f = self.L.zultra_hip_zip_index
+        f.argtypes = [C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint32, C.POINTER(ZipIndexResult), C.POINTER(C.c_float)]
+        f.restype = C.c_int
+        rc = f(device, None if src is None else int(src) if src_dev else src.ctypes.data, src_size, 1 if src_dev else 0, central_at, central_size,
+               dirents.ctypes.data if cap else None, cap, C.byref(res), C.byref(ms))
+        return rc, res, dirents[:res.entries if rc == 0 else 0], float(ms.value)
+
+    def unzip(self, src, src_size, central_at, central_size, local_delta, dst, dst_size, cap=None, device=0):
+        """zultra_hip_unzip. src / dst: a uint8 array (host memory, staged by the call) or an integer device pointer (used in place); cap: room for that
+        many dirents and results, None to pass both as NULL. -> (rc, ZipIndexResult, dirents, results (MEMBER_RESULT_DTYPE), kernel_ms = [index,
+        locals, inflate, copy, check])."""
+        res = ZipIndexResult()
+        dirents = np.zeros(cap or 0, dtype=ZIP_DIRENT_DTYPE)
+        out = np.zeros(cap or 0, dtype=MEMBER_RESULT_DTYPE)
+        src_dev, dst_dev = not isinstance(src, np.ndarray), not isinstance(dst, np.ndarray)
+        ms = (C.c_float * 5)()
+        f = self.L.zultra_hip_unzip
+        f.argtypes = [C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_uint64, C.c_uint64, C.c_int64, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(ZipIndexResult), C.c_void_p, C.c_void_p,
+                      C.c_uint32, C.POINTER(C.c_float)]
+        f.restype = C.c_int
+        rc = f(device, None if src is None else int(src) if src_dev else src.ctypes.data, src_size, 1 if src_dev else 0, central_at, central_size, local_delta,
+               None if dst is None else int(dst) if dst_dev else dst.ctypes.data, dst_size, 1 if dst_dev else 0, C.byref(res),
+               dirents.ctypes.data if cap else None, out.ctypes.data if cap else None, cap or 0, ms)
+        n = res.entries if rc >= 0 else 0
+        return rc, res, dirents[:n], out[:n], [float(v) for v in ms]
+
+    def zip_find_end(self, tail, archive_size):
+        """zultra_zip_find_end over the last len(tail) bytes of an archive -> ZipEnd, or None where the call returns -1."""
+        tail = _as_u8(tail)
+        end = ZipEnd()
+        f = self.L.zultra_zip_find_end
+        f.argtypes = [C.c_void_p, C.c_size_t, C.c_ulonglong, C.POINTER(ZipEnd)]
+        f.restype = C.c_int
+        return end if f(tail.ctypes.data if len(tail) else None, len(tail), archive_size, C.byref(end)) == 0 else None
+
+    def memory_decompress_zip(self, data, max_out, max_info, list_only=False):
+        """zultra_memory_decompress_zip -> (the output's bytes — in list-only mode the size it needs —, or None where the call returns (size_t)-1;
+        the infos (ZIP_INFO_DTYPE) as far as they are known; *pnEntries)."""
+        data = _as_u8(data)
+        out = np.empty(max(max_out, 1), dtype=np.uint8)
+        info = np.zeros(max(max_info, 1), dtype=ZIP_INFO_DTYPE)
+        assert info.itemsize == 48
+        entries = C.c_size_t(0)
+        f = self.L.zultra_memory_decompress_zip
+        f.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+        f.restype = C.c_size_t
+        r = f(data.ctypes.data if len(data) else None, len(data), None if list_only else out.ctypes.data, 0 if list_only else max_out, info.ctypes.data if max_info else None, max_info,
+              C.byref(entries))
+        n = min(int(entries.value), max_info)
+        if r == _SIZE_MAX:
+            return None, info[:n], int(entries.value)
+        return (int(r) if list_only else out[:r].tobytes()), info[:n], int(entries.value)
 
     def checksum(self, data, flags, start=None):
         data = _as_u8(data)

@@ -1487,3 +1487,105 @@ extern "C" size_t zultra_memory_decompress_members(const unsigned char *pIn, siz
    if (pnMembers) *pnMembers = members;
    return written;
 }
+
+// ---- ZIP archives read: the end records on the host, everything else on the device (include/zultra_hip.h: zultra_hip_unzip) ---------------------------
+static unsigned long long zip_get(const unsigned char *p, int nbytes) {
+   unsigned long long v = 0;
+   for (int k = 0; k < nbytes; k++) v |= (unsigned long long)p[k] << (8 * k);
+   return v;
+}
+
+extern "C" int zultra_zip_find_end(const unsigned char *pTail, size_t nTail, unsigned long long nArchiveSize, zultra_zip_end_t *pEnd) {
+   if (!pTail || !pEnd || nTail < 22 || nTail > nArchiveSize) return -1;
+   const unsigned long long tail_at = nArchiveSize - nTail;   // the tail's position in the archive
+   size_t p = nTail - 22;
+   for (;; p--) {   // the last end record whose comment reaches the archive's end exactly
+      if (zip_get(pTail + p, 4) == 0x06054b50 && p + 22 + zip_get(pTail + p + 20, 2) == nTail) break;
+      if (p == 0) return -1;
+   }
+   if (zip_get(pTail + p + 4, 2) != 0 || zip_get(pTail + p + 6, 2) != 0) return -1;   // this disk, the directory's disk
+   zultra_zip_end_t e;
+   e.nEntries = zip_get(pTail + p + 10, 2);
+   e.nCentralSize = zip_get(pTail + p + 12, 4);
+   e.nCentralOff = zip_get(pTail + p + 16, 4);
+   e.nZip64 = 0;
+   unsigned long long dir_end = tail_at + p;
+   if (p >= 20 && zip_get(pTail + p - 20, 4) == 0x07064b50) {
+      const unsigned char *loc = pTail + p - 20;
+      if (zip_get(loc + 4, 4) != 0 || zip_get(loc + 16, 4) != 1) return -1;
+      // the record: where the locator says, or — behind a prefix the locator does not count — directly in front of the locator
+      const unsigned long long named = zip_get(loc + 8, 8);
+      size_t at = (size_t)-1;
+      if (named >= tail_at && named - tail_at <= p - 20 && p - 20 - (size_t)(named - tail_at) >= 56 && zip_get(pTail + (size_t)(named - tail_at), 4) == 0x06064b50)
+         at = (size_t)(named - tail_at);
+      else if (p - 20 >= 56 && zip_get(pTail + p - 76, 4) == 0x06064b50)
+         at = p - 76;
+      if (at == (size_t)-1) return -1;
+      const unsigned char *r = pTail + at;
+      if (zip_get(r + 16, 4) != 0 || zip_get(r + 20, 4) != 0) return -1;
+      e.nEntries = zip_get(r + 32, 8);
+      e.nCentralSize = zip_get(r + 40, 8);
+      e.nCentralOff = zip_get(r + 48, 8);
+      e.nZip64 = 1;
+      dir_end = tail_at + at;
+   }
+   else if (e.nCentralSize == 0xFFFFFFFFull || e.nCentralOff == 0xFFFFFFFFull)
+      return -1;
+   if (e.nCentralSize > dir_end || e.nCentralOff > dir_end - e.nCentralSize) return -1;   // a negative prefix
+   e.nPrefix = dir_end - e.nCentralSize - e.nCentralOff;
+   *pEnd = e;
+   return 0;
+}
+
+extern "C" size_t zultra_memory_decompress_zip(const unsigned char *pIn, size_t nIn, unsigned char *pOut, size_t nMaxOut, zultra_zip_info_t *pInfo, size_t nMaxInfo, size_t *pnEntries) {
+   if (pnEntries) *pnEntries = 0;
+   if (!pIn || nIn == 0 || (!pOut && nMaxOut) || (!pInfo && nMaxInfo)) return (size_t)-1;
+   const size_t tail = nIn < 65535 + 22 + 20 + 56 ? nIn : 65535 + 22 + 20 + 56;
+   zultra_zip_end_t end;
+   if (zultra_zip_find_end(pIn + nIn - tail, tail, nIn, &end) != 0) return (size_t)-1;
+   const unsigned long long central_at = end.nPrefix + end.nCentralOff;
+   if (end.nCentralSize / 46 < end.nEntries) return (size_t)-1;   // (more entries than the directory has room for: nothing is allocated for such a count)
+   const int device = zh_pick_device();
+   uint8_t *const d_in = (uint8_t *)zh_device_upload(device, pIn, nIn);
+   if (!d_in) return (size_t)-1;
+   const uint32_t cap = (uint32_t)zh_min64(end.nEntries, 0xFFFFFFFFull);
+   std::vector<zultra_hip_zip_dirent_t> dirents(cap ? cap : 1);
+   std::vector<zultra_hip_member_result_t> results(cap ? cap : 1);   // (zero-initialised: list-only leaves every status 0)
+   zultra_hip_zip_index_result_t res = {};
+   const bool list = pOut == NULL;
+   int rc;
+   if (list)
+      rc = zultra_hip_zip_index(device, d_in, nIn, 1, central_at, end.nCentralSize, cap ? dirents.data() : NULL, cap, &res, NULL);
+   else
+      rc = zultra_hip_unzip(device, d_in, nIn, 1, central_at, end.nCentralSize, (int64_t)end.nPrefix, pOut, nMaxOut, 0, &res, dirents.data(), results.data(), cap ? cap : 1, NULL);
+   // more output than nMaxOut (stop 4 with the end record's count): nothing was written and the directory was not read back; the infos are known all the
+   // same, from the index alone. That runs the index kernels a second time, over the copy of the archive that is in device memory already: the price of an
+   // error path, paid so that zultra_hip_unzip's refusal stays one that writes nothing
+   const bool again = rc < 0 && !list && res.stop == 4 && res.entries == cap && cap != 0;
+   const int irc = again ? zultra_hip_zip_index(device, d_in, nIn, 1, central_at, end.nCentralSize, dirents.data(), cap, &res, NULL) : 0;
+   zh_device_release(d_in);
+   if ((rc < 0 && !again) || irc != 0) {
+      if (pnEntries && res.stop == 4) *pnEntries = res.entries;
+      return (size_t)-1;
+   }
+   if (pnEntries) *pnEntries = res.entries;
+   bool ok = rc >= 0 && res.stop == 0 && res.entries == end.nEntries && res.entries <= nMaxInfo;
+   for (uint32_t i = 0; i < res.entries; i++) {
+      const zultra_hip_zip_dirent_t &d = dirents[i];
+      const zultra_hip_member_result_t &r = results[i];
+      if (r.reason != 0 || (!list && rc >= 0 && d.method == 8 && r.src_used != d.comp_size)) ok = false;   // (a deflated entry fills its range, as a member of zultra_memory_decompress_batch does)
+      if (i < nMaxInfo) {
+         zultra_zip_info_t &o = pInfo[i];
+         o.nNameAt = d.central_at + 46;
+         o.nNameLen = d.name_len;
+         o.nMethod = d.method;
+         o.nFlags = d.flags;
+         o.nCrc32 = d.crc32;
+         o.nCompSize = d.comp_size;
+         o.nSize = d.size;
+         o.nOutOff = d.dst_off;
+         o.nStatus = r.reason;
+      }
+   }
+   return ok ? (size_t)res.out_size : (size_t)-1;
+}

@@ -1,5 +1,5 @@
 // zh_inflate.hip — host side of the context-free inflate calls of include/zultra_hip.h: batches of raw streams (with or without a preset dictionary), batches
-// of gzip / zlib members, the member index of a whole file, the whole file. No zultra_hip_ctx_t: a call owns what it allocates and releases it when it returns.
+// of gzip / zlib members, the member index of a whole file, the whole file, a ZIP archive's directory and its entries. No zultra_hip_ctx_t: a call owns what it allocates and releases it when it returns.
 #include <zh_platform.h>
 
 #include <string.h>
@@ -12,6 +12,7 @@
 #include "zh_inflate_out.h"
 #include "zh_inflate_check.h"
 #include "zh_inflate_index.h"
+#include "zh_unzip.h"
 
 // ---- batched inflate (zh_inflate_out.h, zh_inflate_check.h) -------------------------------------------------------------------------------------------
 static_assert(sizeof(zultra_hip_inflate_item_t) == sizeof(zh_inflate_item_t) && sizeof(zultra_hip_inflate_result_t) == sizeof(zh_inflate_result_t), "ABI");
@@ -21,6 +22,7 @@ static_assert(sizeof(zultra_hip_member_result_t) == sizeof(zh_member_result_t), 
 enum zh_inflate_event {
    ZH_IEV_INDEX_START, ZH_IEV_INDEX_END, ZH_IEV_ITEMS_START, ZH_IEV_ITEMS_END,   // around zh_ix_tiles and zh_ix_resolve; around zh_ix_items
    ZH_IEV_HEADS, ZH_IEV_INFLATE, ZH_IEV_CHECKS, ZH_IEV_END,   // starts of zh_frame_heads, of the inflate kernel (a streams call's first mark), of zh_check_members; the end
+   ZH_IEV_UZ_LOCALS, ZH_IEV_UZ_INFLATE, ZH_IEV_UZ_COPY, ZH_IEV_UZ_CHECKS, ZH_IEV_UZ_END,   // zultra_hip_unzip: starts of zh_uz_locals, the inflate kernel, zh_uz_copy, zh_check_members; the end
    ZH_INFLATE_EVENTS
 };
 // a one-item batch of zh_check_members whose "output" is a device dictionary (zh_dictid)
@@ -42,13 +44,16 @@ struct zh_inflate_call_t {
    zh_dictjob_t *d_dictjob = NULL;
    zh_ix_tile_t *d_ix_tiles = NULL;   // (the member index only)
    zh_ix_totals_t *d_ix_totals = NULL;
+   zh_zip_dirent_t *d_dirents = NULL;   // (a ZIP archive only, as the two below)
+   zh_uz_copy_t *d_copies = NULL;
+   uint32_t *d_ncopies = NULL;
    hipEvent_t ev[ZH_INFLATE_EVENTS] = {};
    std::vector<uint32_t> order;   // the items with room, by dst_off
    const uint8_t *s8 = NULL, *hist = NULL;   // (hist: the last hist_len bytes of the call's dictionary, where the kernel reads them)
    uint8_t *d8 = NULL;
    uint32_t hist_len = 0;
    ~zh_inflate_call_t() {
-      for (void *p : std::initializer_list<void *>{d_src, d_dst, d_hist, d_items, d_inner, d_results, d_members, d_idx, d_tables, d_dictjob, d_ix_tiles, d_ix_totals}) (void)hipFree(p);
+      for (void *p : std::initializer_list<void *>{d_src, d_dst, d_hist, d_items, d_inner, d_results, d_members, d_idx, d_tables, d_dictjob, d_ix_tiles, d_ix_totals, d_dirents, d_copies, d_ncopies}) (void)hipFree(p);
       for (hipEvent_t e : ev)
          if (e) (void)hipEventDestroy(e);
    }
@@ -227,7 +232,8 @@ static const std::vector<uint32_t> &zh_ck_tables() {
 
 // zh_check_members<framing> over n items: idx = those of at most ZH_CK_SMALL_MAX bytes of room first (spg threads each), then the others
 static int zh_check_launch(uint32_t framing, const uint8_t *src, const uint8_t *dst, uint64_t dst_size, const zh_inflate_item_t *d_items, const zh_inflate_result_t *d_inner,
-                           zh_member_result_t *d_members, const uint32_t *d_idx, uint32_t nsmall, uint32_t nlarge, uint32_t spg, const uint32_t *d_tables) {
+                           zh_member_result_t *d_members, const uint32_t *d_idx, uint32_t nsmall, uint32_t nlarge, uint32_t spg, const uint32_t *d_tables,
+                           const zh_zip_dirent_t *d_dirents = NULL /* ZH_M_ZIP: in the place of d_items */) {
    uint32_t small_blocks, large_blocks = nlarge;
    if (framing == ZH_M_RAW) {
       small_blocks = (uint32_t)zh_min64(((uint64_t)nsmall + nlarge + ZH_CK_THREADS - 1) / ZH_CK_THREADS, 4096);
@@ -244,12 +250,13 @@ static int zh_check_launch(uint32_t framing, const uint8_t *src, const uint8_t *
    switch (framing) {
    case ZH_M_GZIP: check_members = zh_check_members<ZH_M_GZIP>; break;
    case ZH_M_ZLIB: check_members = zh_check_members<ZH_M_ZLIB>; break;
+   case ZH_M_ZIP: check_members = zh_check_members<ZH_M_ZIP>; break;
    }
-   ZH_LAUNCH(check_members, small_blocks + large_blocks, ZH_CK_THREADS, 0, src, dst, dst_size, d_items, d_inner, d_members, d_idx, nsmall, nlarge, spg, small_blocks, d_tables);
+   ZH_LAUNCH(check_members, small_blocks + large_blocks, ZH_CK_THREADS, 0, src, dst, dst_size, d_items, d_inner, d_members, d_idx, nsmall, nlarge, spg, small_blocks, d_tables, d_dirents);
    return 0;
 }
 
-// The checksum kernel's two forms: by the room an item has (what it will have written is known on the device only). Uploads idx and, for gzip, the tables.
+// The checksum kernel's two forms: by the room an item has (what it will have written is known on the device only). Uploads idx and, for the CRC-32, the tables.
 static int zh_check_plan(zh_inflate_call_t &C, const zultra_hip_inflate_item_t *items, uint32_t n, unsigned int framing) {
    std::vector<uint32_t> idx(n);
    for (uint32_t k = 0; k < n; k++)
@@ -261,7 +268,7 @@ static int zh_check_plan(zh_inflate_call_t &C, const zultra_hip_inflate_item_t *
       if (items[k].dst_cap > ZH_CK_SMALL_MAX) idx[C.nsmall + C.nlarge++] = k;
    ZH_TRY(zh_dalloc(&C.d_idx, n));
    ZH_TRY(hipMemcpy(C.d_idx, idx.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice));
-   if (framing == ZH_M_GZIP) {
+   if (framing == ZH_M_GZIP || framing == ZH_M_ZIP) {
       ZH_TRY(zh_dalloc(&C.d_tables, ZH_CK_TABLE_WORDS));
       ZH_TRY(hipMemcpy(C.d_tables, zh_ck_tables().data(), ZH_CK_TABLE_WORDS * sizeof(uint32_t), hipMemcpyHostToDevice));
    }
@@ -329,16 +336,21 @@ extern "C" int zultra_hip_inflate_members(int device, const void *src, size_t sr
 // ---- the member index of a whole file (zh_inflate_index.h) -------------------------------------------------------------------------------------------
 static_assert(sizeof(zh_ix_tile_t) == 64, "one record per tile");
 
-// what the two calls below keep of an index between its passes
+// what the calls below keep of an index between its passes. zip: the records are a ZIP archive's central directory (zh_unzip.h), else gzip members; D0, size:
+// the range of the source that the chain runs over (gzip members: the whole source)
 struct zh_index_t {
-   uint64_t T = 0, ntiles = 0;
+   bool zip = false;
+   uint64_t D0 = 0, size = 0;
+   uint64_t D1 = 0, T = 0, ntiles = 0;   // (zh_index_run)
    zh_ix_totals_t tot = {};
 };
-// 1. the arguments, the device, the events `first` to `last`, the source staged; zh_ix_tiles and zh_ix_resolve between the index's two events; the totals read
-// back (the call's first synchronisation) and reported
-static int zh_index_run(zh_inflate_call_t &C, zh_index_t &X, int device, const void *src, size_t src_size, int src_on_device, int first, int last, zultra_hip_index_result_t *res) {
-   if (!src || src_size == 0 || device < 0 || device >= zultra_hip_device_count()) return -1;
+// 1. the arguments, the device, the index's four events and the events `first` to `last` (first > last: none), the source staged; the format's tile and resolve
+// kernels between the index's two events; the totals read back (the call's first synchronisation) into X.tot
+static int zh_index_run(zh_inflate_call_t &C, zh_index_t &X, int device, const void *src, size_t src_size, int src_on_device, int first, int last) {
+   if (!src || src_size == 0 || X.D0 > src_size || X.size > src_size - X.D0 || device < 0 || device >= zultra_hip_device_count()) return -1;
+   X.D1 = X.D0 + X.size;
    ZH_TRY(hipSetDevice(device));
+   for (int e = ZH_IEV_INDEX_START; e <= ZH_IEV_ITEMS_END; e++) ZH_TRY(hipEventCreate(&C.ev[e]));
    for (int e = first; e <= last; e++) ZH_TRY(hipEventCreate(&C.ev[e]));
    C.s8 = (const uint8_t *)src;
    if (!src_on_device) {
@@ -346,32 +358,54 @@ static int zh_index_run(zh_inflate_call_t &C, zh_index_t &X, int device, const v
       ZH_TRY(hipMemcpy(C.d_src, src, src_size, hipMemcpyHostToDevice));
       C.s8 = C.d_src;
    }
-   const int tile = zh_env("ZULTRA_HIP_INDEX_TILE", 0);   // tests, tools/inflate_time.py: any value >= 32, no power of two needed
-   X.T = tile >= (int)ZH_IX_TILE_MIN ? (uint64_t)tile : (uint64_t)ZH_IX_TILE;
-   X.ntiles = ((uint64_t)src_size + X.T - 1) / X.T;
-   ZH_TRY(zh_dalloc(&C.d_ix_tiles, (size_t)X.ntiles));
+   const int tile = zh_env("ZULTRA_HIP_INDEX_TILE", 0);   // tests, tools/inflate_time.py, tools/unzip_time.py: any value >= 32, no power of two needed
+   X.T = tile >= (int)ZH_IX_TILE_MIN ? (uint64_t)tile : X.zip ? (uint64_t)ZH_UZ_TILE : (uint64_t)ZH_IX_TILE;
+   X.ntiles = (X.size + X.T - 1) / X.T;   // (0: an empty directory, which the resolve pass alone reports)
+   ZH_TRY(zh_dalloc(&C.d_ix_tiles, (size_t)zh_max64(X.ntiles, 1)));
    ZH_TRY(zh_dalloc(&C.d_ix_totals, 1));
-   const uint32_t grid = zh_capped((uint32_t)zh_min64(X.ntiles, 32ull * zh_device_cus(device)), zh_grid_cap());   // (one wave per workgroup, as the inflate kernel)
+   const uint32_t grid = zh_capped((uint32_t)zh_min64(zh_max64(X.ntiles, 1), 32ull * zh_device_cus(device)), zh_grid_cap());   // (one wave per workgroup, as the inflate kernel)
    ZH_TRY(hipEventRecord(C.ev[ZH_IEV_INDEX_START], 0));
-   ZH_LAUNCH(zh_ix_tiles, grid, ZH_IX_THREADS, 0, C.s8, (uint64_t)src_size, X.T, X.ntiles, C.d_ix_tiles);
-   ZH_LAUNCH(zh_ix_resolve, 1, ZH_IX_THREADS, 0, C.s8, (uint64_t)src_size, X.T, X.ntiles, C.d_ix_tiles, C.d_ix_totals);
+   if (X.zip) {
+      if (X.ntiles) ZH_LAUNCH(zh_uz_tiles, grid, ZH_IX_THREADS, 0, C.s8, (uint64_t)src_size, X.D0, X.D1, X.T, X.ntiles, C.d_ix_tiles);
+      ZH_LAUNCH(zh_uz_resolve, 1, ZH_IX_THREADS, 0, C.s8, X.D0, X.D1, X.T, X.ntiles, C.d_ix_tiles, C.d_ix_totals);
+   }
+   else {
+      ZH_LAUNCH(zh_ix_tiles, grid, ZH_IX_THREADS, 0, C.s8, (uint64_t)src_size, X.T, X.ntiles, C.d_ix_tiles);
+      ZH_LAUNCH(zh_ix_resolve, 1, ZH_IX_THREADS, 0, C.s8, (uint64_t)src_size, X.T, X.ntiles, C.d_ix_tiles, C.d_ix_totals);
+   }
    ZH_TRY(hipEventRecord(C.ev[ZH_IEV_INDEX_END], 0));
    ZH_TRY(hipMemcpy(&X.tot, C.d_ix_totals, sizeof(X.tot), hipMemcpyDeviceToHost));
    ZH_TRY(hipGetLastError());
+   return 0;
+}
+// the totals as the two public result records name them
+static void zh_index_report(const zh_index_t &X, zultra_hip_index_result_t *res) {
    res->members = (uint32_t)zh_min64(X.tot.members, 0xFFFFFFFFull);
    res->stop = X.tot.stop;
    res->out_size = X.tot.out_size;
    res->src_used = X.tot.src_used;
    res->tiles = (uint32_t)zh_min64(X.tot.tiles, 0xFFFFFFFFull);
    res->tiles_rewalked = (uint32_t)zh_min64(X.tot.tiles_rewalked, 0xFFFFFFFFull);
-   return 0;
 }
-// 2. zh_ix_items into C.d_items (the index's member count of them), between the items' two events
-static int zh_index_items(zh_inflate_call_t &C, const zh_index_t &X, size_t src_size) {
-   ZH_TRY(zh_dalloc(&C.d_items, (size_t)X.tot.members));
+static void zh_index_report(const zh_index_t &X, zultra_hip_zip_index_result_t *res) {
+   res->entries = (uint32_t)zh_min64(X.tot.members, 0xFFFFFFFFull);
+   res->stop = X.tot.stop;
+   res->out_size = X.tot.out_size;
+   res->dir_used = X.tot.src_used - X.D0;
+   res->tiles = (uint32_t)zh_min64(X.tot.tiles, 0xFFFFFFFFull);
+   res->tiles_rewalked = (uint32_t)zh_min64(X.tot.tiles_rewalked, 0xFFFFFFFFull);
+}
+// 2. the format's items kernel into C.d_items or C.d_dirents (the index's count of them), between the items' two events
+static int zh_index_items(zh_inflate_call_t &C, const zh_index_t &X) {
+   ZH_TRY(X.zip ? zh_dalloc(&C.d_dirents, (size_t)X.tot.members) : zh_dalloc(&C.d_items, (size_t)X.tot.members));
    const uint32_t grid = zh_capped((uint32_t)zh_min64((X.ntiles + ZH_IX_THREADS - 1) / ZH_IX_THREADS, 4096), zh_grid_cap());
    ZH_TRY(hipEventRecord(C.ev[ZH_IEV_ITEMS_START], 0));
-   ZH_LAUNCH(zh_ix_items, grid, ZH_IX_THREADS, 0, C.s8, (uint64_t)src_size, X.T, X.ntiles, C.d_ix_tiles, C.d_items);
+   if (X.zip) {
+      ZH_LAUNCH(zh_uz_entries, grid, ZH_IX_THREADS, 0, C.s8, X.D0, X.D1, X.T, X.ntiles, C.d_ix_tiles, C.d_dirents);
+   }
+   else {
+      ZH_LAUNCH(zh_ix_items, grid, ZH_IX_THREADS, 0, C.s8, X.D1, X.T, X.ntiles, C.d_ix_tiles, C.d_items);
+   }
    ZH_TRY(hipEventRecord(C.ev[ZH_IEV_ITEMS_END], 0));
    return 0;
 }
@@ -391,7 +425,9 @@ extern "C" int zultra_hip_index_members(int device, const void *src, size_t src_
    memset(res, 0, sizeof(*res));
    zh_inflate_call_t C;
    zh_index_t X;
-   if (zh_index_run(C, X, device, src, src_size, src_on_device, ZH_IEV_INDEX_START, ZH_IEV_ITEMS_END, res)) return -1;
+   X.size = src_size;
+   if (zh_index_run(C, X, device, src, src_size, src_on_device, 0, -1)) return -1;
+   zh_index_report(X, res);
    const bool want = items != NULL && cap != 0;
    if (X.tot.members > 0xFFFFFFFFull || (want && X.tot.members > cap)) {
       res->stop = 4;
@@ -399,7 +435,7 @@ extern "C" int zultra_hip_index_members(int device, const void *src, size_t src_
    }
    const bool with_items = want && X.tot.members != 0;
    if (with_items) {
-      if (zh_index_items(C, X, src_size)) return -1;
+      if (zh_index_items(C, X)) return -1;
       ZH_TRY(hipMemcpy(items, C.d_items, (size_t)X.tot.members * sizeof(zh_inflate_item_t), hipMemcpyDeviceToHost));
    }
    ZH_TRY(hipDeviceSynchronize());
@@ -418,7 +454,9 @@ extern "C" int zultra_hip_inflate_file(int device, const void *src, size_t src_s
    memset(res, 0, sizeof(*res));
    zh_inflate_call_t C;
    zh_index_t X;
-   if (zh_index_run(C, X, device, src, src_size, src_on_device, ZH_IEV_INDEX_START, ZH_IEV_END, res)) return -1;
+   X.size = src_size;
+   if (zh_index_run(C, X, device, src, src_size, src_on_device, ZH_IEV_HEADS, ZH_IEV_END)) return -1;
+   zh_index_report(X, res);
    if (X.tot.members > 0xFFFFFFFFull || X.tot.out_size > dst_size || (results && X.tot.members > results_cap)) {
       res->stop = 4;   // nothing is decoded: res says how much room the file needs
       return -1;
@@ -429,7 +467,7 @@ extern "C" int zultra_hip_inflate_file(int device, const void *src, size_t src_s
       return 0;
    }
    const size_t out_size = (size_t)X.tot.out_size;
-   if (zh_index_items(C, X, src_size)) return -1;
+   if (zh_index_items(C, X)) return -1;
    std::vector<zultra_hip_inflate_item_t> items(n);
    ZH_TRY(hipMemcpy(items.data(), C.d_items, (size_t)n * sizeof(zh_inflate_item_t), hipMemcpyDeviceToHost));
    ZH_TRY(hipGetLastError());
@@ -446,6 +484,133 @@ extern "C" int zultra_hip_inflate_file(int device, const void *src, size_t src_s
    }
    if (zh_members_run(C, device, src_size, dst_on_device ? dst_size : out_size, ZH_M_GZIP, false, NULL, 0, 0, items.data(), n, results, kernel_ms ? kernel_ms + 1 : NULL)) return -1;
    if (kernel_ms) kernel_ms[0] = zh_index_ms(C, true);
+   C.order.reserve(n);
+   for (uint32_t k = 0; k < n; k++)   // (as the index put them)
+      if (items[k].dst_cap) C.order.push_back(k);
+   return zh_inflate_collect(C, dst, dst_on_device, items.data(), n, results);
+}
+
+// ---- a ZIP archive read (zh_unzip.h) ------------------------------------------------------------------------------------------------------------------
+static_assert(sizeof(zultra_hip_zip_dirent_t) == sizeof(zh_zip_dirent_t) && sizeof(zh_zip_dirent_t) == 48, "ABI");
+
+// The directory index alone.
+extern "C" int zultra_hip_zip_index(int device, const void *src, size_t src_size, int src_on_device, uint64_t central_at, uint64_t central_size, zultra_hip_zip_dirent_t *dirents, uint32_t cap,
+                                    zultra_hip_zip_index_result_t *res, float *kernel_ms) {
+   ZH_EMU_SERIALIZE();
+   if (kernel_ms) *kernel_ms = 0.f;
+   if (!res || (!dirents && cap)) return -1;
+   memset(res, 0, sizeof(*res));
+   zh_inflate_call_t C;
+   zh_index_t X;
+   X.zip = true, X.D0 = central_at, X.size = central_size;
+   if (zh_index_run(C, X, device, src, src_size, src_on_device, 0, -1)) return -1;
+   zh_index_report(X, res);
+   const bool want = dirents != NULL && cap != 0;
+   if (X.tot.members > 0xFFFFFFFFull || (want && X.tot.members > cap)) {
+      res->stop = 4;
+      return -1;
+   }
+   const bool with_items = want && X.tot.members != 0;
+   if (with_items) {
+      if (zh_index_items(C, X)) return -1;
+      ZH_TRY(hipMemcpy(dirents, C.d_dirents, (size_t)X.tot.members * sizeof(zh_zip_dirent_t), hipMemcpyDeviceToHost));
+   }
+   ZH_TRY(hipDeviceSynchronize());
+   ZH_TRY(hipGetLastError());
+   if (kernel_ms) *kernel_ms = zh_index_ms(C, with_items);
+   return 0;
+}
+
+// A whole archive: the index; the dirents read once, for the checksum kernel's two forms and the copy kernel's grid; then local headers, inflate, copy and
+// checks in four launches on the null stream, the results read back, one synchronisation at the end. The index makes the destination ranges disjoint, in order
+// and — behind the out_size gate — in range.
+extern "C" int zultra_hip_unzip(int device, const void *src, size_t src_size, int src_on_device, uint64_t central_at, uint64_t central_size, int64_t local_delta, void *dst, size_t dst_size,
+                                int dst_on_device, zultra_hip_zip_index_result_t *res, zultra_hip_zip_dirent_t *dirents, zultra_hip_member_result_t *results, uint32_t cap, float *kernel_ms) {
+   ZH_EMU_SERIALIZE();
+   if (kernel_ms)
+      for (int i = 0; i < 5; i++) kernel_ms[i] = 0.f;
+   if (!res || (!dst && dst_size) || local_delta > (1ll << 62) || local_delta < -(1ll << 62)) return -1;
+   memset(res, 0, sizeof(*res));
+   zh_inflate_call_t C;
+   zh_index_t X;
+   X.zip = true, X.D0 = central_at, X.size = central_size;
+   if (zh_index_run(C, X, device, src, src_size, src_on_device, ZH_IEV_UZ_LOCALS, ZH_IEV_UZ_END)) return -1;
+   zh_index_report(X, res);
+   if (X.tot.stop == 1 || X.tot.stop == 2) return -1;   // nothing is decoded from a directory that does not end where it should
+   if (X.tot.members > 0xFFFFFFFFull || X.tot.out_size > dst_size || ((dirents || results) && X.tot.members > cap)) {
+      res->stop = 4;   // nothing is decoded: res says how much room the archive needs
+      return -1;
+   }
+   const uint32_t n = (uint32_t)X.tot.members;
+   if (n == 0) {
+      if (kernel_ms) kernel_ms[0] = zh_index_ms(C, false);
+      return 0;
+   }
+   const size_t out_size = (size_t)X.tot.out_size;
+   if (zh_index_items(C, X)) return -1;
+   std::vector<zultra_hip_zip_dirent_t> own_dirents;
+   if (!dirents) {
+      own_dirents.resize(n);
+      dirents = own_dirents.data();
+   }
+   ZH_TRY(hipMemcpy(dirents, C.d_dirents, (size_t)n * sizeof(zh_zip_dirent_t), hipMemcpyDeviceToHost));
+   ZH_TRY(hipGetLastError());
+   // an entry's room as an item: what zh_check_plan splits by and zh_inflate_collect copies by; the stored entries that may be copied, and the largest of them
+   std::vector<zultra_hip_inflate_item_t> items(n);
+   uint32_t ncopy = 0, copy_max = 0;
+   for (uint32_t k = 0; k < n; k++) {
+      items[k] = {0, 0, dirents[k].dst_off, dirents[k].size};
+      if (dirents[k].method == 0 && dirents[k].size && dirents[k].size != 0xFFFFFFFFu) {
+         ncopy++;
+         copy_max = std::max(copy_max, dirents[k].size);
+      }
+   }
+   C.d8 = (uint8_t *)dst;
+   if (!dst_on_device) {   // a host destination is staged: exactly the bytes the index counted
+      ZH_TRY(zh_dalloc(&C.d_dst, out_size ? out_size : 1));
+      C.d8 = C.d_dst;
+   }
+   const size_t room = dst_on_device ? dst_size : out_size;
+   ZH_TRY(zh_dalloc(&C.d_inner, n));
+   ZH_TRY(zh_dalloc(&C.d_results, n));
+   ZH_TRY(zh_dalloc(&C.d_members, n));
+   ZH_TRY(zh_dalloc(&C.d_copies, ncopy ? ncopy : 1));
+   ZH_TRY(zh_dalloc(&C.d_ncopies, 1));
+   ZH_TRY(hipMemset(C.d_ncopies, 0, sizeof(uint32_t)));
+   if (zh_check_plan(C, items.data(), n, ZH_M_ZIP)) return -1;
+   const uint32_t grid_cap = zh_grid_cap();
+   ZH_TRY(hipEventRecord(C.ev[ZH_IEV_UZ_LOCALS], 0));
+   ZH_LAUNCH(zh_uz_locals, zh_capped((uint32_t)zh_min64(((uint64_t)n + ZH_UZ_THREADS - 1) / ZH_UZ_THREADS, 4096), grid_cap), ZH_UZ_THREADS, 0, C.s8, (uint64_t)src_size, C.d_dirents, n,
+             (int64_t)local_delta, C.d_inner, C.d_members, C.d_copies, C.d_ncopies);
+   ZH_TRY(hipEventRecord(C.ev[ZH_IEV_UZ_INFLATE], 0));
+   if (zh_inflate_launch(C, device, src_size, room, C.d_inner, n)) return -1;
+   ZH_TRY(hipEventRecord(C.ev[ZH_IEV_UZ_COPY], 0));
+   if (ncopy) {
+      // a grid of a multiple of yslices workgroups, yslices by the largest stored entry (zh_zip_copy's layout)
+      const uint32_t waves = ZH_UZ_COPY_THREADS / 64;
+      uint32_t yslices = (uint32_t)zh_min64(zh_max64(((uint64_t)copy_max / 16 + ZH_ZIP_SLICE_CHUNKS - 1) / ZH_ZIP_SLICE_CHUNKS, 1), ZH_UZ_MAX_YSLICES);
+      uint32_t xdim = (uint32_t)zh_min64(((uint64_t)ncopy + waves - 1) / waves, zh_max64(8ull * zh_device_cus(device) / yslices, 1));
+      if (grid_cap) {
+         yslices = min(yslices, grid_cap);
+         xdim = max(1u, min(xdim, grid_cap / yslices));
+      }
+      ZH_LAUNCH(zh_uz_copy, xdim * yslices, ZH_UZ_COPY_THREADS, 0, C.s8, (uint64_t)src_size, C.d8, C.d_copies, C.d_ncopies, yslices);
+   }
+   ZH_TRY(hipEventRecord(C.ev[ZH_IEV_UZ_CHECKS], 0));
+   if (zh_check_launch(ZH_M_ZIP, C.s8, C.d8, room, C.d_inner, C.d_results, C.d_members, C.d_idx, C.nsmall, C.nlarge, C.spg, C.d_tables, C.d_dirents)) return -1;
+   ZH_TRY(hipEventRecord(C.ev[ZH_IEV_UZ_END], 0));
+   std::vector<zultra_hip_member_result_t> own;
+   if (!results) {
+      own.resize(n);
+      results = own.data();
+   }
+   ZH_TRY(hipMemcpy(results, C.d_members, (size_t)n * sizeof(zh_member_result_t), hipMemcpyDeviceToHost));
+   ZH_TRY(hipDeviceSynchronize());
+   ZH_TRY(hipGetLastError());
+   if (kernel_ms) {
+      kernel_ms[0] = zh_index_ms(C, true);
+      for (int i = 0; i < 4; i++) (void)hipEventElapsedTime(kernel_ms + 1 + i, C.ev[ZH_IEV_UZ_LOCALS + i], C.ev[ZH_IEV_UZ_LOCALS + i + 1]);
+   }
    C.order.reserve(n);
    for (uint32_t k = 0; k < n; k++)   // (as the index put them)
       if (items[k].dst_cap) C.order.push_back(k);

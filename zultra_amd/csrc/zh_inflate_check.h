@@ -9,6 +9,9 @@
 // the trailer does not fit in the item (the member is cut off); 15 (checksum); 16 (gzip ISIZE). `check` is the checksum COMPUTED over the output,
 // filled whenever the stream decoded.
 //
+// The ZIP form (zh_unzip.h) has no trailer: the expected CRC-32 and size come from the central directory's record (zh_zip_dirent_t), a stored entry counts as
+// decoded, and the order is 17 / 14 (zh_uz_locals), the inflate kernel's reason, 16 (out_size != size), 15 (CRC-32).
+//
 // The checksum follows zh_stitch.h's zh_crc32_blocks / zh_crc32_small: 256-byte slices, one per thread, aligned to the END of the item's output
 // (only slice 0 is short); the CRC byte table and the "append 256 zero bytes" operator in LDS; for Adler-32 the slice sums folded with the
 // `after * s1 + s2` weighting. What differs: lengths are 64-bit; the output starts at any byte address and nothing outside
@@ -32,6 +35,8 @@
 #define ZH_M_RAW 0u    // framing: ZULTRA_FLAG_ZLIB_FRAMING, ZULTRA_FLAG_GZIP_FRAMING (libzultra.h)
 #define ZH_M_ZLIB 1u
 #define ZH_M_GZIP 2u
+#define ZH_M_ZIP 3u    // an entry of a ZIP archive (zh_unzip.h): no trailer, the expected CRC-32 and size stand in the central directory
+#define ZH_M_UNSUPPORTED 17u   // (ZIP only)
 
 #define ZH_CK_THREADS 256
 #define ZH_CK_SLICE 256u                             // bytes per thread-slice
@@ -46,6 +51,13 @@ typedef struct zh_member_result_s {
    uint64_t out_size, src_used;
    uint32_t head_size, check;
 } zh_member_result_t;
+
+// zultra_hip_zip_dirent_t (include/zultra_hip.h): one record of a ZIP archive's central directory, as zh_unzip.h's index writes it
+typedef struct zh_zip_dirent_s {
+   uint64_t central_at, local_off, dst_off;   // the record's position in the source; the local header's in the archive; the sum of `size` in front of the record
+   uint32_t comp_size, size, crc32, name_len;
+   uint16_t method, flags, extra_len, comment_len;
+} zh_zip_dirent_t;
 
 #if defined(__HIPCC__) || defined(ZH_EMU)
 
@@ -195,6 +207,7 @@ struct zh_ck_item_t {
    zh_inflate_item_t it;
    zh_inflate_result_t in;
    uint32_t frame_reason, head;
+   uint32_t want;   // (ZIP: the CRC-32 the directory names)
    uint64_t n;   // bytes to sum: 0 unless the stream decoded
 };
 __device__ __forceinline__ zh_ck_item_t zh_ck_fetch(const zh_inflate_item_t *items, const zh_inflate_result_t *inner, const zh_member_result_t *results, uint32_t k, uint64_t dst_size) {
@@ -205,7 +218,37 @@ __device__ __forceinline__ zh_ck_item_t zh_ck_fetch(const zh_inflate_item_t *ite
    m.head = results[k].head_size;
    const bool decoded = m.frame_reason == 0 && m.in.reason == 0 && m.it.dst_off <= dst_size && m.it.dst_cap <= dst_size - m.it.dst_off;
    m.n = decoded ? (m.in.out_size < m.it.dst_cap ? m.in.out_size : m.it.dst_cap) : 0;   // (the inflate kernel never writes more than dst_cap)
+   m.want = 0;
    return m;
+}
+// ... of a ZIP entry: its range and what to expect from the dirent; a stored entry that zh_uz_locals has passed counts as decoded, `size` bytes out of comp_size
+// (zh_uz_copy has put them there); the inflate kernel's result is a deflated entry's only
+__device__ __forceinline__ zh_ck_item_t zh_ck_fetch_zip(const zh_zip_dirent_t *dirents, const zh_inflate_result_t *inner, const zh_member_result_t *results, uint32_t k, uint64_t dst_size) {
+   const zh_zip_dirent_t e = dirents[k];
+   zh_ck_item_t m;
+   m.it.src_off = 0;
+   m.it.src_size = e.comp_size;
+   m.it.dst_off = e.dst_off;
+   m.it.dst_cap = e.size;
+   m.frame_reason = results[k].reason;
+   m.head = results[k].head_size;
+   m.want = e.crc32;
+   if (e.method == 8)
+      m.in = inner[k];
+   else {
+      m.in.reason = 0;
+      m.in.blocks = 0;
+      m.in.out_size = e.size;
+      m.in.src_used = e.comp_size;
+   }
+   const bool decoded = m.frame_reason == 0 && m.in.reason == 0 && m.it.dst_off <= dst_size && m.it.dst_cap <= dst_size - m.it.dst_off;
+   m.n = decoded ? (m.in.out_size < m.it.dst_cap ? m.in.out_size : m.it.dst_cap) : 0;
+   return m;
+}
+template <uint32_t FRAMING>
+__device__ __forceinline__ zh_ck_item_t zh_ck_fetch_as(const zh_inflate_item_t *items, const zh_zip_dirent_t *dirents, const zh_inflate_result_t *inner, const zh_member_result_t *results, uint32_t k,
+                                                       uint64_t dst_size) {
+   return FRAMING == ZH_M_ZIP ? zh_ck_fetch_zip(dirents, inner, results, k, dst_size) : zh_ck_fetch(items, inner, results, k, dst_size);
 }
 
 // The final result of item k (one thread). sum: the finished CRC-32 / Adler-32 of its output.
@@ -217,7 +260,22 @@ __device__ __forceinline__ void zh_ck_finish(const zh_ck_item_t &m, const uint8_
    r.src_used = (uint64_t)m.head + m.in.src_used;
    r.head_size = m.head;
    r.check = 0;
-   if (m.frame_reason) {
+   if (FRAMING == ZH_M_ZIP) {   // 17 and 14 (zh_uz_locals); the inflate kernel's reason; 16, the size, before 15, the CRC-32: a short output fails both, and 16 says more
+      r.src_used = m.in.src_used;   // (the deflate bytes consumed: the header is no part of comp_size)
+      if (m.frame_reason) {
+         r.reason = m.frame_reason;
+         r.blocks = 0;
+         r.out_size = r.src_used = 0;
+         r.head_size = 0;
+      }
+      else if (m.in.reason)
+         r.reason = m.in.reason;
+      else {
+         r.check = sum;
+         r.reason = r.out_size != m.it.dst_cap ? ZH_M_BAD_ISIZE : sum != m.want ? ZH_M_BAD_CHECK : 0u;
+      }
+   }
+   else if (m.frame_reason) {
       r.reason = m.frame_reason;
       r.blocks = 0;
       r.out_size = r.src_used = 0;
@@ -252,21 +310,22 @@ __device__ __forceinline__ uint32_t zh_ck_adler(const uint32_t *asum, uint64_t n
 }
 
 // src / dst: the call's buffers (dst is only read). idx[0 .. nsmall): the items of the several-to-a-workgroup form, spg threads each;
-// idx[nsmall .. nsmall + nlarge): the others. tables: ZH_CK_TABLE_WORDS words (gzip; else not looked at).
+// idx[nsmall .. nsmall + nlarge): the others. tables: ZH_CK_TABLE_WORDS words (gzip and ZIP; else not looked at). dirents: ZIP only, in the place of items.
 template <uint32_t FRAMING>
 __global__ void __launch_bounds__(ZH_CK_THREADS)
 zh_check_members(const uint8_t *src, const uint8_t *dst, uint64_t dst_size, const zh_inflate_item_t *__restrict__ items, const zh_inflate_result_t *__restrict__ inner,
-                 zh_member_result_t *results, const uint32_t *__restrict__ idx, uint32_t nsmall, uint32_t nlarge, uint32_t spg, uint32_t small_blocks, const uint32_t *__restrict__ tables) {
+                 zh_member_result_t *results, const uint32_t *__restrict__ idx, uint32_t nsmall, uint32_t nlarge, uint32_t spg, uint32_t small_blocks, const uint32_t *__restrict__ tables,
+                 const zh_zip_dirent_t *__restrict__ dirents) {
    constexpr bool ADLER = FRAMING == ZH_M_ZLIB;
    const uint32_t tid = threadIdx.x;
    if (FRAMING == ZH_M_RAW) {   // nothing to sum: one thread per item puts the result together
       const uint32_t n = nsmall + nlarge;
       for (uint64_t k = (uint64_t)blockIdx.x * ZH_CK_THREADS + tid; k < n; k += (uint64_t)gridDim.x * ZH_CK_THREADS)
-         zh_ck_finish<FRAMING>(zh_ck_fetch(items, inner, results, (uint32_t)k, dst_size), src, 0u, results + k);
+         zh_ck_finish<FRAMING>(zh_ck_fetch(items, inner, results, (uint32_t)k, dst_size), src, 0u, results + k);   // (raw has no ZIP form)
       return;
    }
    __shared__ zh_ck_lds_t S;
-   if (FRAMING == ZH_M_GZIP) {
+   if (FRAMING == ZH_M_GZIP || FRAMING == ZH_M_ZIP) {
       for (uint32_t k = tid; k < ZH_CK_TABLE_WORDS; k += ZH_CK_THREADS) S.T[k] = tables[k];
    }
    if (blockIdx.x < small_blocks) {
@@ -284,7 +343,7 @@ zh_check_members(const uint8_t *src, const uint8_t *dst, uint64_t dst_size, cons
          uint64_t nslices = 0;
          if (live) {
             k = idx[at];
-            m = zh_ck_fetch(items, inner, results, k, dst_size);
+            m = zh_ck_fetch_as<FRAMING>(items, dirents, inner, results, k, dst_size);
             nslices = (m.n + ZH_CK_SLICE - 1) / ZH_CK_SLICE;
             if (nslices > spg) m.n = nslices = 0;   // (dst_cap <= spg * ZH_CK_SLICE, as the host chose spg: never)
             const uint32_t pad = spg - (uint32_t)nslices;   // empty slots in front: their state 0 stays 0 under the operator
@@ -311,7 +370,7 @@ zh_check_members(const uint8_t *src, const uint8_t *dst, uint64_t dst_size, cons
    const uint32_t large_blocks = gridDim.x - small_blocks;
    for (uint32_t at = blockIdx.x - small_blocks; at < nlarge; at += large_blocks) {
       const uint32_t k = idx[nsmall + at];
-      const zh_ck_item_t m = zh_ck_fetch(items, inner, results, k, dst_size);
+      const zh_ck_item_t m = zh_ck_fetch_as<FRAMING>(items, dirents, inner, results, k, dst_size);
       const uint64_t nslices = (m.n + ZH_CK_SLICE - 1) / ZH_CK_SLICE;
       const uint64_t nrounds = (nslices + ZH_CK_THREADS - 1) / ZH_CK_THREADS;
       const uint64_t pad = nrounds * ZH_CK_THREADS - nslices;

@@ -22,6 +22,8 @@
 //                  chain jumps over stay unused. The pass ends at a stop and writes the totals.
 //   zh_ix_items    one lane per used tile: the walk from the tile's entry once more, items[base + i] written.
 //
+// The walk, the scan and the three passes are templates over a RECORD FORMAT and a range [D0, D1) of the source (here: the whole source); zh_unzip.h walks a ZIP
+// archive's central directory with them.
 // Dependent loads in a row: about T / (mean member) in the first and the last pass, S / T in the middle one.
 // Every result equals the serial walk bit for bit for ANY bytes in src, and no load touches a byte outside src[0 .. S): zh_ix_probe orders its
 // loads behind the comparisons that bound them.
@@ -79,46 +81,61 @@ __device__ __forceinline__ uint32_t zh_ix_probe(const uint8_t *src, uint64_t S, 
    return 1u;
 }
 
-// The chain from p while p < end (one lane). ITEMS: item base + i is written for member i of the walk, its output at out_base + the ISIZEs before it.
+// The gzip index as a record format of the tiled chain walk below. A FORMAT F names: item_t, what the last pass writes per record; SIG / SIG_MASK, the
+// little-endian bytes a record starts with, and BEHIND, how many bytes of them may lie behind a lane's 16-byte window (their count less one); probe(src, D1,
+// p, &len, &val) — what starts at p <= D1, the end of the chain's range: ZH_IX_MEMBER with the record's length and the value the index sums, or a stop kind,
+// every load inside [p, D1) —; and put(item, src, p, len, sum, val), item i of a walk, `sum` the values in front of it. zh_unzip.h has the second format.
+struct zh_ix_gzip_t {
+   typedef zh_inflate_item_t item_t;
+   static constexpr uint32_t SIG = 0x088b1fu, SIG_MASK = 0xFFFFFFu, BEHIND = 2u;
+   static __device__ __forceinline__ uint32_t probe(const uint8_t *src, uint64_t D1, uint64_t p, uint32_t *len, uint32_t *val) { return zh_ix_probe(src, D1, p, len, val); }
+   static __device__ __forceinline__ void put(zh_inflate_item_t *item, const uint8_t *src, uint64_t p, uint32_t len, uint64_t sum, uint32_t val) {
+      zh_inflate_item_t it;
+      it.src_off = p;
+      it.src_size = len;
+      it.dst_off = sum;
+      it.dst_cap = val;
+      *item = it;
+   }
+};
+
+// The chain from p while p < end (one lane), in src[.. D1). ITEMS: item base + i is written for record i of the walk, with out_base + the values before it.
 struct zh_ix_walk_t {
    uint64_t exit, out_sum;
    uint32_t members, stop;
 };
-template <bool ITEMS>
-__device__ __forceinline__ zh_ix_walk_t zh_ix_walk(const uint8_t *src, uint64_t S, uint64_t p, uint64_t end, zh_inflate_item_t *items, uint64_t out_base) {
+template <class F, bool ITEMS>
+__device__ __forceinline__ zh_ix_walk_t zh_ix_walk(const uint8_t *src, uint64_t D1, uint64_t p, uint64_t end, typename F::item_t *items, uint64_t out_base) {
    zh_ix_walk_t w;
    w.out_sum = 0;
    w.members = 0;
    w.stop = ZH_IX_MEMBER;
    while (p < end) {
-      uint32_t len = 0, isize = 0;
-      const uint32_t kind = zh_ix_probe(src, S, p, &len, &isize);
+      uint32_t len = 0, val = 0;
+      const uint32_t kind = F::probe(src, D1, p, &len, &val);
       if (kind != ZH_IX_MEMBER) {
          w.stop = kind;
          break;
       }
-      if (ITEMS) {
-         zh_inflate_item_t it;
-         it.src_off = p;
-         it.src_size = len;
-         it.dst_off = out_base + w.out_sum;
-         it.dst_cap = isize;
-         items[w.members] = it;
-      }
-      w.members++;   // (a tile holds fewer than 2^32 members: T < 2^32 * 20 bytes, as the host has seen to)
-      w.out_sum += isize;
+      if (ITEMS) F::put(items + w.members, src, p, len, out_base + w.out_sum, val);
+      w.members++;   // (a tile holds fewer than 2^32 records: T < 2^32 * 20 bytes, as the host has seen to)
+      w.out_sum += val;
       p += len;
    }
    w.exit = p;
    return w;
 }
 
-__device__ __forceinline__ uint64_t zh_ix_tile_end(uint64_t k, uint64_t T, uint64_t S) {
-   return (S - k * T > T) ? (k + 1u) * T : S + 1u;   // (the last tile's walk goes on to p == S, which is a stop)
+// Tile k of the chain's range [D0, D1) is [D0 + k T, D0 + (k + 1) T).
+__device__ __forceinline__ uint64_t zh_ix_tile_end(uint64_t k, uint64_t T, uint64_t D0, uint64_t D1) {
+   const uint64_t from = D0 + k * T;
+   return (D1 - from > T) ? from + T : D1 + 1u;   // (the last tile's walk goes on to p == D1, which is a stop)
 }
 
-// The first position in [from, to) that starts a hinted member, or ZH_IX_NOWHERE: the whole wave, wave-uniform result. to <= S.
-__device__ __forceinline__ uint64_t zh_ix_scan(const uint8_t *src, uint64_t S, uint64_t from, uint64_t to) {
+// The first position in [from, to) that starts a record, or ZH_IX_NOWHERE: the whole wave, wave-uniform result. to <= D1 <= S, the size of the source: no
+// load touches a byte outside src[0 .. S).
+template <class F>
+__device__ __forceinline__ uint64_t zh_ix_scan(const uint8_t *src, uint64_t S, uint64_t D1, uint64_t from, uint64_t to) {
    const uint32_t lane = zh_lane();
    const int64_t lead = (int64_t)((uintptr_t)(src + from) & 15u);
    // in round `cb` lane l looks at the sixteen positions [cb + 16 l, cb + 16 l + 16): the window is 16-byte aligned in memory
@@ -139,12 +156,12 @@ __device__ __forceinline__ uint64_t zh_ix_scan(const uint8_t *src, uint64_t S, u
             if (at >= 0 && (uint64_t)at < S) d[j >> 2] |= (uint32_t)src[at] << (8 * (j & 3));
          }
       }
-      // the two bytes behind the window: the next lane's first ones; lane 63 loads its own
+      // the BEHIND bytes behind the window: the next lane's first ones; lane 63 loads its own
       d[4] = zh_shfl(d[0], (int)((lane + 1u) & 63u));
       if (lane == 63u) {
          d[4] = 0;
 #pragma unroll
-         for (int j = 0; j < 2; j++) {
+         for (int j = 0; j < (int)F::BEHIND; j++) {
             const int64_t at = w + 16 + j;
             if (at >= 0 && (uint64_t)at < S) d[4] |= (uint32_t)src[at] << (8 * j);
          }
@@ -152,15 +169,15 @@ __device__ __forceinline__ uint64_t zh_ix_scan(const uint8_t *src, uint64_t S, u
       uint32_t mask = 0;
 #pragma unroll
       for (int i = 0; i < 16; i++) {
-         const uint32_t three = (i & 3) ? zh_funnel(d[(i >> 2) + 1], d[i >> 2], 8u * (i & 3)) : d[i >> 2];
-         if ((three & 0xFFFFFFu) == 0x088b1fu) mask |= 1u << i;
+         const uint32_t sig = (i & 3) ? zh_funnel(d[(i >> 2) + 1], d[i >> 2], 8u * (i & 3)) : d[i >> 2];
+         if ((sig & F::SIG_MASK) == F::SIG) mask |= 1u << i;
       }
       uint64_t hit = ZH_IX_NOWHERE;
       while (mask) {   // (rare: the lane's candidates in order, each probed in full)
          const int64_t at = w + (__ffs((int)mask) - 1);
          mask &= mask - 1u;
-         uint32_t len, isize;
-         if (at >= (int64_t)from && at < (int64_t)to && zh_ix_probe(src, S, (uint64_t)at, &len, &isize) == ZH_IX_MEMBER) {
+         uint32_t len, val;
+         if (at >= (int64_t)from && at < (int64_t)to && F::probe(src, D1, (uint64_t)at, &len, &val) == ZH_IX_MEMBER) {
             hit = (uint64_t)at;
             break;
          }
@@ -175,12 +192,13 @@ __device__ __forceinline__ uint64_t zh_ix_scan(const uint8_t *src, uint64_t S, u
    return ZH_IX_NOWHERE;
 }
 
+// The three passes over the chain's range [D0, D1) of src[0 .. S), for any format; the kernels below and zh_unzip.h's are these with a format named.
 // One wave per tile, striding.
-__global__ void __launch_bounds__(ZH_IX_THREADS)
-zh_ix_tiles(const uint8_t *src, uint64_t S, uint64_t T, uint64_t ntiles, zh_ix_tile_t *__restrict__ tiles) {
+template <class F>
+__device__ __forceinline__ void zh_ix_tiles_pass(const uint8_t *src, uint64_t S, uint64_t D0, uint64_t D1, uint64_t T, uint64_t ntiles, zh_ix_tile_t *__restrict__ tiles) {
    for (uint64_t k = blockIdx.x; k < ntiles; k += gridDim.x) {
-      const uint64_t from = k * T, to = (S - from > T) ? from + T : S;
-      const uint64_t guess = k == 0 ? 0ull : zh_ix_scan(src, S, from, to);
+      const uint64_t from = D0 + k * T, to = (D1 - from > T) ? from + T : D1;
+      const uint64_t guess = k == 0 ? D0 : zh_ix_scan<F>(src, S, D1, from, to);
       if (zh_lane() == 0) {
          zh_ix_tile_t r;
          r.guess = guess;
@@ -191,7 +209,7 @@ zh_ix_tiles(const uint8_t *src, uint64_t S, uint64_t T, uint64_t ntiles, zh_ix_t
          w.out_sum = 0;
          w.members = 0;
          w.stop = ZH_IX_MEMBER;
-         if (guess != ZH_IX_NOWHERE) w = zh_ix_walk<false>(src, S, guess, zh_ix_tile_end(k, T, S), NULL, 0);
+         if (guess != ZH_IX_NOWHERE) w = zh_ix_walk<F, false>(src, D1, guess, zh_ix_tile_end(k, T, D0, D1), NULL, 0);
          r.exit = w.exit;
          r.out_sum = w.out_sum;
          r.members = w.members;
@@ -201,21 +219,21 @@ zh_ix_tiles(const uint8_t *src, uint64_t S, uint64_t T, uint64_t ntiles, zh_ix_t
    }
 }
 
-// One wave, lane 0 working: the chain of tiles from position 0.
-__global__ void __launch_bounds__(ZH_IX_THREADS)
-zh_ix_resolve(const uint8_t *src, uint64_t S, uint64_t T, uint64_t ntiles, zh_ix_tile_t *tiles, zh_ix_totals_t *totals) {
+// One wave, lane 0 working: the chain of tiles from position D0.
+template <class F>
+__device__ __forceinline__ void zh_ix_resolve_pass(const uint8_t *src, uint64_t D0, uint64_t D1, uint64_t T, uint64_t ntiles, zh_ix_tile_t *tiles, zh_ix_totals_t *totals) {
    if (blockIdx.x != 0 || threadIdx.x != 0) return;
    zh_ix_totals_t t;
    t.members = t.out_size = t.tiles = t.tiles_rewalked = 0;
    t.stop = 0;
    t.pad = 0;
-   uint64_t e = 0;
+   uint64_t e = D0;
    for (;;) {
-      if (e >= S) break;   // (e == S: the file is a complete chain; a walk never passes S)
-      const uint64_t k = e / T;   // (< ntiles, as e < S)
+      if (e >= D1) break;   // (e == D1: the range is a complete chain; a walk never passes D1)
+      const uint64_t k = (e - D0) / T;   // (< ntiles, as e < D1)
       zh_ix_tile_t r = tiles[k];
       if (r.guess != e) {
-         const zh_ix_walk_t w = zh_ix_walk<false>(src, S, e, zh_ix_tile_end(k, T, S), NULL, 0);
+         const zh_ix_walk_t w = zh_ix_walk<F, false>(src, D1, e, zh_ix_tile_end(k, T, D0, D1), NULL, 0);
          r.exit = w.exit;
          r.out_sum = w.out_sum;
          r.members = w.members;
@@ -230,7 +248,7 @@ zh_ix_resolve(const uint8_t *src, uint64_t S, uint64_t T, uint64_t ntiles, zh_ix
       t.members += r.members;
       t.out_size += r.out_sum;
       t.tiles++;
-      e = r.exit;   // (> entry unless the walk stopped at once: every member is at least 20 bytes long)
+      e = r.exit;   // (> entry unless the walk stopped at once: every record is at least 20 bytes long)
       if (r.stop != ZH_IX_MEMBER) {
          t.stop = r.stop;
          break;
@@ -241,11 +259,25 @@ zh_ix_resolve(const uint8_t *src, uint64_t S, uint64_t T, uint64_t ntiles, zh_ix
 }
 
 // One lane per tile the chain entered: its items, items[member_base ..).
-__global__ void __launch_bounds__(ZH_IX_THREADS)
-zh_ix_items(const uint8_t *src, uint64_t S, uint64_t T, uint64_t ntiles, const zh_ix_tile_t *__restrict__ tiles, zh_inflate_item_t *__restrict__ items) {
+template <class F>
+__device__ __forceinline__ void zh_ix_items_pass(const uint8_t *src, uint64_t D0, uint64_t D1, uint64_t T, uint64_t ntiles, const zh_ix_tile_t *__restrict__ tiles, typename F::item_t *__restrict__ items) {
    for (uint64_t k = (uint64_t)blockIdx.x * ZH_IX_THREADS + threadIdx.x; k < ntiles; k += (uint64_t)gridDim.x * ZH_IX_THREADS) {
       const zh_ix_tile_t r = tiles[k];
-      if (r.used && r.members) (void)zh_ix_walk<true>(src, S, r.entry, zh_ix_tile_end(k, T, S), items + r.member_base, r.out_base);
+      if (r.used && r.members) (void)zh_ix_walk<F, true>(src, D1, r.entry, zh_ix_tile_end(k, T, D0, D1), items + r.member_base, r.out_base);
    }
+}
+
+// The gzip index: the chain's range is the whole source.
+__global__ void __launch_bounds__(ZH_IX_THREADS)
+zh_ix_tiles(const uint8_t *src, uint64_t S, uint64_t T, uint64_t ntiles, zh_ix_tile_t *__restrict__ tiles) {
+   zh_ix_tiles_pass<zh_ix_gzip_t>(src, S, 0, S, T, ntiles, tiles);
+}
+__global__ void __launch_bounds__(ZH_IX_THREADS)
+zh_ix_resolve(const uint8_t *src, uint64_t S, uint64_t T, uint64_t ntiles, zh_ix_tile_t *tiles, zh_ix_totals_t *totals) {
+   zh_ix_resolve_pass<zh_ix_gzip_t>(src, 0, S, T, ntiles, tiles, totals);
+}
+__global__ void __launch_bounds__(ZH_IX_THREADS)
+zh_ix_items(const uint8_t *src, uint64_t S, uint64_t T, uint64_t ntiles, const zh_ix_tile_t *__restrict__ tiles, zh_inflate_item_t *__restrict__ items) {
+   zh_ix_items_pass<zh_ix_gzip_t>(src, 0, S, T, ntiles, tiles, items);
 }
 #endif

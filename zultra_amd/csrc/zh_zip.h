@@ -13,6 +13,7 @@
 // records. No byte has two writers, nothing is read back, and the two kernels need no order between them.
 // An empty entry (a zero-length file or a directory) has no max-block: method 0, sizes 0, CRC 0, version needed 10.
 #pragma once
+#include "zh_copy.h"
 #include "zh_frame.h"
 
 #define ZH_ZIP_EMPTY 0xFFFFFFFFu    // entry_block[i]: no max-block
@@ -127,10 +128,7 @@ zh_zip_records(zh_zip_entry_t *entries, const uint64_t *__restrict__ src_off, co
 // chunks, where workgroup g is x = g / yslices along the entries and y = g % yslices along the slices (a one-dimensional grid of a multiple of yslices workgroups:
 // the host sizes yslices by the largest input of the batch, it needs no count from the device). An entry of 2 MiB is 256 slices.
 #define ZH_ZIP_COPY_THREADS 256
-#define ZH_ZIP_SLICE_CHUNKS 512u   // 8 KiB: eight stores a lane
-#define ZH_ZIP_UNROLL 2u
 #define ZH_ZIP_MAX_YSLICES 32u
-__device__ __forceinline__ uint32_t zh_zip_shift(uint32_t lo, uint32_t hi, uint32_t sh) { return sh ? (lo >> sh) | (hi << (32u - sh)) : lo; }   // (sh = 0: no shift by 32)
 __global__ void __launch_bounds__(ZH_ZIP_COPY_THREADS)
 zh_zip_copy(const zh_zip_entry_t *__restrict__ entries, const uint64_t *__restrict__ src_off, uint32_t n, uint64_t base_off, uint32_t yslices, const uint8_t *__restrict__ stream,
             const zh_zip_report_t *__restrict__ report, uint8_t *out) {
@@ -149,41 +147,9 @@ zh_zip_copy(const zh_zip_entry_t *__restrict__ entries, const uint64_t *__restri
          const uint64_t d = lane < 16 ? d0 + lane : a1 + (lane - 16);
          if (d < (lane < 16 ? a0 : d1)) out[d] = stream[d + delta];
       }
-      const uint32_t nchunks = (uint32_t)((a1 - a0) >> 4), bs = (uint32_t)(a0 + delta) & 15u, sh = (bs & 3u) * 8u;
-      for (uint32_t s = y; (uint64_t)s * ZH_ZIP_SLICE_CHUNKS < nchunks; s += yslices) {
-         const uint32_t end = min(nchunks, (s + 1) * ZH_ZIP_SLICE_CHUNKS);
-         for (uint32_t k0 = s * ZH_ZIP_SLICE_CHUNKS + lane; k0 < end; k0 += 64 * ZH_ZIP_UNROLL) {
-            // ZH_ZIP_UNROLL chunks a lane and round, all their loads in flight before the first store. Aligned loads: the 16 bytes that hold the chunk's first source
-            // byte and, where the source is not aligned like the destination, the 16 behind them. They may reach up to 15 bytes in front of the stream and up to 15
-            // behind its end — inside the stream buffer, which starts aligned and has 16 bytes of slack.
-            uint4 A[ZH_ZIP_UNROLL], B[ZH_ZIP_UNROLL];
-#pragma unroll
-            for (uint32_t u = 0; u < ZH_ZIP_UNROLL; u++) {
-               const uint4 *p = (const uint4 *)(stream + ((a0 + (uint64_t)16 * (k0 + 64 * u) + delta) & mask));
-               A[u] = B[u] = make_uint4(0, 0, 0, 0);
-               if (k0 + 64 * u < end) {
-                  A[u] = p[0];
-                  if (bs) B[u] = p[1];
-               }
-            }
-#pragma unroll
-            for (uint32_t u = 0; u < ZH_ZIP_UNROLL; u++) {
-               const uint4 a = A[u], b = B[u];
-               uint4 r = a;
-               if (bs) {
-                  uint32_t v0, v1, v2, v3, v4;
-                  switch (bs >> 2) {
-                  case 0: v0 = a.x, v1 = a.y, v2 = a.z, v3 = a.w, v4 = b.x; break;
-                  case 1: v0 = a.y, v1 = a.z, v2 = a.w, v3 = b.x, v4 = b.y; break;
-                  case 2: v0 = a.z, v1 = a.w, v2 = b.x, v3 = b.y, v4 = b.z; break;
-                  default: v0 = a.w, v1 = b.x, v2 = b.y, v3 = b.z, v4 = b.w; break;
-                  }
-                  r = make_uint4(zh_zip_shift(v0, v1, sh), zh_zip_shift(v1, v2, sh), zh_zip_shift(v2, v3, sh), zh_zip_shift(v3, v4, sh));
-               }
-               if (k0 + 64 * u < end) *(uint4 *)(out + a0 + (uint64_t)16 * (k0 + 64 * u)) = r;
-            }
-         }
-      }
+      // the interior (zh_copy.h). Its aligned loads may reach up to 15 bytes in front of the stream and up to 15 behind its end — inside the stream buffer, which
+      // starts aligned and has 16 bytes of slack.
+      zh_copy_chunks(out + a0, stream + (a0 + delta), (uint32_t)((a1 - a0) >> 4), y, yslices, lane);
    }
 }
 #endif

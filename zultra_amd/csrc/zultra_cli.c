@@ -11,7 +11,12 @@
  *    zultra_amd_cli -x -m [-f gzip] [-d <device>] [-v] <infile> <outfile>
  *    zultra_amd_cli -f bgzf [-b <block size>] [-d <device>] [-c] [-v] <infile> <outfile>
  *    zultra_amd_cli -a <archive.zip> [-d <device>] [-c] [-v] <file>...
+ *    zultra_amd_cli -x -a <archive.zip> [-d <device>] [-v] <outdir>
  *
+ * -x -a: unzip(1) — the archive (this tool's, zip(1)'s, Python's zipfile's: stored and deflated entries) is listed, then decoded on the device
+ *     (zultra_memory_decompress_zip: directory index, local headers, inflate / copy and the CRC-32 checks), and every entry written under <outdir>, directories
+ *     made as needed; an entry whose name ends in '/' is a directory. Before anything is written the whole archive is refused where a name is empty or absolute
+ *     or holds a ".." component, a backslash or a NUL byte. With -v one line per entry, and the entries, the index's tiles and the tiles walked again.
  * -a: a ZIP archive of the files named, every file an entry under its name as given, headers and central directory written on the device
  *     (zultra_memory_compress_zip). A file is one max-block: at most 2 MiB; an empty file is an empty entry. No dictionary.
  * -f bgzf: bgzip(1) — <infile> in blocks of -b bytes (default and at most 65280), every block a BGZF member written on the device, and BGZF's end marker
@@ -31,6 +36,8 @@
 #include <stdlib.h>
 #include <string.h>
 #include <time.h>
+#include <errno.h>
+#include <sys/stat.h>
 
 #include "../../include/libzultra.h"
 #include "../../include/zultra_hip.h"
@@ -159,6 +166,122 @@ static int write_zip(const char *archive, char **files, int n, int verbose, int 
    return rc;
 }
 
+/* mkdir -p of `path` (a directory), or of the directories in front of its last component (a file) */
+static int make_dirs(char *path, int is_dir) {
+   for (char *p = path + 1;; p++) {
+      if (*p == '/' || (*p == 0 && is_dir)) {
+         const char keep = *p;
+         *p = 0;
+         const int bad = mkdir(path, 0777) != 0 && errno != EEXIST;
+         *p = keep;
+         if (bad) return -1;
+      }
+      if (*p == 0) return 0;
+   }
+}
+
+/* a name that stays under the directory it is unpacked into */
+static int name_is_safe(const unsigned char *name, size_t n) {
+   if (n == 0 || name[0] == '/') return 0;
+   for (size_t i = 0, start = 0; i <= n; i++) {
+      if (i < n && (name[i] == 0 || name[i] == '\\')) return 0;
+      if (i == n || name[i] == '/') {
+         if (i - start == 2 && name[start] == '.' && name[start + 1] == '.') return 0;
+         start = i + 1;
+      }
+   }
+   return 1;
+}
+
+/* -x -a: the archive through zultra_memory_decompress_zip, listed first, then decoded; its entries written under outdir */
+static int extract_zip(const char *archive, const char *outdir, int verbose, int device) {
+   FILE *fin = fopen(archive, "rb");
+   if (!fin) {
+      fprintf(stderr, "error opening '%s' for reading\n", archive);
+      return 100;
+   }
+   size_t n = 0, cap = (size_t)1 << 20;
+   unsigned char *in = (unsigned char *)malloc(cap), *out = NULL;
+   for (size_t got; in && (got = fread(in + n, 1, cap - n, fin)) > 0;) {
+      n += got;
+      if (n == cap) {
+         unsigned char *more = (unsigned char *)realloc(in, cap *= 2);
+         if (!more) free(in);
+         in = more;
+      }
+   }
+   fclose(fin);
+   zultra_zip_end_t end;
+   zultra_zip_info_t *info = NULL;
+   char *path = NULL;
+   int rc = 100;
+   const size_t tail = n < 65535 + 22 + 20 + 56 ? n : 65535 + 22 + 20 + 56;
+   if (!in)
+      fprintf(stderr, "out of memory\n");
+   else if (zultra_zip_find_end(in + n - tail, tail, n, &end) != 0 || end.nEntries > n / 46)
+      fprintf(stderr, "'%s' is no ZIP archive (no end record, or one of several disks)\n", archive);
+   else {
+      const size_t entries = (size_t)end.nEntries;
+      size_t listed = 0, longest = 0;
+      info = (zultra_zip_info_t *)calloc(entries ? entries : 1, sizeof(*info));
+      const double t0 = now_s();
+      const size_t total = info ? zultra_memory_decompress_zip(in, n, NULL, 0, info, entries, &listed) : (size_t)-1;
+      int safe = total != (size_t)-1;
+      if (!safe) fprintf(stderr, "the central directory of '%s' does not read (damaged, or no HIP device: this library has no CPU path)\n", archive);
+      for (size_t i = 0; safe && i < entries; i++) {
+         if (!name_is_safe(in + info[i].nNameAt, info[i].nNameLen)) {
+            fprintf(stderr, "entry %llu has a name that is empty, absolute or holds '..', a backslash or a NUL byte: nothing is unpacked\n", (unsigned long long)i);
+            safe = 0;
+         }
+         if (info[i].nNameLen > longest) longest = info[i].nNameLen;
+      }
+      out = safe ? (unsigned char *)malloc(total ? total : 1) : NULL;
+      path = safe ? (char *)malloc(strlen(outdir) + longest + 2) : NULL;
+      if (safe && (!out || !path)) fprintf(stderr, "out of memory\n");
+      if (out && path) {
+         const size_t size = zultra_memory_decompress_zip(in, n, out, total, info, entries, &listed);
+         const double dt = now_s() - t0;
+         if (size == (size_t)-1) {
+            fprintf(stderr, "decompression error:");
+            for (size_t i = 0; i < entries; i++)
+               if (info[i].nStatus) fprintf(stderr, " entry %llu '%.*s' reason %u;", (unsigned long long)i, (int)info[i].nNameLen, (const char *)in + info[i].nNameAt, info[i].nStatus);
+            fprintf(stderr, " (reasons: include/zultra_hip.h, zultra_hip_unzip) nothing is unpacked\n");
+         }
+         else {
+            rc = 0;
+            for (size_t i = 0; i < entries && !rc; i++) {
+               const int is_dir = in[info[i].nNameAt + info[i].nNameLen - 1] == '/';
+               sprintf(path, "%s/%.*s", outdir, (int)info[i].nNameLen, (const char *)in + info[i].nNameAt);
+               FILE *f = make_dirs(path, is_dir) == 0 && !is_dir ? fopen(path, "wb") : NULL;
+               if (!is_dir && (!f || fwrite(out + info[i].nOutOff, 1, info[i].nSize, f) != info[i].nSize)) {
+                  fprintf(stderr, "error writing '%s'\n", path);
+                  rc = 100;
+               }
+               if (f) fclose(f);
+               if (verbose && !rc)
+                  fprintf(stdout, "%10u -> %10u  %s  %08x  %.*s\n", info[i].nCompSize, info[i].nSize, info[i].nMethod == 8 ? "deflated" : "stored  ", info[i].nCrc32, (int)info[i].nNameLen,
+                          (const char *)in + info[i].nNameAt);
+            }
+            if (!entries && make_dirs(strcpy(path, outdir), 1) != 0) rc = 100;
+         }
+         if (verbose && !rc) {
+            zultra_hip_zip_index_result_t ix;
+            memset(&ix, 0, sizeof(ix));
+            /* zultra_memory_decompress_zip does not hand its index result on, so the counts come from an index of the directory's bytes alone, as a source
+             * of their own: the tiles are cut from the directory's start, so they are the same ones, and only the directory is uploaded again */
+            if (end.nCentralSize) (void)zultra_hip_zip_index(device, in + end.nPrefix + end.nCentralOff, (size_t)end.nCentralSize, 0, 0, end.nCentralSize, NULL, 0, &ix, NULL);
+            fprintf(stdout, "%llu entries, %llu -> %llu bytes, %.1f MB/s; the directory index: %u tiles, %u rewalked\n", (unsigned long long)entries, (unsigned long long)n, (unsigned long long)size,
+                    dt > 0 ? (double)size / dt / 1e6 : 0.0, ix.tiles, ix.tiles_rewalked);
+         }
+      }
+   }
+   free(in);
+   free(out);
+   free(info);
+   free(path);
+   return rc;
+}
+
 /* -x: the whole file through zultra_memory_decompress. The output size is not known in advance (gzip's ISIZE is a hint, modulo 2^32): the buffer
  * grows until the call succeeds or the bound of the format is passed (a deflate stream expands at most 1032 : 1). */
 static int extract(FILE *fin, FILE *fout, unsigned flags, int verbose, const void *dict, int dict_size, int members, int device) {
@@ -252,14 +375,16 @@ int main(int argc, char **argv) {
       fprintf(stderr, "-b %u: a BGZF block holds at most %u bytes of input\n", block, ZULTRA_HIP_BGZF_BLOCK);
       return 100;
    }
-   if (archive ? (argc - i < 1 || do_extract || bgzf || dict_name) : argc - i != 2 || chunk == 0 || (members && (!do_extract || flags != ZULTRA_FLAG_GZIP_FRAMING || dict_name)) || (bgzf && !do_extract && dict_name)) {
+   if (archive ? ((do_extract ? argc - i != 1 || members || verify : argc - i < 1) || bgzf || dict_name) : argc - i != 2 || chunk == 0 || (members && (!do_extract || flags != ZULTRA_FLAG_GZIP_FRAMING || dict_name)) || (bgzf && !do_extract && dict_name)) {
       fprintf(stderr, "usage: %s [-b <max block size>] [-f gzip|zlib|raw] [-k <chunk KiB>] [-d <device>] [-D <dictionary>] [-c] [-v] <infile> <outfile>\n"
                       "       %s -x [-f gzip|zlib|raw] [-d <device>] [-D <dictionary>] [-v] <infile> <outfile>\n"
                       "       %s -x -m [-f gzip] [-d <device>] [-v] <infile> <outfile>   (any number of gzip members: BGZF, pigz -i, cat a.gz b.gz)\n"
                       "       %s -f bgzf [-b <block size, at most 65280>] [-d <device>] [-c] [-v] <infile> <outfile>   (BGZF members and the end marker)\n"
-                      "       %s -a <archive.zip> [-d <device>] [-c] [-v] <file>...   (a ZIP archive: every file, of at most 2 MiB, an entry under its name)\n", argv[0], argv[0], argv[0], argv[0], argv[0]);
+                      "       %s -a <archive.zip> [-d <device>] [-c] [-v] <file>...   (a ZIP archive: every file, of at most 2 MiB, an entry under its name)\n"
+                      "       %s -x -a <archive.zip> [-d <device>] [-v] <outdir>   (unpack a ZIP archive: stored and deflated entries, checked on the device)\n", argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
       return 100;
    }
+   if (archive && do_extract) return extract_zip(archive, argv[i], verbose, device);
    if (archive) return write_zip(archive, argv + i, argc - i, verbose, verify);
    void *dict = NULL;
    int dict_size = 0;

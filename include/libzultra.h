@@ -170,6 +170,23 @@ size_t zultra_memory_decompress_batch(const unsigned char *pIn, size_t nIn, cons
  * skips the two bytes). No dictionary. */
 size_t zultra_memory_decompress_members(const unsigned char *pIn, size_t nIn, unsigned char *pOut, size_t nMaxOut, size_t *pnMembers /* may be NULL */);
 
+/* A byte range of a BGZF file, and bgzip's `.gzi` index of one (include/zultra_hip.h: zultra_hip_inflate_range).
+ * The index: le64 N, then N pairs le64 compressed offset, le64 uncompressed offset, each pair the start of a member. zultra_memory_index_gzi writes one pair
+ * for every indexed member of pIn but the first, in order, empty members included (byte equality with bgzip's own file is not claimed; the reader below takes
+ * any list of member starts, as bgzip's are). It succeeds only where the whole input is a chain of BGZF members (stop kind 0). pGzi == NULL returns the size
+ * needed. Returns the bytes written, or (size_t)-1: any other stop, nMaxGzi too small, bad arguments, no device.
+ * zultra_memory_decompress_range writes bytes [nFirst, nFirst + nBytes) of the concatenated output to pOut and returns their count: short at the end of the
+ * file, 0 behind it. Only the members that hold those bytes are inflated and checked. Without an index (pGzi NULL) the whole input is uploaded and indexed on
+ * the device; (size_t)-1 if a decoded member fails, the range exceeds nMaxOut, or the index stops with kind 1..3 and nFirst + nBytes reaches past the indexed
+ * prefix (the call cannot know what follows). With an index, only the window pIn[c0 .. c1) is uploaded: (c0, u0) the last pair with u <= nFirst — (0, 0) in
+ * front of the first —, (c1, u1) the first pair with u >= nFirst + nBytes, c1 the end of the input without one; bytes of pIn outside the window are never
+ * read. The index is validated — nGzi == 8 + 16 N, compressed offsets strictly increasing, above 0 and below nIn, uncompressed offsets not decreasing — and so
+ * is what it says of the window: a member starts at the window's byte 0, the chain ends exactly at c1, and where c1 came from a pair the window's output is
+ * u1 - u0 bytes. Anything else is (size_t)-1, an index that lies included. */
+size_t zultra_memory_index_gzi(const unsigned char *pIn, size_t nIn, unsigned char *pGzi /* may be NULL */, size_t nMaxGzi);
+size_t zultra_memory_decompress_range(const unsigned char *pIn, size_t nIn, unsigned long long nFirst, size_t nBytes,
+                                      unsigned char *pOut, size_t nMaxOut, const unsigned char *pGzi /* may be NULL */, size_t nGzi);
+
 /* bgzip(1): pIn cut into blocks of nBlockSize bytes (0 = 65280, bgzip's; at most 65280; the last block is shorter), every block an independent BGZF
  * member — a gzip member whose `BC` extra subfield holds its size, at most 65536 bytes —, and BGZF's 28-byte empty member behind the last: the container
  * zultra_memory_decompress_members and zultra_hip_inflate_file read in parallel. The blocks are compressed as max-blocks without history, in as many

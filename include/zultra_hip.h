@@ -349,6 +349,37 @@ int zultra_hip_inflate_file(int device, const void *src, size_t src_size, int sr
                             float *kernel_ms /* [4]: index, frame, inflate, check; may be NULL */);
 
 /*
+ * A BYTE RANGE of such a file: only the members that cover it are inflated. U is the concatenation of the outputs of the indexed members (the
+ * chain above from p = 0, with any stop kind), F = |U| the sum of their ISIZEs. The range is clipped to U: lo = min(first, F), hi = min(first + nbytes, F), the
+ * sum saturating at 2^64 - 1; out_size = hi - lo and dst[0 .. out_size) = U[lo .. hi). With out_size == 0 (nbytes == 0, or first >= F) nothing is decoded,
+ * range_members is 0 and the call returns 0. Otherwise m0 is the member with ISIZE > 0 that holds byte lo and m1 the one that holds byte hi - 1; the call
+ * decodes members m0 .. m1 and no others — empty members between them go through as zero-length items, as in zultra_hip_inflate_file —, results[k] is what
+ * zultra_hip_inflate_file reports for member m0 + k, field for field, and the return value is the number of decoded members whose reason is not 0. A member
+ * outside m0 .. m1 is never looked at beyond what the index reads: if it is damaged the call does not notice. A stop of 1..3 is no error: res->stop reports it
+ * and the range is served from the indexed prefix. If out_size > dst_size, or results != NULL and range_members > results_cap, stop is 4, the call returns -1,
+ * nothing is written and res says how much room is needed. Bad arguments (-1) are those of zultra_hip_inflate_file.
+ * Members that lie wholly inside [lo, hi) are decoded straight into their place in dst, also where dst is a device pointer used in place; the one or two that
+ * straddle an end of the range are decoded and CRC-checked in full in memory the call owns, and their slices moved into dst. Nothing outside
+ * dst[0 .. out_size) is ever written (of a host dst only out_size bytes). If a member fails, its own part of the range is unspecified and every other member's
+ * bytes are in place. The call owns memory in proportion to the tile count, the members decoded and the straddling members' ISIZEs, never to F or to the
+ * file's member count, and reads back 32 bytes per decoded member.
+ *   members, stop, src_used, tiles, tiles_rewalked : the index of the WHOLE source, as in zultra_hip_index_result_t; file_size is F
+ *   first_member, range_members : m0 and m1 - m0 + 1
+ * kernel_ms (may be NULL): five — index, select + items, frame, inflate, check + edges.
+ */
+typedef struct zultra_hip_range_result_s {
+   uint32_t members, stop;                 /* the index of the whole source; 4 = too little room (nothing decoded) */
+   uint64_t file_size, src_used;           /* sum of ISIZE of the indexed members; the stop position */
+   uint32_t first_member, range_members;   /* the members decoded: first_member .. first_member + range_members - 1 */
+   uint64_t out_size;                      /* bytes of the range that exist: what was (or would be) written to dst[0 .. out_size) */
+   uint32_t tiles, tiles_rewalked;
+} zultra_hip_range_result_t;
+int zultra_hip_inflate_range(int device, const void *src, size_t src_size, int src_on_device, uint64_t first, uint64_t nbytes,
+                             void *dst, size_t dst_size, int dst_on_device, zultra_hip_range_result_t *res,
+                             zultra_hip_member_result_t *results /* host, results_cap; may be NULL */, uint32_t results_cap,
+                             float *kernel_ms /* [5]: index, select + items, frame, inflate, check + edges; may be NULL */);
+
+/*
  * Many small independent inputs ("files", BASELINE.json configuration 5: 4 KiB records, each its own stream). A files
  * context takes inputs below 8192 bytes — the splitter never cuts those (blockdeflate.c:646), so a batch needs no host
  * decision and its whole kernel sequence is replayed from one captured hipGraph. zultra_hip_compress_files runs

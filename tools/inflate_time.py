@@ -10,8 +10,10 @@ zultra_hip_inflate_members (zh_frame_heads, the inflate kernel, zh_check_members
 bare streams and host zlib.crc32 / zlib.adler32 over the output on one core, all in one process. Then the file leg: the first --bgzf-bytes of the
 corpus as ONE BGZF file built on the host (payloads of 65 280 bytes, host zlib level 6), indexed, inflated and checked device to device by
 zultra_hip_inflate_file (four kernel times: index, frame, inflate, check) with ZULTRA_HIP_INDEX_TILE swept over 64 KiB .. 4 MiB, next to the route
-without the index in the same process: a host walk of BSIZE over a host copy of the file, then zultra_hip_inflate_members over those items. One JSON
-line.
+without the index in the same process: a host walk of BSIZE over a host copy of the file, then zultra_hip_inflate_members over those items. Then the
+range leg (--only range; no part of the whole run): bytes of 64 KiB, 1 MiB and 16 MiB from the middle of the same file by zultra_hip_inflate_range, device
+to device (five kernel times: index, select + items, frame, inflate, check + edges), next to the route to the same bytes without it in the same process:
+zultra_hip_inflate_file of the whole file. One JSON line.
 
     python tools/inflate_time.py [--files N] [--file-size BYTES] [--reps N] [--dict-size BYTES] [--step-timeout SECONDS] [--lib PATH]
 
@@ -26,6 +28,8 @@ The steps run in this order, every GPU step in a process of its own under its ow
        streams; zlib.crc32 and zlib.adler32 over the output on one core (the outputs are read back once and compared with the input)
     7. zultra_hip_inflate_file over the BGZF file per tile size, then the host walk and zultra_hip_inflate_members (the output is read back once
        and compared with the input)
+    range (--only range). zultra_hip_inflate_range per range size, then zultra_hip_inflate_file of the whole file (every range is read back once and
+       compared with the input)
 --lib: another build of the library (an A/B of the plain kernel against an older build); steps 4 and 5 are left out where it has no dictionary kernel,
 step 6 where it has no members call, step 7 where it has no file call."""
 import argparse
@@ -49,7 +53,8 @@ def library(args):
         return zultra_amd.lib()
     from zultra_amd._ffi import Lib
     return Lib(args.lib, allow_missing=("zultra_memory_decompress_dict", "zultra_hip_inflate_streams_dict", "zultra_memory_decompress_batch", "zultra_hip_inflate_members",
-                                        "zultra_hip_index_members", "zultra_hip_inflate_file", "zultra_memory_decompress_members"))
+                                        "zultra_hip_index_members", "zultra_hip_inflate_file", "zultra_memory_decompress_members",
+                                        "zultra_hip_inflate_range", "zultra_memory_index_gzi", "zultra_memory_decompress_range"))
 
 
 def batch(args):
@@ -288,6 +293,62 @@ def child_file(args):
     return 0
 
 
+RANGE_SIZES = [64 << 10, 1 << 20, 16 << 20]
+
+
+def child_range(args):
+    import numpy as np
+
+    import corpus
+    import inflate_cases as I
+    import inflate_file_cases as F
+    import verify_cases as V
+    L = library(args)
+    if L.device_count() < 1:
+        raise RuntimeError("no HIP device visible: nothing can be timed")
+    L.is_emulator = False
+    nrec = (args.bgzf_bytes + args.file_size - 1) // args.file_size
+    raw = np.ascontiguousarray(corpus.json_files(0, nrec, args.file_size), dtype=np.uint8).tobytes()[:args.bgzf_bytes]
+    buf = b"".join(F.bgzf(raw[at: at + 65280]) for at in range(0, len(raw), 65280)) + F.EOF_MARKER
+    src, dst = V.DeviceCopy(L, np.frombuffer(buf, dtype=np.uint8).copy()), V.DeviceCopy(L, np.zeros(len(raw), dtype=np.uint8))
+    out = {"bgzf_input_bytes": len(raw), "bgzf_file_bytes": len(buf), "range_kernel_ms_by_size": {}}
+    names = ("index", "select_items", "frame", "inflate", "check_edges")
+    for size in RANGE_SIZES:
+        first = len(raw) // 2 - size // 2 + 12345   # (no member boundary: both ends straddle)
+        times, calls = [], []
+        for it in range(2 + args.reps):   # (two warm-up calls)
+            t0 = time.perf_counter()
+            rc, res, _, ms = L.inflate_range(src.ptr, len(buf), first, size, dst.ptr, size, None)
+            calls.append(1e3 * (time.perf_counter() - t0))
+            assert rc == 0 and res.stop == 0 and res.out_size == size, (size, rc, res.stop, res.out_size)
+            if it >= 2:
+                times.append(ms)
+        assert I.device_read(L, dst, size).tobytes() == raw[first: first + size], "the range differs from the input (%d)" % size
+        row = {name: float(np.median([t[k] for t in times])) for k, name in enumerate(names)}
+        row.update({"call_ms_min": min(calls[2:]), "first_member": res.first_member, "range_members": res.range_members, "members": res.members, "tiles": res.tiles})
+        out["range_kernel_ms_by_size"][str(size)] = row
+    # the route without the range call: the whole file inflated, the bytes a slice of it
+    times, calls = [], []
+    for it in range(2 + args.reps):
+        t0 = time.perf_counter()
+        rc, res, _, ms = L.inflate_file(src.ptr, len(buf), dst.ptr, len(raw), None)
+        calls.append(1e3 * (time.perf_counter() - t0))
+        assert rc == 0 and res.stop == 0 and res.out_size == len(raw)
+        if it >= 2:
+            times.append(ms)
+    med = [float(np.median([t[k] for t in times])) for k in range(4)]
+    out["range_whole_file_route"] = {"index": med[0], "frame": med[1], "inflate": med[2], "check": med[3], "call_ms_min": min(calls[2:]), "members": res.members}
+    for size in RANGE_SIZES:
+        row = out["range_kernel_ms_by_size"][str(size)]
+        row["index_share_of_kernels"] = row["index"] / sum(row[name] for name in names)
+        row["select_and_edges_over_inflate"] = (row["select_items"] + row["check_edges"]) / row["inflate"]
+        row["call_over_whole_file_call"] = row["call_ms_min"] / out["range_whole_file_route"]["call_ms_min"]
+    src.free()
+    dst.free()
+    print(json.dumps(out), flush=True)
+    return 0
+
+
 def gpu_step(name, args):
     cmd = [sys.executable, os.path.abspath(__file__), "--child", name, "--files", str(args.files), "--file-size", str(args.file_size), "--reps", str(args.reps),
            "--dict-size", str(args.dict_size), "--bgzf-bytes", str(args.bgzf_bytes), "--stream-file", args.stream_file] + (["--lib", args.lib] if args.lib else [])
@@ -308,11 +369,11 @@ def main():
     ap.add_argument("--bgzf-bytes", type=int, default=100 * 1000 * 1000, help="bytes of the corpus the file leg frames as one BGZF file")
     ap.add_argument("--only", default="", help="run only this step (e.g. file) and print its JSON line")
     ap.add_argument("--lib", default="", help="another build of libzultra_amd.so to time instead of the tree's")
-    ap.add_argument("--child", choices=["inflate", "verify", "dict", "members", "file"], help="(internal) the process that opens the GPU")
+    ap.add_argument("--child", choices=["inflate", "verify", "dict", "members", "file", "range"], help="(internal) the process that opens the GPU")
     ap.add_argument("--stream-file", default="", help="(internal) where the inflate step leaves the streams for host zlib")
     args = ap.parse_args()
     if args.child:
-        sys.exit({"inflate": child_inflate, "verify": child_verify, "dict": child_dict, "members": child_members, "file": child_file}[args.child](args))
+        sys.exit({"inflate": child_inflate, "verify": child_verify, "dict": child_dict, "members": child_members, "file": child_file, "range": child_range}[args.child](args))
     import numpy as np
     if args.only:
         print(json.dumps(gpu_step(args.only, args)), flush=True)

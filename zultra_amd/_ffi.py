@@ -91,6 +91,12 @@ class IndexResult(C.Structure):
     _fields_ = [("members", C.c_uint32), ("stop", C.c_uint32), ("out_size", C.c_uint64), ("src_used", C.c_uint64), ("tiles", C.c_uint32), ("tiles_rewalked", C.c_uint32)]
 
 
+class RangeResult(C.Structure):
+    # zultra_hip_range_result_t
+    _fields_ = [("members", C.c_uint32), ("stop", C.c_uint32), ("file_size", C.c_uint64), ("src_used", C.c_uint64), ("first_member", C.c_uint32), ("range_members", C.c_uint32),
+                ("out_size", C.c_uint64), ("tiles", C.c_uint32), ("tiles_rewalked", C.c_uint32)]
+
+
 class ZipIndexResult(C.Structure):
     # zultra_hip_zip_index_result_t
     _fields_ = [("entries", C.c_uint32), ("stop", C.c_uint32), ("out_size", C.c_uint64), ("dir_used", C.c_uint64), ("tiles", C.c_uint32), ("tiles_rewalked", C.c_uint32)]
@@ -134,6 +140,7 @@ EXPORTS = [
     "zultra_memory_decompress", "zultra_hip_inflate_streams", "zultra_memory_decompress_dict", "zultra_hip_inflate_streams_dict",
     "zultra_memory_decompress_batch", "zultra_hip_inflate_members",
     "zultra_hip_index_members", "zultra_hip_inflate_file", "zultra_memory_decompress_members",
+    "zultra_hip_inflate_range", "zultra_memory_index_gzi", "zultra_memory_decompress_range",
     # framed members
     "zultra_hip_frame_members", "zultra_hip_last_frame_ms", "zultra_memory_bound_bgzf", "zultra_memory_compress_bgzf", "zultra_memory_compress_batch",
     # ZIP archives
@@ -351,6 +358,55 @@ class Lib:
                None if dst is None else int(dst) if dst_dev else dst.ctypes.data, dst_size, 1 if dst_dev else 0, C.byref(res),
                out.ctypes.data if results_cap is not None else None, results_cap or 0, ms)
         return rc, res, out[:res.members if rc >= 0 else 0], [float(v) for v in ms]
+
+    def inflate_range(self, src, src_size, first, nbytes, dst, dst_size, results_cap=None, device=0):
+        """zultra_hip_inflate_range: bytes [first, first + nbytes) of the file's output. src / dst: a uint8 array (host memory, staged by the call) or an
+        integer device pointer (used in place); results_cap: room for that many per-member results, None to pass results = NULL.
+        -> (rc, RangeResult, results (MemberResult's layout, the decoded members'), kernel_ms = [index, select + items, frame, inflate, check + edges])."""
+        res = RangeResult()
+        out = np.zeros(results_cap or 0, dtype=MEMBER_RESULT_DTYPE)
+        src_dev, dst_dev = not isinstance(src, np.ndarray), not isinstance(dst, np.ndarray)
+        ms = (C.c_float * 5)()
+        f = self.L.zultra_hip_inflate_range
+        f.argtypes = [C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_uint64, C.c_uint64, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(RangeResult), C.c_void_p, C.c_uint32, C.POINTER(C.c_float)]
+        f.restype = C.c_int
+        rc = f(device, None if src is None else int(src) if src_dev else src.ctypes.data, src_size, 1 if src_dev else 0, first, nbytes,
+               None if dst is None else int(dst) if dst_dev else dst.ctypes.data, dst_size, 1 if dst_dev else 0, C.byref(res),
+               out.ctypes.data if results_cap is not None else None, results_cap or 0, ms)
+        return rc, res, out[:min(res.range_members, len(out)) if rc >= 0 else 0], [float(v) for v in ms]
+
+    def memory_index_gzi(self, data, cap=None, query=False):
+        """zultra_memory_index_gzi -> the .gzi index of a BGZF file as bytes (query: the size needed, pGzi = NULL), or None where the call returns
+        (size_t)-1. cap: bytes of room, default what the query says."""
+        data = _as_u8(data)
+        f = self.L.zultra_memory_index_gzi
+        f.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
+        f.restype = C.c_size_t
+        src = data.ctypes.data if len(data) else None
+        if query or cap is None:
+            r = f(src, len(data), None, 0)
+            if r == _SIZE_MAX:
+                return None
+            if query:
+                return int(r)
+            cap = int(r)
+        out = np.empty(max(cap, 1), dtype=np.uint8)
+        r = f(src, len(data), out.ctypes.data, cap)
+        return None if r == _SIZE_MAX else out[:r].tobytes()
+
+    def memory_decompress_range(self, data, first, nbytes, max_out=None, gzi=None):
+        """zultra_memory_decompress_range -> bytes [first, first + nbytes) of the output (short at the end of the file), or None where the call returns
+        (size_t)-1. data: bytes or a uint8 array (used as it is); gzi: the .gzi index, or None; max_out: bytes of room, default nbytes."""
+        data = _as_u8(data)
+        if max_out is None:
+            max_out = nbytes
+        out = np.empty(max(max_out, 1), dtype=np.uint8)
+        g = None if gzi is None else _as_u8(gzi)
+        f = self.L.zultra_memory_decompress_range
+        f.argtypes = [C.c_void_p, C.c_size_t, C.c_ulonglong, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
+        f.restype = C.c_size_t
+        r = f(data.ctypes.data if len(data) else None, len(data), first, nbytes, out.ctypes.data, max_out, None if g is None else g.ctypes.data if len(g) else out.ctypes.data, 0 if g is None else len(g))
+        return None if r == _SIZE_MAX else out[:r].tobytes()
 
     def memory_decompress_members(self, data, max_out):
         """zultra_memory_decompress_members -> (the concatenated output, members), or (None, 0) where the call returns (size_t)-1."""

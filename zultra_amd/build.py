@@ -15,7 +15,7 @@ CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libzultra_amd.so")
 CLI = os.path.join(HERE, "zultra_amd_cli")
 SOURCES = ["zh_device.hip", "zh_inflate.hip", "libzultra.cpp"]
-HEADERS = ["zh_platform.h", "zh_host.h", "zh_common.h", "zh_matchfinder.h", "zh_mf_group_lds.h", "zh_huffman.h", "zh_split.h", "zh_parse.h", "zh_parse_chain.h", "zh_parse_lanes.h", "zh_encode.h", "zh_stitch.h", "zh_frame.h", "zh_copy.h", "zh_zip.h", "zh_deflate_dec.h", "zh_verify.h", "zh_inflate_out.h", "zh_inflate_check.h", "zh_inflate_index.h", "zh_unzip.h"]
+HEADERS = ["zh_platform.h", "zh_host.h", "zh_common.h", "zh_matchfinder.h", "zh_mf_group_lds.h", "zh_huffman.h", "zh_split.h", "zh_parse.h", "zh_parse_chain.h", "zh_parse_lanes.h", "zh_encode.h", "zh_stitch.h", "zh_frame.h", "zh_copy.h", "zh_zip.h", "zh_deflate_dec.h", "zh_verify.h", "zh_inflate_out.h", "zh_inflate_check.h", "zh_inflate_index.h", "zh_inflate_range.h", "zh_unzip.h"]
 
 
 def hipcc_path():

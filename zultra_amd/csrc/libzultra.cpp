@@ -1488,6 +1488,91 @@ extern "C" size_t zultra_memory_decompress_members(const unsigned char *pIn, siz
    return written;
 }
 
+// ---- a byte range of a BGZF file, and bgzip's .gzi index (include/zultra_hip.h: zultra_hip_inflate_range) ----------------------------------------------
+static unsigned long long gzi_get(const unsigned char *p) {
+   unsigned long long v = 0;
+   for (int k = 0; k < 8; k++) v |= (unsigned long long)p[k] << (8 * k);
+   return v;
+}
+static void gzi_put(unsigned char *p, unsigned long long v) {
+   for (int k = 0; k < 8; k++) p[k] = (unsigned char)(v >> (8 * k));
+}
+
+// One pair for every indexed member but the first. The source is uploaded once: the index runs over it twice, for the count and for the items.
+extern "C" size_t zultra_memory_index_gzi(const unsigned char *pIn, size_t nIn, unsigned char *pGzi, size_t nMaxGzi) try {
+   if (!pIn || nIn == 0) return (size_t)-1;
+   const int device = zh_pick_device();
+   uint8_t *const d_in = (uint8_t *)zh_device_upload(device, pIn, nIn);
+   if (!d_in) return (size_t)-1;
+   size_t size = (size_t)-1;
+   zultra_hip_index_result_t ix;
+   if (zultra_hip_index_members(device, d_in, nIn, 1, NULL, 0, &ix, NULL) == 0 && ix.stop == 0 && ix.members >= 1) {
+      const size_t n = ix.members - 1;
+      size = 8 + 16 * n;
+      if (pGzi && nMaxGzi < size) size = (size_t)-1;
+      else if (pGzi) {
+         std::vector<zultra_hip_inflate_item_t> items(ix.members);
+         if (zultra_hip_index_members(device, d_in, nIn, 1, items.data(), ix.members, &ix, NULL) != 0 || ix.stop != 0 || ix.members != n + 1) size = (size_t)-1;
+         else {
+            gzi_put(pGzi, n);
+            for (size_t i = 0; i < n; i++) {
+               gzi_put(pGzi + 8 + 16 * i, items[i + 1].src_off);
+               gzi_put(pGzi + 16 + 16 * i, items[i + 1].dst_off);
+            }
+         }
+      }
+   }
+   zh_device_release(d_in);
+   return size;
+}
+catch (...) {
+   return (size_t)-1;
+}
+
+extern "C" size_t zultra_memory_decompress_range(const unsigned char *pIn, size_t nIn, unsigned long long nFirst, size_t nBytes, unsigned char *pOut, size_t nMaxOut,
+                                                 const unsigned char *pGzi, size_t nGzi) {
+   if (!pIn || nIn == 0 || (!pOut && nMaxOut) || (!pGzi && nGzi)) return (size_t)-1;
+   const int device = zh_pick_device();
+   unsigned char none = 0;
+   unsigned char *const out = pOut ? pOut : &none;
+   const unsigned long long end = (unsigned long long)nBytes > ~0ull - nFirst ? ~0ull : nFirst + nBytes;
+   zultra_hip_range_result_t res;
+   if (!pGzi) {
+      if (zultra_hip_inflate_range(device, pIn, nIn, 0, nFirst, nBytes, out, nMaxOut, 0, &res, NULL, 0, NULL) != 0) return (size_t)-1;   // a member failed, too little room, an error
+      if (res.stop != 0 && end > res.file_size) return (size_t)-1;   // what lies behind the indexed prefix is unknown
+      return (size_t)res.out_size;
+   }
+   // the index: well-formed, and in order
+   if (nGzi < 8 || (nGzi - 8) % 16 != 0 || gzi_get(pGzi) != (nGzi - 8) / 16) return (size_t)-1;
+   const size_t n = (nGzi - 8) / 16;
+   const auto coff = [pGzi](size_t i) { return gzi_get(pGzi + 8 + 16 * i); };
+   const auto uoff = [pGzi](size_t i) { return gzi_get(pGzi + 16 + 16 * i); };
+   for (size_t i = 0; i < n; i++)
+      if (coff(i) == 0 || coff(i) >= nIn || (i && (coff(i) <= coff(i - 1) || uoff(i) < uoff(i - 1)))) return (size_t)-1;
+   if (nBytes == 0) return 0;
+   // (c0, u0): the last pair with u <= nFirst; (c1, u1): the first with u >= end (behind the former, as end > nFirst)
+   size_t lo = 0, hi = n;   // pairs [0, lo) have u <= nFirst
+   while (lo < hi) {
+      const size_t mid = lo + (hi - lo) / 2;
+      if (uoff(mid) <= nFirst) lo = mid + 1;
+      else hi = mid;
+   }
+   const unsigned long long c0 = lo ? coff(lo - 1) : 0, u0 = lo ? uoff(lo - 1) : 0;
+   size_t at = lo;
+   hi = n;   // pairs [lo, at) have u < end
+   while (at < hi) {
+      const size_t mid = at + (hi - at) / 2;
+      if (uoff(mid) < end) at = mid + 1;
+      else hi = mid;
+   }
+   const bool bounded = at < n;
+   const unsigned long long c1 = bounded ? coff(at) : nIn, u1 = bounded ? uoff(at) : 0;
+   if (zultra_hip_inflate_range(device, pIn + c0, (size_t)(c1 - c0), 0, nFirst - u0, nBytes, out, nMaxOut, 0, &res, NULL, 0, NULL) != 0) return (size_t)-1;
+   // what the index said of the window: a member at its first byte, the chain's end at its last, and the output between the two pairs
+   if (res.members == 0 || res.stop != 0 || (bounded && res.file_size != u1 - u0)) return (size_t)-1;
+   return (size_t)res.out_size;
+}
+
 // ---- ZIP archives read: the end records on the host, everything else on the device (include/zultra_hip.h: zultra_hip_unzip) ---------------------------
 static unsigned long long zip_get(const unsigned char *p, int nbytes) {
    unsigned long long v = 0;

@@ -1,5 +1,5 @@
 // zh_inflate.hip — host side of the context-free inflate calls of include/zultra_hip.h: batches of raw streams (with or without a preset dictionary), batches
-// of gzip / zlib members, the member index of a whole file, the whole file, a ZIP archive's directory and its entries. No zultra_hip_ctx_t: a call owns what it allocates and releases it when it returns.
+// of gzip / zlib members, the member index of a whole file, the whole file, a byte range of it, a ZIP archive's directory and its entries. No zultra_hip_ctx_t: a call owns what it allocates and releases it when it returns.
 #include <zh_platform.h>
 
 #include <string.h>
@@ -12,6 +12,7 @@
 #include "zh_inflate_out.h"
 #include "zh_inflate_check.h"
 #include "zh_inflate_index.h"
+#include "zh_inflate_range.h"
 #include "zh_unzip.h"
 
 // ---- batched inflate (zh_inflate_out.h, zh_inflate_check.h) -------------------------------------------------------------------------------------------
@@ -22,6 +23,7 @@ static_assert(sizeof(zultra_hip_member_result_t) == sizeof(zh_member_result_t), 
 enum zh_inflate_event {
    ZH_IEV_INDEX_START, ZH_IEV_INDEX_END, ZH_IEV_ITEMS_START, ZH_IEV_ITEMS_END,   // around zh_ix_tiles and zh_ix_resolve; around zh_ix_items
    ZH_IEV_HEADS, ZH_IEV_INFLATE, ZH_IEV_CHECKS, ZH_IEV_END,   // starts of zh_frame_heads, of the inflate kernel (a streams call's first mark), of zh_check_members; the end
+   ZH_IEV_RG_PLAN, ZH_IEV_RG_ITEMS, ZH_IEV_RG_END,   // zultra_hip_inflate_range: behind zh_rg_select (the items' START in front of it), in front of zh_rg_items (their END behind it), behind zh_rg_edges
    ZH_IEV_UZ_LOCALS, ZH_IEV_UZ_INFLATE, ZH_IEV_UZ_COPY, ZH_IEV_UZ_CHECKS, ZH_IEV_UZ_END,   // zultra_hip_unzip: starts of zh_uz_locals, the inflate kernel, zh_uz_copy, zh_check_members; the end
    ZH_INFLATE_EVENTS
 };
@@ -44,6 +46,8 @@ struct zh_inflate_call_t {
    zh_dictjob_t *d_dictjob = NULL;
    zh_ix_tile_t *d_ix_tiles = NULL;   // (the member index only)
    zh_ix_totals_t *d_ix_totals = NULL;
+   zh_rg_plan_t *d_plan = NULL;   // (a range only, as the next: the members that straddle an end of it, decoded in full)
+   uint8_t *d_edge = NULL;
    zh_zip_dirent_t *d_dirents = NULL;   // (a ZIP archive only, as the two below)
    zh_uz_copy_t *d_copies = NULL;
    uint32_t *d_ncopies = NULL;
@@ -53,7 +57,7 @@ struct zh_inflate_call_t {
    uint8_t *d8 = NULL;
    uint32_t hist_len = 0;
    ~zh_inflate_call_t() {
-      for (void *p : std::initializer_list<void *>{d_src, d_dst, d_hist, d_items, d_inner, d_results, d_members, d_idx, d_tables, d_dictjob, d_ix_tiles, d_ix_totals, d_dirents, d_copies, d_ncopies}) (void)hipFree(p);
+      for (void *p : std::initializer_list<void *>{d_src, d_dst, d_hist, d_items, d_inner, d_results, d_members, d_idx, d_tables, d_dictjob, d_ix_tiles, d_ix_totals, d_plan, d_edge, d_dirents, d_copies, d_ncopies}) (void)hipFree(p);
       for (hipEvent_t e : ev)
          if (e) (void)hipEventDestroy(e);
    }
@@ -294,11 +298,10 @@ static const zh_member_result_t *zh_dictid(zh_inflate_call_t &C, unsigned int fr
 }
 
 // 5. the members of a call whose n items lie in C.d_items (`items`: the host's copy of them): headers, inflate, checksums and trailers in three launches
-// on the null stream, the results read back, one synchronisation at the end; ms: the three kernel times. dst_size: what the kernels are told of the
-// destination; dict: the whole dictionary (dict_size 0: none; zh_inflate_args has taken its history); with_dictid: zh_frame_heads gets a DICTID to
-// compare with (a call that takes a dictionary: a whole file does not).
-static int zh_members_run(zh_inflate_call_t &C, int device, size_t src_size, size_t dst_size, unsigned int framing, bool with_dictid, const void *dict, size_t dict_size, int dict_on_device,
-                          const zultra_hip_inflate_item_t *items, uint32_t n, zultra_hip_member_result_t *results, float *ms) {
+// on the null stream, between the call's events HEADS .. END. dst_size: what the kernels are told of the destination; dict: the whole dictionary (dict_size 0:
+// none; zh_inflate_args has taken its history); with_dictid: zh_frame_heads gets a DICTID to compare with (a call that takes a dictionary: a whole file does not).
+static int zh_members_enqueue(zh_inflate_call_t &C, int device, size_t src_size, size_t dst_size, unsigned int framing, bool with_dictid, const void *dict, size_t dict_size, int dict_on_device,
+                              const zultra_hip_inflate_item_t *items, uint32_t n) {
    ZH_TRY(zh_dalloc(&C.d_inner, n));
    ZH_TRY(zh_dalloc(&C.d_members, n));
    if (zh_check_plan(C, items, n, framing)) return -1;
@@ -312,12 +315,21 @@ static int zh_members_run(zh_inflate_call_t &C, int device, size_t src_size, siz
    ZH_TRY(hipEventRecord(C.ev[ZH_IEV_CHECKS], 0));
    if (zh_check_launch(framing, C.s8, C.d8, dst_size, C.d_items, C.d_results, C.d_members, C.d_idx, C.nsmall, C.nlarge, C.spg, C.d_tables)) return -1;
    ZH_TRY(hipEventRecord(C.ev[ZH_IEV_END], 0));
+   return 0;
+}
+// 6. ... their results read back, the call's one synchronisation; ms: the three kernel times
+static int zh_members_collect(const zh_inflate_call_t &C, uint32_t n, zultra_hip_member_result_t *results, float *ms) {
    ZH_TRY(hipMemcpy(results, C.d_members, (size_t)n * sizeof(zh_member_result_t), hipMemcpyDeviceToHost));
    ZH_TRY(hipDeviceSynchronize());
    ZH_TRY(hipGetLastError());
    if (ms)
       for (int i = 0; i < 3; i++) (void)hipEventElapsedTime(ms + i, C.ev[ZH_IEV_HEADS + i], C.ev[ZH_IEV_HEADS + i + 1]);
    return 0;
+}
+static int zh_members_run(zh_inflate_call_t &C, int device, size_t src_size, size_t dst_size, unsigned int framing, bool with_dictid, const void *dict, size_t dict_size, int dict_on_device,
+                          const zultra_hip_inflate_item_t *items, uint32_t n, zultra_hip_member_result_t *results, float *ms) {
+   if (zh_members_enqueue(C, device, src_size, dst_size, framing, with_dictid, dict, dict_size, dict_on_device, items, n)) return -1;
+   return zh_members_collect(C, n, results, ms);
 }
 
 // Many gzip / zlib members (or raw streams).
@@ -488,6 +500,133 @@ extern "C" int zultra_hip_inflate_file(int device, const void *src, size_t src_s
    for (uint32_t k = 0; k < n; k++)   // (as the index put them)
       if (items[k].dst_cap) C.order.push_back(k);
    return zh_inflate_collect(C, dst, dst_on_device, items.data(), n, results);
+}
+
+// ---- a byte range of a whole file (zh_inflate_range.h) ---------------------------------------------------------------------------------------------------
+static void zh_index_report(const zh_index_t &X, zultra_hip_range_result_t *res) {
+   res->members = (uint32_t)zh_min64(X.tot.members, 0xFFFFFFFFull);
+   res->stop = X.tot.stop;
+   res->file_size = X.tot.out_size;
+   res->src_used = X.tot.src_used;
+   res->tiles = (uint32_t)zh_min64(X.tot.tiles, 0xFFFFFFFFull);
+   res->tiles_rewalked = (uint32_t)zh_min64(X.tot.tiles_rewalked, 0xFFFFFFFFull);
+}
+
+// Bytes [first, first + nbytes) of the indexed members' output: the index; the two members that hold the ends of the range picked from the tile records (the
+// plan, read back with the room checks); the items of members m0 .. m1, those wholly inside the range rebased to it, the one or two that straddle an end sent
+// to the edge buffer; ONE batch through the three launches — its destination the lower of the two buffers' addresses, so that every member of the range is
+// in flight at once —; the slices moved out of the edge buffer; the results read back behind one synchronisation.
+extern "C" int zultra_hip_inflate_range(int device, const void *src, size_t src_size, int src_on_device, uint64_t first, uint64_t nbytes, void *dst, size_t dst_size, int dst_on_device,
+                                        zultra_hip_range_result_t *res, zultra_hip_member_result_t *results, uint32_t results_cap, float *kernel_ms) {
+   ZH_EMU_SERIALIZE();
+   if (kernel_ms)
+      for (int i = 0; i < 5; i++) kernel_ms[i] = 0.f;
+   if (!res || !dst) return -1;
+   memset(res, 0, sizeof(*res));
+   zh_inflate_call_t C;
+   zh_index_t X;
+   X.size = src_size;
+   if (zh_index_run(C, X, device, src, src_size, src_on_device, ZH_IEV_HEADS, ZH_IEV_RG_END)) return -1;
+   zh_index_report(X, res);
+   const uint64_t F = X.tot.out_size, lo = zh_min64(first, F), hi = zh_min64(nbytes > ~0ull - first ? ~0ull : first + nbytes, F);
+   res->out_size = hi - lo;
+   if (hi == lo) {   // nothing of the range exists: nothing is decoded
+      ZH_TRY(hipDeviceSynchronize());
+      if (kernel_ms) kernel_ms[0] = zh_index_ms(C, false);
+      return 0;
+   }
+   // the plan
+   ZH_TRY(zh_dalloc(&C.d_plan, 1));
+   ZH_TRY(hipEventRecord(C.ev[ZH_IEV_ITEMS_START], 0));
+   ZH_LAUNCH(zh_rg_select, 1, ZH_RG_THREADS, 0, C.s8, (uint64_t)src_size, X.ntiles, C.d_ix_tiles, lo, hi - 1u, C.d_plan);
+   ZH_TRY(hipEventRecord(C.ev[ZH_IEV_RG_PLAN], 0));
+   zh_rg_plan_t plan;
+   ZH_TRY(hipMemcpy(&plan, C.d_plan, sizeof(plan), hipMemcpyDeviceToHost));
+   ZH_TRY(hipGetLastError());
+   const zh_rg_end_t &a = plan.end[0], &b = plan.end[1];
+   if (!a.found || !b.found || b.member < a.member || b.tile < a.tile || b.tile >= X.ntiles) return -1;   // (never: the index holds every byte below F)
+   const uint64_t count = b.member - a.member + 1u;
+   res->first_member = (uint32_t)zh_min64(a.member, 0xFFFFFFFFull);
+   res->range_members = (uint32_t)zh_min64(count, 0xFFFFFFFFull);
+   if (a.member > 0xFFFFFFFFull || count > 0xFFFFFFFFull || hi - lo > dst_size || (results && count > results_cap)) {
+      res->stop = 4;   // nothing is decoded: res says how much room the range needs
+      return -1;
+   }
+   const uint32_t n = (uint32_t)count;
+   const size_t out_size = (size_t)(hi - lo);
+   // the members that straddle an end: decoded in full into the edge buffer, the head's at 0, the tail's behind it, both 16-byte aligned
+   const bool one = a.member == b.member;
+   const bool head_edge = a.out_off < lo || a.out_off + a.isize > hi, tail_edge = !one && b.out_off + b.isize > hi;
+   const uint64_t tail_at = head_edge ? ((uint64_t)a.isize + 15u) & ~15ull : 0u, edge_room = tail_at + (tail_edge ? ((uint64_t)b.isize + 15u) & ~15ull : 0u);
+   // the two buffers: a host destination is staged behind the edge buffer in one allocation, exactly the bytes of the range
+   uint8_t *range8 = (uint8_t *)dst, *edge8 = NULL;
+   if (!dst_on_device) {
+      ZH_TRY(zh_dalloc(&C.d_dst, (size_t)edge_room + out_size));
+      edge8 = C.d_dst;
+      range8 = C.d_dst + edge_room;
+   }
+   else if (edge_room) {
+      ZH_TRY(zh_dalloc(&C.d_edge, (size_t)edge_room));
+      edge8 = C.d_edge;
+   }
+   // ... as one destination for the three launches: from the lower address to the end of the higher buffer
+   C.d8 = edge_room && edge8 < range8 ? edge8 : range8;
+   const uint64_t range_at = (uint64_t)(range8 - C.d8), edge_at = edge_room ? (uint64_t)(edge8 - C.d8) : 0u;
+   const size_t span = (size_t)zh_max64(range_at + out_size, edge_at + edge_room);
+   zh_rg_edge_t head = {}, tail = {};
+   if (head_edge) {
+      head.buf_at = 0;
+      head.from = lo - a.out_off;   // (the member holds byte lo)
+      head.to = zh_min64(hi - a.out_off, a.isize);
+      head.dst_at = 0;
+      head.slot = 0;
+   }
+   if (tail_edge) {
+      tail.buf_at = tail_at;
+      tail.from = 0;
+      tail.to = hi - b.out_off;
+      tail.dst_at = b.out_off - lo;
+      tail.slot = n - 1u;
+   }
+   // the items, where the three launches read them; the host's copy of them for the checksum kernel's two forms: 32 bytes per member of the range
+   ZH_TRY(zh_dalloc(&C.d_items, n));
+   const uint64_t ntiles = b.tile - a.tile + 1u;
+   ZH_TRY(hipEventRecord(C.ev[ZH_IEV_RG_ITEMS], 0));
+   ZH_LAUNCH(zh_rg_items, zh_capped((uint32_t)zh_min64((ntiles + ZH_RG_THREADS - 1) / ZH_RG_THREADS, 4096), zh_grid_cap()), ZH_RG_THREADS, 0, C.s8, (uint64_t)src_size, C.d_ix_tiles, a.tile,
+             b.tile, a.member, b.member, lo, hi, range_at, edge_at, edge_at + tail_at, C.d_items);
+   ZH_TRY(hipEventRecord(C.ev[ZH_IEV_ITEMS_END], 0));
+   std::vector<zultra_hip_inflate_item_t> items(n);
+   ZH_TRY(hipMemcpy(items.data(), C.d_items, (size_t)n * sizeof(zh_inflate_item_t), hipMemcpyDeviceToHost));
+   ZH_TRY(hipGetLastError());
+   std::vector<zultra_hip_member_result_t> own;
+   if (!results) {
+      own.resize(n);
+      results = own.data();
+   }
+   ZH_TRY(zh_dalloc(&C.d_results, n));
+   if (zh_members_enqueue(C, device, src_size, span, ZH_M_GZIP, false, NULL, 0, 0, items.data(), n)) return -1;
+   if (head_edge || tail_edge) {   // a wave per edge and slice, as many slices as the longer edge has
+      const uint64_t longest = zh_max64(head.to - head.from, tail.to - tail.from);
+      uint32_t yslices = (uint32_t)zh_min64(zh_max64((longest / 16 + ZH_ZIP_SLICE_CHUNKS - 1) / ZH_ZIP_SLICE_CHUNKS, 1), ZH_RG_MAX_YSLICES);
+      if (zh_grid_cap()) yslices = max(1u, min(yslices, zh_grid_cap() / 2));
+      ZH_LAUNCH(zh_rg_edges, 2 * yslices, ZH_RG_THREADS, 0, edge8, edge_room, range8, head, tail, C.d_members, yslices);
+   }
+   ZH_TRY(hipEventRecord(C.ev[ZH_IEV_RG_END], 0));
+   if (zh_members_collect(C, n, results, kernel_ms ? kernel_ms + 2 : NULL)) return -1;
+   if (kernel_ms) {
+      kernel_ms[0] = zh_index_ms(C, false);
+      float select = 0.f, fill = 0.f, edges = 0.f;
+      (void)hipEventElapsedTime(&select, C.ev[ZH_IEV_ITEMS_START], C.ev[ZH_IEV_RG_PLAN]);
+      (void)hipEventElapsedTime(&fill, C.ev[ZH_IEV_RG_ITEMS], C.ev[ZH_IEV_ITEMS_END]);
+      (void)hipEventElapsedTime(&edges, C.ev[ZH_IEV_END], C.ev[ZH_IEV_RG_END]);
+      kernel_ms[1] = select + fill;
+      kernel_ms[4] += edges;
+   }
+   int bad = 0;
+   for (uint32_t k = 0; k < n; k++)
+      if (results[k].reason != 0) bad++;
+   if (!dst_on_device) ZH_TRY(hipMemcpy(dst, range8, out_size, hipMemcpyDeviceToHost));
+   return bad;
 }
 
 // ---- a ZIP archive read (zh_unzip.h) ------------------------------------------------------------------------------------------------------------------

@@ -9,7 +9,8 @@
  *    zultra_amd_cli [-b <max block size>] [-f gzip|zlib|raw] [-k <chunk KiB>] [-d <device>] [-D <dictionary>] [-c] [-v] <infile> <outfile>
  *    zultra_amd_cli -x [-f gzip|zlib|raw] [-d <device>] [-D <dictionary>] [-v] <infile> <outfile>
  *    zultra_amd_cli -x -m [-f gzip] [-d <device>] [-v] <infile> <outfile>
- *    zultra_amd_cli -f bgzf [-b <block size>] [-d <device>] [-c] [-v] <infile> <outfile>
+ *    zultra_amd_cli -x -m -r <first>:<length> [-i <file.gzi>] [-f gzip] [-d <device>] [-v] <infile> <outfile>
+ *    zultra_amd_cli -f bgzf [-b <block size>] [-i <file.gzi>] [-d <device>] [-c] [-v] <infile> <outfile>
  *    zultra_amd_cli -a <archive.zip> [-d <device>] [-c] [-v] <file>...
  *    zultra_amd_cli -x -a <archive.zip> [-d <device>] [-v] <outdir>
  *
@@ -21,6 +22,12 @@
  *     (zultra_memory_compress_zip). A file is one max-block: at most 2 MiB; an empty file is an empty entry. No dictionary.
  * -f bgzf: bgzip(1) — <infile> in blocks of -b bytes (default and at most 65280), every block a BGZF member written on the device, and BGZF's end marker
  *     (zultra_memory_compress_bgzf); `-x -m -f gzip` is the way back. No dictionary: a member stands alone.
+ * -r: with -x -m — only bytes <first> .. <first> + <length> of the concatenated output are written, and only the members that hold them are inflated
+ *     (zultra_memory_decompress_range); a range that reaches past the end of the file is cut there. With -i the .gzi index of the file is read and only the
+ *     compressed window the range needs is uploaded; the index is checked against what the window holds. With -v the first member decoded, their number and
+ *     the index's tiles are printed, from a query over the whole file (zultra_hip_inflate_range without room: nothing is decoded for it).
+ * -i: with -f bgzf — bgzip's .gzi index of the file written (zultra_memory_index_gzi over the output: one more index pass on the device): le64 N, then a pair
+ *     of le64 compressed offset, le64 uncompressed offset for every member but the first.
  * -D: a preset dictionary, loaded as the reference's tool loads it (zultra_dictionary_load: the last 32 KiB of the file; tool/zultra.c -D). Compressing,
  *     it is set before the first zultra_stream_compress (zultra_stream_set_dictionary: the history of the first max-block; a zlib header gets FDICT and
  *     the DICTID); with -x the stream is inflated against it (zultra_memory_decompress_dict: a zlib stream's DICTID must be this dictionary's).
@@ -49,7 +56,7 @@ static double now_s(void) {
 }
 
 /* -f bgzf: the whole file through zultra_memory_compress_bgzf */
-static int write_bgzf(FILE *fin, FILE *fout, unsigned block, int verbose, int verify) {
+static int write_bgzf(FILE *fin, FILE *fout, unsigned block, int verbose, int verify, const char *gzi_name) {
    size_t n = 0, cap = (size_t)1 << 20;
    unsigned char *in = (unsigned char *)malloc(cap);
    for (size_t got; in && (got = fread(in + n, 1, cap - n, fin)) > 0;) {
@@ -82,6 +89,19 @@ static int write_bgzf(FILE *fin, FILE *fout, unsigned block, int verbose, int ve
    if (verbose && !rc)
       fprintf(stdout, "%llu -> %llu bytes (%.2f %%), %.1f MB/s\n", (unsigned long long)n, (unsigned long long)size, n ? 100.0 * (double)size / (double)n : 0.0, dt > 0 ? (double)n / dt / 1e6 : 0.0);
    if (verbose && verify && !rc) fprintf(stdout, "verified %llu bytes on the device\n", zultra_verified_bytes());
+   if (gzi_name && !rc) {   /* -i: the index of what was written */
+      const size_t gzi_size = zultra_memory_index_gzi(out, size, NULL, 0);
+      unsigned char *gzi = gzi_size != (size_t)-1 ? (unsigned char *)malloc(gzi_size) : NULL;
+      FILE *fgzi = gzi ? fopen(gzi_name, "wb") : NULL;
+      if (!fgzi || zultra_memory_index_gzi(out, size, gzi, gzi_size) != gzi_size || fwrite(gzi, 1, gzi_size, fgzi) != gzi_size) {
+         fprintf(stderr, "error writing the index '%s'\n", gzi_name);
+         rc = 100;
+      }
+      else if (verbose)
+         fprintf(stdout, "index: %llu entries\n", (unsigned long long)((gzi_size - 8) / 16));
+      if (fgzi) fclose(fgzi);
+      free(gzi);
+   }
    zultra_release_cached_contexts();
    free(in);
    free(out);
@@ -336,11 +356,75 @@ static int extract(FILE *fin, FILE *fout, unsigned flags, int verbose, const voi
    return rc;
 }
 
+/* a whole file in memory; NULL (and a message) where it does not read */
+static unsigned char *read_file(FILE *f, size_t *size) {
+   size_t n = 0, cap = (size_t)1 << 20;
+   unsigned char *in = (unsigned char *)malloc(cap);
+   for (size_t got; in && (got = fread(in + n, 1, cap - n, f)) > 0;) {
+      n += got;
+      if (n == cap) {
+         unsigned char *more = (unsigned char *)realloc(in, cap *= 2);
+         if (!more) free(in);
+         in = more;
+      }
+   }
+   if (!in) fprintf(stderr, "out of memory\n");
+   *size = n;
+   return in;
+}
+
+/* -x -m -r: bytes first .. first + length of the file's output through zultra_memory_decompress_range, with the .gzi index where one is named */
+static int extract_range(FILE *fin, FILE *fout, unsigned long long first, unsigned long long length, const char *gzi_name, int verbose, int device) {
+   size_t n = 0, gzi_size = 0;
+   unsigned char *in = read_file(fin, &n), *gzi = NULL, *out = NULL;
+   int rc = in ? 0 : 100;
+   if (!rc && gzi_name) {
+      FILE *fgzi = fopen(gzi_name, "rb");
+      gzi = fgzi ? read_file(fgzi, &gzi_size) : NULL;
+      if (fgzi) fclose(fgzi);
+      if (!gzi) {
+         fprintf(stderr, "error reading the index '%s'\n", gzi_name);
+         rc = 100;
+      }
+   }
+   const unsigned long long bound = (unsigned long long)n * 1032 + 1024;   /* (a deflate stream expands at most 1032 : 1) */
+   const size_t room = (size_t)(length < bound ? length : bound);
+   if (!rc && !(out = (unsigned char *)malloc(room ? room : 1))) {
+      fprintf(stderr, "out of memory\n");
+      rc = 100;
+   }
+   if (!rc) {
+      const double t0 = now_s();
+      const size_t size = zultra_memory_decompress_range(in, n, first, room, out, room, gzi, gzi_size);
+      const double dt = now_s() - t0;
+      if (size == (size_t)-1) {
+         fprintf(stderr, "decompression error (a damaged member in the range, no BGZF file, an index that does not fit the file, or no HIP device: this library has no CPU path)\n");
+         rc = 100;
+      }
+      else if (size && fwrite(out, 1, size, fout) != size) {
+         fprintf(stderr, "write error\n");
+         rc = 100;
+      }
+      if (verbose && !rc) {
+         zultra_hip_range_result_t rg;
+         memset(&rg, 0, sizeof(rg));
+         (void)zultra_hip_inflate_range(device, in, n, 0, first, room, out, 0, 0, &rg, NULL, 0, NULL);   /* (no room: a query, nothing is decoded) */
+         fprintf(stdout, "%llu bytes from %llu, %.1f MB/s; first member %u, %u members of %u; the index: %u tiles, %u rewalked\n", (unsigned long long)size, first,
+                 dt > 0 ? (double)size / dt / 1e6 : 0.0, rg.first_member, rg.range_members, rg.members, rg.tiles, rg.tiles_rewalked);
+      }
+   }
+   free(in);
+   free(gzi);
+   free(out);
+   return rc;
+}
+
 int main(int argc, char **argv) {
    unsigned flags = ZULTRA_FLAG_GZIP_FRAMING, block = 0;
    size_t chunk = (size_t)8 << 20;
    int verbose = 0, verify = 0, do_extract = 0, members = 0, device = 0, bgzf = 0, i = 1;
-   const char *dict_name = NULL, *archive = NULL;
+   const char *dict_name = NULL, *archive = NULL, *range = NULL, *gzi_name = NULL;
+   unsigned long long range_first = 0, range_length = 0;
    if (getenv("ZULTRA_HIP_DEVICE")) device = atoi(getenv("ZULTRA_HIP_DEVICE"));   /* (the library's own default: -m sizes its buffer with an index call on the same device) */
    for (; i < argc && argv[i][0] == '-' && argv[i][1]; i++) {
       if (!strcmp(argv[i], "-b") && i + 1 < argc)
@@ -358,6 +442,10 @@ int main(int argc, char **argv) {
          dict_name = argv[++i];
       else if (!strcmp(argv[i], "-a") && i + 1 < argc)
          archive = argv[++i];
+      else if (!strcmp(argv[i], "-r") && i + 1 < argc)
+         range = argv[++i];
+      else if (!strcmp(argv[i], "-i") && i + 1 < argc)
+         gzi_name = argv[++i];
       else if (!strcmp(argv[i], "-v"))
          verbose = 1;
       else if (!strcmp(argv[i], "-x"))
@@ -375,13 +463,29 @@ int main(int argc, char **argv) {
       fprintf(stderr, "-b %u: a BGZF block holds at most %u bytes of input\n", block, ZULTRA_HIP_BGZF_BLOCK);
       return 100;
    }
+   int range_ok = 1;
+   if (range) {   /* <first>:<length>, both decimal */
+      char *end = NULL;
+      range_first = strtoull(range, &end, 10);
+      range_ok = end != range && *end == ':' && end[1] >= '0' && end[1] <= '9';
+      if (range_ok) {
+         const char *len = end + 1;
+         range_length = strtoull(len, &end, 10);
+         range_ok = *end == 0;
+      }
+   }
+   if (!range_ok || (range && (!members || archive)) || (gzi_name && !(range || (bgzf && !do_extract)))) {
+      fprintf(stderr, "-r <first>:<length> goes with -x -m; -i <file.gzi> with -f bgzf (written) or with -x -m -r (read)\n");
+      return 100;
+   }
    if (archive ? ((do_extract ? argc - i != 1 || members || verify : argc - i < 1) || bgzf || dict_name) : argc - i != 2 || chunk == 0 || (members && (!do_extract || flags != ZULTRA_FLAG_GZIP_FRAMING || dict_name)) || (bgzf && !do_extract && dict_name)) {
       fprintf(stderr, "usage: %s [-b <max block size>] [-f gzip|zlib|raw] [-k <chunk KiB>] [-d <device>] [-D <dictionary>] [-c] [-v] <infile> <outfile>\n"
                       "       %s -x [-f gzip|zlib|raw] [-d <device>] [-D <dictionary>] [-v] <infile> <outfile>\n"
                       "       %s -x -m [-f gzip] [-d <device>] [-v] <infile> <outfile>   (any number of gzip members: BGZF, pigz -i, cat a.gz b.gz)\n"
-                      "       %s -f bgzf [-b <block size, at most 65280>] [-d <device>] [-c] [-v] <infile> <outfile>   (BGZF members and the end marker)\n"
+                      "       %s -x -m -r <first>:<length> [-i <file.gzi>] [-f gzip] [-d <device>] [-v] <infile> <outfile>   (a byte range of a BGZF file's output)\n"
+                      "       %s -f bgzf [-b <block size, at most 65280>] [-i <file.gzi>] [-d <device>] [-c] [-v] <infile> <outfile>   (BGZF members and the end marker)\n"
                       "       %s -a <archive.zip> [-d <device>] [-c] [-v] <file>...   (a ZIP archive: every file, of at most 2 MiB, an entry under its name)\n"
-                      "       %s -x -a <archive.zip> [-d <device>] [-v] <outdir>   (unpack a ZIP archive: stored and deflated entries, checked on the device)\n", argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
+                      "       %s -x -a <archive.zip> [-d <device>] [-v] <outdir>   (unpack a ZIP archive: stored and deflated entries, checked on the device)\n", argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
       return 100;
    }
    if (archive && do_extract) return extract_zip(archive, argv[i], verbose, device);
@@ -404,6 +508,12 @@ int main(int argc, char **argv) {
       fclose(fin);
       return 100;
    }
+   if (do_extract && range) {
+      const int xrc = extract_range(fin, fout, range_first, range_length, gzi_name, verbose, device);
+      fclose(fin);
+      fclose(fout);
+      return xrc;
+   }
    if (do_extract) {
       const int xrc = extract(fin, fout, flags, verbose, dict, dict_size, members, device);
       fclose(fin);
@@ -412,7 +522,7 @@ int main(int argc, char **argv) {
       return xrc;
    }
    if (bgzf) {
-      const int brc = write_bgzf(fin, fout, block, verbose, verify);
+      const int brc = write_bgzf(fin, fout, block, verbose, verify, gzi_name);
       fclose(fin);
       fclose(fout);
       return brc;

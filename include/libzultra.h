@@ -217,6 +217,21 @@ size_t zultra_memory_bound_zip(size_t nInTotal, size_t nNamesTotal, size_t n);
 size_t zultra_memory_compress_zip(const unsigned char *pIn, size_t nIn, const size_t *pInOff, const size_t *pInSize,
                                   const char *pNames, const size_t *pNameOff /* n + 1 */, size_t n,
                                   unsigned char *pOut, size_t nMaxOut, unsigned int nDosDateTime);
+/* The same two calls for inputs of ANY size: an input is a run of max-blocks of nMaxBlockSize bytes (clamped like zultra_memory_compress's: 0 = 1 MiB, then
+ * 32768 .. 2 MiB) that carries its bit phase and its history from max-block to max-block, and many such streams share a device batch (include/zultra_hip.h: the
+ * grouped assembly, zultra_hip_frame_streams / zultra_hip_zip_streams). Member i — entry i's data — is byte for byte zultra_memory_compress(input i, nFlags,
+ * nMaxBlockSize), for any input size. The inputs are gathered into pinned staging one behind the other; a stream lies wholly in one batch, and there are as many
+ * batches as the context's max-blocks (ZULTRA_HIP_BATCH_BLOCKS) and data capacity need. LIMIT: an input with more max-blocks than one context holds is
+ * refused — zultra_memory_compress remains the call for one huge input. zultra_memory_compress_streams refuses an empty input, zultra_memory_compress_zip_streams
+ * makes it an empty entry. nMaxOut: the sum of zultra_memory_bound(size i, nFlags, nMaxBlockSize) suffices; for the archive (nFlags 0) add both copies of the
+ * names, 76 bytes per entry, and 98. Everything else — arguments, pOutOff, names, nDosDateTime, the 0xFFFFFFFF limit of an archive, (size_t)-1, one device, the
+ * verification of every batch after framing with zultra_set_verify — is as for the two calls above. */
+size_t zultra_memory_compress_streams(const unsigned char *pIn, size_t nIn, const size_t *pInOff, const size_t *pInSize, size_t n,
+                                      unsigned char *pOut, size_t nMaxOut, size_t *pOutOff /* n + 1, written */, const unsigned int nFlags /* 0, ZLIB, GZIP */,
+                                      unsigned int nMaxBlockSize);
+size_t zultra_memory_compress_zip_streams(const unsigned char *pIn, size_t nIn, const size_t *pInOff, const size_t *pInSize,
+                                          const char *pNames, const size_t *pNameOff /* n + 1 */, size_t n,
+                                          unsigned char *pOut, size_t nMaxOut, unsigned int nDosDateTime, unsigned int nMaxBlockSize);
 /* The end of a ZIP archive, for callers who assemble one from the device layer's parts: the end of central directory record (22 bytes), and in front of it, with
  * more than 65535 entries, the ZIP64 end record and its locator (98 bytes in all). Pure host code. Returns the bytes written, or (size_t)-1: nMaxOut too small,
  * or nCentralOff or nCentralSize at or above 0xFFFFFFFF. */

@@ -453,6 +453,39 @@ int zultra_hip_zip_read(zultra_hip_ctx_t *ctx, void *out, size_t offset, size_t 
 void zultra_hip_last_zip_ms(const zultra_hip_ctx_t *ctx, float *ms /* [3]: scan, records, copy */);
 
 /*
+ * Streams of several max-blocks in one batch: the GROUPED assembly. A grouping of the last batch is stream_first[0 .. nstreams), host, max-block
+ * indices: stream_first[0] == 0, strictly increasing, below the batch's block count; stream s is max-blocks stream_first[s] .. stream_first[s + 1] - 1, the last
+ * stream runs to the end of the batch. It is valid only if the first max-block of every stream has prev == 0 and every other max-block b continues b - 1:
+ * win_off[b] + prev[b] == win_off[b-1] + prev[b-1] + n[b-1], prev[b] == min(32768, the stream's bytes in front of b), and n[b-1] == the context's max-block size.
+ * Under these rules stream s is BYTE FOR BYTE what zultra_memory_compress(input s, framing, the context's max-block size) produces: inside a stream the bit phase
+ * is carried from max-block to max-block and the history is real, between streams there is a BFINAL and a byte-aligned restart. Anything else returns -1 and
+ * nothing is written. Explicit assembly only: nothing of it goes out with a batch (no zultra_hip_stitch_with_batch, no captured graph), and after it
+ * zultra_hip_stitch_files, zultra_hip_stitch_device, zultra_hip_frame_members and zultra_hip_zip_members behave as after any other explicit assembly;
+ * zultra_hip_verify_device verifies it.
+ * zultra_hip_frame_streams: the streams as members back to back in the stream buffer.
+ *   framing  : 0 (raw deflate streams back to back), ZULTRA_FLAG_ZLIB_FRAMING or ZULTRA_FLAG_GZIP_FRAMING; BGZF is -1 — a BGZF member cannot hold several max-blocks
+ *   members  : host, nstreams: off, size, check = the stream's Adler-32 / CRC-32 (0 for raw), flags = 0. gzip's ISIZE is the stream's size
+ * Returns as zultra_hip_frame_members: 0; -1 for bad arguments, an invalid grouping, no batch, HIP errors; -2 where the reference fails with ZULTRA_ERROR_DST, the
+ * members do not fit the stream buffer, or a stream reaches 2^32 bytes. Nothing is written for -1 and -2.
+ * zultra_hip_zip_streams: zultra_hip_zip_members with the streams as entries — entry_stream[i] is the stream of entry i or 0xFFFFFFFF for an empty entry, the streams
+ * named are every stream of the grouping once, in increasing order (NULL: entry i is stream i); names, name_off, base_off, dos_datetime, entries, local_bytes,
+ * central_bytes, the 0xFFFFFFFF limit and the return codes are zultra_hip_zip_members'. It gathers from the plain grouped form (framing 0) where the stream buffer
+ * holds it FOR THE SAME GROUPING, and assembles it first otherwise.
+ */
+int zultra_hip_frame_streams(zultra_hip_ctx_t *ctx, const uint32_t *stream_first /* host, nstreams */, uint32_t nstreams, unsigned int framing,
+                             zultra_hip_member_t *members /* host, nstreams */, uint64_t *total_bytes);
+int zultra_hip_zip_streams(zultra_hip_ctx_t *ctx, const uint32_t *stream_first /* host, nstreams */, uint32_t nstreams, const void *names, const uint32_t *name_off /* n + 1, host */,
+                           const uint32_t *entry_stream /* n, host; NULL: entry i = stream i */, uint32_t n, uint64_t base_off, uint32_t dos_datetime,
+                           zultra_hip_zip_entry_t *entries /* host, n; may be NULL */, uint64_t *local_bytes, uint64_t *central_bytes);
+/* A measurement hook (tools/streams_time.py): device time of the last grouped assembly's launches, milliseconds. */
+void zultra_hip_last_streams_ms(const zultra_hip_ctx_t *ctx, float *ms /* [3]: scan, fold, frame kernel */);
+/* Diagnostics (tests): the items of the last assembly's scan, per sub-block {u64 dst_bit, u32 stored, u32 is_final} — returns their count, -1 on errors —; and what the
+ * host's serial statement of the grouped rule gives for a grouping of the last batch: the same items (nsubs; may be NULL), file_off (nstreams + 1; may be NULL) and
+ * *end_bit. 0; -1 for an invalid grouping or framing; -2 where the reference fails with ZULTRA_ERROR_DST or a stream reaches 2^32 bytes. */
+int zultra_hip_stitch_items(zultra_hip_ctx_t *ctx, void *items /* nsubs x 16 bytes */);
+int zultra_hip_plan_streams(zultra_hip_ctx_t *ctx, const uint32_t *stream_first, uint32_t nstreams, unsigned int framing, void *items, uint64_t *file_off, uint64_t *end_bit);
+
+/*
  * A ZIP archive READ: the central directory indexed on the device, then every entry checked against its local header, inflated or copied,
  * and its CRC-32 taken and compared there. The caller names the directory — src[central_at .. central_at + central_size), from zultra_zip_find_end
  * (libzultra.h) or from zultra_hip_zip_device —, the device finds the records: one starts at p when 46 bytes lie in front of the directory's end, src[p..p+4) =

@@ -115,6 +115,7 @@ ZIP_DIRENT_DTYPE = [("central_at", "<u8"), ("local_off", "<u8"), ("dst_off", "<u
                     ("method", "<u2"), ("flags", "<u2"), ("extra_len", "<u2"), ("comment_len", "<u2")]   # zultra_hip_zip_dirent_t
 ZIP_INFO_DTYPE = np.dtype([("nNameAt", "<u8"), ("nNameLen", "<u4"), ("nMethod", "<u4"), ("nFlags", "<u4"), ("nCrc32", "<u4"), ("nCompSize", "<u4"), ("nSize", "<u4"),
                            ("nOutOff", "<u8"), ("nStatus", "<u4")], align=True)   # zultra_zip_info_t
+STITCH_ITEM_DTYPE = [("dst_bit", "<u8"), ("stored", "<u4"), ("is_final", "<u4")]   # zh_stitch_item_t (zultra_hip_stitch_items)
 MEMBER_RESULT_DTYPE = [("reason", "<u4"), ("blocks", "<u4"), ("out_size", "<u8"), ("src_used", "<u8"), ("head_size", "<u4"), ("check", "<u4")]
 
 
@@ -147,6 +148,9 @@ EXPORTS = [
     "zultra_hip_zip_members", "zultra_hip_zip_device", "zultra_hip_zip_read", "zultra_hip_last_zip_ms",
     "zultra_zip_end_records", "zultra_memory_bound_zip", "zultra_memory_compress_zip",
     "zultra_hip_zip_index", "zultra_hip_unzip", "zultra_zip_find_end", "zultra_memory_decompress_zip",
+    # streams of several max-blocks in one batch
+    "zultra_hip_frame_streams", "zultra_hip_zip_streams", "zultra_hip_last_streams_ms", "zultra_hip_stitch_items", "zultra_hip_plan_streams",
+    "zultra_memory_compress_streams", "zultra_memory_compress_zip_streams",
 ]
 
 
@@ -513,6 +517,46 @@ class Lib:
         f.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint]
         f.restype = C.c_size_t
         r = f(data.ctypes.data if len(data) else None, len(data), in_off.ctypes.data, in_size.ctypes.data, blob.ctypes.data, name_off.ctypes.data, n, out.ctypes.data, cap, dos_datetime)
+        return None if r == _SIZE_MAX else out[:r].tobytes()
+
+    def memory_compress_streams(self, data, inputs, flags, max_block=0, cap=None):
+        """zultra_memory_compress_streams over the inputs [(offset, size)] of `data`, of any size: one member of framing `flags` each, back to back.
+        -> (the bytes, out_off as n + 1 integers), or (None, None) where the call returns (size_t)-1. cap: bytes of room, default the sum of the bounds."""
+        data = _as_u8(data)
+        n = len(inputs)
+        in_off = np.array([m[0] for m in inputs], dtype=np.uintp)
+        in_size = np.array([m[1] for m in inputs], dtype=np.uintp)
+        if cap is None:
+            cap = sum(self.memory_bound(int(m[1]), flags, max_block) for m in inputs)
+        out = np.empty(max(cap, 1), dtype=np.uint8)
+        out_off = np.zeros(n + 1, dtype=np.uintp)
+        f = self.L.zultra_memory_compress_streams
+        f.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint, C.c_uint]
+        f.restype = C.c_size_t
+        r = f(data.ctypes.data, len(data), in_off.ctypes.data, in_size.ctypes.data, n, out.ctypes.data, cap, out_off.ctypes.data, flags, max_block)
+        if r == _SIZE_MAX:
+            return None, None
+        return out[:r].tobytes(), [int(v) for v in out_off]
+
+    def memory_compress_zip_streams(self, data, inputs, names, dos_datetime=0, max_block=0, cap=None):
+        """zultra_memory_compress_zip_streams: memory_compress_zip for inputs of any size, as streams of max-blocks of max_block bytes. -> the archive's
+        bytes, or None where the call returns (size_t)-1. cap: bytes of room, default the sum of the bounds, both copies of the names, 76 per entry and 98."""
+        data = _as_u8(data)
+        n = len(inputs)
+        names = [s.encode("utf-8") if isinstance(s, str) else bytes(s) for s in names]
+        assert len(names) == n
+        blob = _as_u8(b"".join(names) + b"\0")
+        name_off = np.concatenate([[0], np.cumsum([len(s) for s in names])]).astype(np.uintp)
+        in_off = np.array([m[0] for m in inputs], dtype=np.uintp)
+        in_size = np.array([m[1] for m in inputs], dtype=np.uintp)
+        if cap is None:
+            cap = sum(self.memory_bound(int(m[1]), 0, max_block) for m in inputs) + 2 * int(name_off[-1]) + 76 * n + 98
+        out = np.empty(max(cap, 1), dtype=np.uint8)
+        f = self.L.zultra_memory_compress_zip_streams
+        f.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint, C.c_uint]
+        f.restype = C.c_size_t
+        r = f(data.ctypes.data if len(data) else None, len(data), in_off.ctypes.data, in_size.ctypes.data, blob.ctypes.data, name_off.ctypes.data, n, out.ctypes.data, cap, dos_datetime,
+              max_block)
         return None if r == _SIZE_MAX else out[:r].tobytes()
 
     def zip_index(self, src, src_size, central_at, central_size, cap, device=0):
@@ -899,6 +943,71 @@ class HipContext:
         f.restype = C.c_int
         rc = f(self.h, blob.ctypes.data, name_off.ctypes.data, None if eb is None else eb.ctypes.data, n, base_off, dos_datetime, entries.ctypes.data, C.byref(local), C.byref(central))
         return rc, entries[:n], int(local.value), int(central.value), self.zip_ptr()[1]
+
+    def frame_streams(self, stream_first, framing):
+        """zultra_hip_frame_streams over the last batch: stream s = max-blocks stream_first[s] .. stream_first[s + 1] - 1, a complete member of `framing`
+        (0, FLAG_ZLIB, FLAG_GZIP) each. -> (rc, members as a MEMBER_DTYPE array, total_bytes); rc 0, or -1 / -2 as the call returns them."""
+        first = np.ascontiguousarray(stream_first, dtype=np.uint32)
+        members = np.zeros(max(len(first), 1), dtype=MEMBER_DTYPE)
+        total = C.c_uint64(0)
+        f = self.lib.L.zultra_hip_frame_streams
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint, C.c_void_p, C.POINTER(C.c_uint64)]
+        f.restype = C.c_int
+        rc = f(self.h, first.ctypes.data if len(first) else None, len(first), framing, members.ctypes.data, C.byref(total))
+        return rc, members[:len(first)], int(total.value)
+
+    def zip_streams(self, stream_first, names, entry_stream=None, base_off=0, dos_datetime=0):
+        """zultra_hip_zip_streams over the last batch: zip_members with the streams of the grouping stream_first as entries. -> (rc, entries as a
+        ZIP_ENTRY_DTYPE array, local_bytes, central_bytes, central_at)."""
+        first = np.ascontiguousarray(stream_first, dtype=np.uint32)
+        names = [s.encode("utf-8") if isinstance(s, str) else bytes(s) for s in names]
+        n = len(names)
+        blob = _as_u8(b"".join(names) + b"\0")
+        name_off = np.concatenate([[0], np.cumsum([len(s) for s in names])]).astype(np.uint32)
+        es = None if entry_stream is None else np.ascontiguousarray(entry_stream, dtype=np.uint32)
+        entries = np.zeros(max(n, 1), dtype=ZIP_ENTRY_DTYPE)
+        local, central = C.c_uint64(0), C.c_uint64(0)
+        f = self.lib.L.zultra_hip_zip_streams
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        f.restype = C.c_int
+        rc = f(self.h, first.ctypes.data if len(first) else None, len(first), blob.ctypes.data, name_off.ctypes.data, None if es is None else es.ctypes.data, n, base_off, dos_datetime,
+               entries.ctypes.data, C.byref(local), C.byref(central))
+        return rc, entries[:n], int(local.value), int(central.value), self.zip_ptr()[1]
+
+    def streams_ms(self):
+        """Device time of the last grouped assembly's launches, milliseconds: (scan, fold, frame kernel)."""
+        ms = (C.c_float * 3)()
+        f = self.lib.L.zultra_hip_last_streams_ms
+        f.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+        f.restype = None
+        f(self.h, ms)
+        return [float(v) for v in ms]
+
+    def stitch_items(self):
+        """zultra_hip_stitch_items -> the items of the last assembly's scan, a STITCH_ITEM_DTYPE array (one per sub-block)."""
+        cnt = C.c_uint32()
+        self.lib.L.zultra_hip_subblocks(self.h, C.byref(cnt))
+        items = np.zeros(max(cnt.value, 1), dtype=STITCH_ITEM_DTYPE)
+        f = self.lib.L.zultra_hip_stitch_items
+        f.argtypes = [C.c_void_p, C.c_void_p]
+        f.restype = C.c_int
+        if f(self.h, items.ctypes.data) != cnt.value:
+            raise ZultraError("zultra_hip_stitch_items")
+        return items[:cnt.value]
+
+    def plan_streams(self, stream_first, framing):
+        """zultra_hip_plan_streams: the host planner's statement of a grouped assembly of the last batch -> (rc, items, file_off, end_bit)."""
+        first = np.ascontiguousarray(stream_first, dtype=np.uint32)
+        cnt = C.c_uint32()
+        self.lib.L.zultra_hip_subblocks(self.h, C.byref(cnt))
+        items = np.zeros(max(cnt.value, 1), dtype=STITCH_ITEM_DTYPE)
+        file_off = np.zeros(len(first) + 1, dtype=np.uint64)
+        end = C.c_uint64(0)
+        f = self.lib.L.zultra_hip_plan_streams
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
+        f.restype = C.c_int
+        rc = f(self.h, first.ctypes.data if len(first) else None, len(first), framing, items.ctypes.data, file_off.ctypes.data, C.byref(end))
+        return rc, items[:cnt.value], file_off, int(end.value)
 
     def zip_ptr(self):
         """zultra_hip_zip_device -> (the device pointer of the zip buffer, or None before the first zip_members; where the central part starts in it)."""

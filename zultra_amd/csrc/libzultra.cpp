@@ -1347,6 +1347,129 @@ extern "C" size_t zultra_memory_compress_zip(const unsigned char *pIn, size_t nI
    return (size_t)-1;
 }
 
+// ---- inputs of any size as streams of several max-blocks in one batch (include/zultra_hip.h: the grouped assembly) -----------------------------------
+// The batches of n inputs, each a run of max-blocks of bs bytes with real history (batch_describe), under zultra_memory_compress_streams and
+// zultra_memory_compress_zip_streams. An input lies wholly in one batch; a batch takes inputs while the context has max-blocks left. The inputs are gathered into
+// the context's pinned staging one behind the other, and per_batch(context, stage, bytes, blocks, stream_first, i, j) does the rest for the inputs i .. j - 1 —
+// stream_first has one entry per non-empty input of them. Empty inputs as in for_input_batches. Returns false where anything fails, an input with more
+// max-blocks than the context holds among it.
+template <typename F>
+static bool for_stream_batches(const unsigned char *pIn, size_t nIn, const size_t *pInOff, const size_t *pInSize, size_t n, uint32_t bs, bool allow_empty, F per_batch) {
+   uint64_t total_blocks = 0, most = 0;
+   for (size_t i = 0; i < n; i++) {
+      if (!pInSize[i] && allow_empty) continue;
+      if (!pInSize[i] || pInSize[i] > nIn || pInOff[i] > nIn - pInSize[i] || pInSize[i] >= 0xFFFFFFFFull) return false;
+      const uint64_t nb = ((uint64_t)pInSize[i] + bs - 1) / bs;
+      total_blocks += nb;
+      most = nb > most ? nb : most;
+   }
+   if (!total_blocks) return true;
+   const int dev = zh_pick_device();
+   const uint32_t cap = ctx_blocks(dev, bs, total_blocks);
+   if (most > cap) return false;   // (one huge input is zultra_memory_compress's business)
+   zultra_hip_ctx_t *c = ctx_acquire_on(dev, bs, cap);
+   if (!c) return false;
+   std::vector<zultra_hip_block_t> blocks;
+   std::vector<uint32_t> stream_first;
+   bool ok = true;
+   for (size_t i = 0; ok && i < n;) {
+      size_t j = i, bytes = 0;
+      blocks.clear();
+      stream_first.clear();
+      for (; j < n; j++) {
+         if (!pInSize[j]) continue;
+         const size_t nb = (pInSize[j] + bs - 1) / bs;
+         if (blocks.size() + nb > cap) break;
+         stream_first.push_back((uint32_t)blocks.size());
+         blocks.resize(blocks.size() + nb);
+         zultra_hip_block_t *first = blocks.data() + stream_first.back();
+         batch_describe(first, 0, bs, nb, (uint32_t)(pInSize[j] - (nb - 1) * bs));
+         for (size_t k = 0; k < nb; k++) first[k].win_off += bytes;
+         bytes += pInSize[j];
+      }
+      uint8_t *stage = blocks.empty() ? NULL : (uint8_t *)zultra_hip_staging(c, 0, bytes);
+      if (!stage) {
+         ok = false;
+         break;
+      }
+      for (size_t k = i, s = 0; k < j; k++)
+         if (pInSize[k]) zh_threaded_copy(stage + blocks[stream_first[s++]].win_off, pIn + pInOff[k], pInSize[k], 8u << 20);
+      ok = per_batch(c, stage, bytes, blocks, stream_first, i, j);
+      i = j;
+   }
+   ctx_release(c);
+   return ok;
+}
+
+extern "C" size_t zultra_memory_compress_streams(const unsigned char *pIn, size_t nIn, const size_t *pInOff, const size_t *pInSize, size_t n, unsigned char *pOut, size_t nMaxOut,
+                                                 size_t *pOutOff, const unsigned int nFlags, unsigned int nMaxBlockSize) try {
+   if (!pIn || !pInOff || !pInSize || !n || !pOut || !pOutOff || (nFlags != 0 && nFlags != ZULTRA_FLAG_ZLIB_FRAMING && nFlags != ZULTRA_FLAG_GZIP_FRAMING) || zultra_hip_device_count() <= 0)
+      return (size_t)-1;
+   std::vector<zultra_hip_member_t> members;
+   size_t w = 0;
+   const bool ok = for_stream_batches(pIn, nIn, pInOff, pInSize, n, zh_clamp_block(nMaxBlockSize), false,
+                                      [&](zultra_hip_ctx_t *c, const uint8_t *stage, size_t bytes, const std::vector<zultra_hip_block_t> &blocks, const std::vector<uint32_t> &stream_first, size_t i, size_t j) {
+      uint64_t total = 0;
+      members.resize(j - i);
+      if (zultra_hip_compress_blocks(c, stage, bytes, 0, blocks.data(), (uint32_t)blocks.size()) <= 0) return false;
+      if (zultra_hip_frame_streams(c, stream_first.data(), (uint32_t)stream_first.size(), nFlags, members.data(), &total) != 0) return false;
+      if (zh_verify_on() && !zh_verify_stitched(c)) return false;
+      if (total > nMaxOut - w || zultra_hip_stream_read(c, pOut + w, 0, (size_t)total) != 0) return false;
+      for (size_t k = i; k < j; k++) pOutOff[k] = w + (size_t)members[k - i].off;
+      w += (size_t)total;
+      return true;
+   });
+   if (!ok) return (size_t)-1;
+   pOutOff[n] = w;
+   return w;
+} catch (...) {
+   return (size_t)-1;
+}
+
+extern "C" size_t zultra_memory_compress_zip_streams(const unsigned char *pIn, size_t nIn, const size_t *pInOff, const size_t *pInSize, const char *pNames, const size_t *pNameOff, size_t n,
+                                                     unsigned char *pOut, size_t nMaxOut, unsigned int nDosDateTime, unsigned int nMaxBlockSize) try {
+   if (!pInOff || !pInSize || !pNames || !pNameOff || !n || !pOut) return (size_t)-1;
+   size_t nempty = 0;
+   for (size_t i = 0; i < n; i++) nempty += !pInSize[i];
+   if (nempty == n) return zultra_memory_compress_zip(pIn, nIn, pInOff, pInSize, pNames, pNameOff, n, pOut, nMaxOut, nDosDateTime);   // (no batch: the records are the host's)
+   for (size_t i = 0; i < n; i++)
+      if (pNameOff[i + 1] <= pNameOff[i] || pNameOff[i + 1] - pNameOff[i] > 65535) return (size_t)-1;
+   if (pNameOff[n] - pNameOff[0] >= 0xFFFFFFFFull || !pIn || zultra_hip_device_count() <= 0) return (size_t)-1;
+   const unsigned int dos = nDosDateTime ? nDosDateTime : 0x00210000u;
+   std::vector<unsigned char> central;
+   std::vector<uint32_t> name_off, entry_stream;
+   std::vector<zultra_hip_member_t> members;
+   size_t w = 0;
+   const bool ok = for_stream_batches(pIn, nIn, pInOff, pInSize, n, zh_clamp_block(nMaxBlockSize), true,
+                                      [&](zultra_hip_ctx_t *c, const uint8_t *stage, size_t bytes, const std::vector<zultra_hip_block_t> &blocks, const std::vector<uint32_t> &stream_first, size_t i, size_t j) {
+      const uint32_t nstreams = (uint32_t)stream_first.size();
+      if (zultra_hip_compress_blocks(c, stage, bytes, 0, blocks.data(), (uint32_t)blocks.size()) <= 0) return false;
+      if (zh_verify_on()) {   // (on the plain grouped layout, which the gather then finds in place)
+         uint64_t total = 0;
+         members.resize(nstreams);
+         if (zultra_hip_frame_streams(c, stream_first.data(), nstreams, 0, members.data(), &total) != 0 || !zh_verify_stitched(c)) return false;
+      }
+      name_off.resize(j - i + 1);
+      entry_stream.resize(j - i);
+      for (size_t k = i; k <= j; k++) name_off[k - i] = (uint32_t)(pNameOff[k] - pNameOff[i]);
+      for (size_t k = i, s = 0; k < j; k++) entry_stream[k - i] = pInSize[k] ? (uint32_t)s++ : 0xFFFFFFFFu;
+      uint64_t local = 0, cent = 0, central_at = 0;
+      if (zultra_hip_zip_streams(c, stream_first.data(), nstreams, pNames + pNameOff[i], name_off.data(), entry_stream.data(), (uint32_t)(j - i), w, dos, NULL, &local, &cent) != 0) return false;
+      if (local > nMaxOut - w || zultra_hip_zip_read(c, pOut + w, 0, (size_t)local) != 0) return false;
+      (void)zultra_hip_zip_device(c, &central_at);
+      central.resize(central.size() + (size_t)cent);
+      if (zultra_hip_zip_read(c, central.data() + central.size() - (size_t)cent, (size_t)central_at, (size_t)cent) != 0) return false;
+      w += (size_t)local;
+      return true;
+   });
+   if (!ok || central.size() > nMaxOut - w) return (size_t)-1;
+   memcpy(pOut + w, central.data(), central.size());
+   const size_t end = zultra_zip_end_records(pOut + w + central.size(), nMaxOut - w - central.size(), n, w, central.size());
+   return end == (size_t)-1 ? end : w + central.size() + end;
+} catch (...) {
+   return (size_t)-1;
+}
+
 // ================================================================================================================
 // Decompression: the framing on the host, the deflate stream on the device (zultra_hip_inflate_streams)
 // ================================================================================================================

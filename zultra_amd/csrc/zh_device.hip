@@ -24,6 +24,7 @@
 #include "zh_stitch.h"
 #include "zh_frame.h"
 #include "zh_zip.h"
+#include "zh_streams.h"
 #include "zh_verify.h"
 
 #define ZH_MAX_RUNS 8           // staggered runs of a batch (ZULTRA_HIP_STREAMS)
@@ -73,11 +74,14 @@ static void zh_graph_clear(zh_graph_set_t *G) {
 // of its own (files); scan_only: the scan's report and nothing else (zultra_hip_stitch_phase_table); framed (files form only, zultra_hip_frame_members): room for a
 // header and a trailer around every stream, and the kernel that fills it
 struct zh_frame_args_t { uint32_t framing, eof; };   // (eof: bytes of end marker behind the last member)
+struct zh_group_args_t { uint32_t nstreams; uint64_t hash; };   // (the grouped form, zh_streams.h: how many streams, and a hash of their first max-blocks)
 struct zh_stitch_job_t {
    uint32_t phase;
    int final_block;
    bool files, scan_only, framed;
    zh_frame_args_t frame;   // (framed)
+   bool streams;            // the grouped form: runs of max-blocks as streams, always with a frame kernel behind it (framing 0: it writes the members' records alone)
+   zh_group_args_t group;   // (streams)
 };
 
 // What the stream buffer holds of the last batch — the one record every call that assembles writes and every call that reads the buffer asks (zh_assembly_*
@@ -87,16 +91,19 @@ struct zh_stitch_job_t {
 //    assembly, {FILES, gap 0, with_batch, rc}. A failed verdict is kept (rc != 0): the call that asks for that assembly returns the rc without launching, and
 //    nothing usable is there for verify and zip.
 //  * Every explicit assembly — zultra_hip_stitch_device with no matching with-batch result, zultra_hip_stitch_files, zultra_hip_frame_members,
-//    zultra_hip_stitch_phase_table, the one inside zultra_hip_zip_members — clears the record before it enqueues (the items and the scan's report are rewritten) and,
+//    zultra_hip_stitch_phase_table, zultra_hip_frame_streams, the ones inside zultra_hip_zip_members and zultra_hip_zip_streams — clears the record before it enqueues (the items and the scan's report are rewritten) and,
 //    if it succeeds and moved bits, records its layout with with_batch = false. A failed one and the phase table's scan leave NONE: verify refuses behind them.
 //  * Only a with-batch result is handed out without a launch; an explicit assembly asked for again is done again (a caller may have written the buffer,
 //    zultra_hip_stream_write). zultra_hip_zip_members gathers from whatever plain files form the buffer holds, with-batch or explicit.
-enum zh_layout_t { ZH_LAYOUT_NONE, ZH_LAYOUT_STREAM, ZH_LAYOUT_FILES };
+//  * The grouped form (STREAMS) is explicit only. It remembers its grouping: zultra_hip_zip_streams gathers from a plain grouped form of THE SAME grouping and
+//    assembles otherwise; to every other call it is just not the layout that call asks for.
+enum zh_layout_t { ZH_LAYOUT_NONE, ZH_LAYOUT_STREAM, ZH_LAYOUT_FILES, ZH_LAYOUT_STREAMS };
 struct zh_assembly_t {
    zh_layout_t layout;    // what d_stream / d_items / d_scan_out (and d_file_off) describe
    uint32_t phase;        // STREAM: the phase it starts at
    int final_block;       // STREAM: the final block it was stitched with
-   uint32_t gap;          // FILES: head + tail bytes between the streams (0: the plain form)
+   uint32_t gap;          // FILES, STREAMS: head + tail bytes between the streams (0: the plain form)
+   zh_group_args_t group; // STREAMS: the grouping it was built with
    bool with_batch;       // it went out behind the batch's kernels (the armed stitch, a files context's graph)
    int rc;                // zh_stitch_verdict of it: the buffer is usable iff layout != NONE && rc == 0
 };
@@ -233,6 +240,14 @@ struct zultra_hip_ctx_s {
    float verify_ms;
    // framed members (zh_frame.h, zultra_hip_frame_members): allocated by the first call (zh_need_frame)
    zh_member_t *d_members;
+   // the grouped form (zh_streams.h, zultra_hip_frame_streams / zultra_hip_zip_streams): allocated by the first call (zh_need_streams)
+   uint32_t *d_stream_of;     // per max-block its stream | ZH_STREAM_START, behind them (at nblocks) the streams' first max-blocks and the block count
+   std::vector<uint32_t> h_stream_of;   // ... as uploaded by the last call
+   zh_block_t *d_sblocks;     // per stream what the writers read per max-block: {first byte, 0, size} ...
+   uint32_t *d_scrc, *d_sadler;   // ... and the checksums' parts (zh_fold_streams)
+   uint32_t largest_stream;   // of the last grouping
+   hipEvent_t ev_fold[2];     // around zh_fold_streams
+   float streams_ms[3];       // scan, fold, frame kernel of the last grouped assembly
    hipEvent_t ev_frame[4];    // around the scan, the mover and the frame kernel
    float frame_ms[3];
    // a ZIP archive's entries (zh_zip.h, zultra_hip_zip_members): allocated by the first call, grown where a call needs more
@@ -573,7 +588,7 @@ static void zh_shape(zultra_hip_ctx_t *c, uint32_t max_block, uint32_t max_block
 
 // The sets a buffer can belong to: it is allocated with the first of its sets that is asked for. CORE, and FILES or BLOCKS by the kind of context, at creation — TRACE
 // too under ZULTRA_HIP_CHAIN_TRACE=1 (zh_creation_sets); the others by the first call that needs them (zh_need_*).
-enum { ZH_SET_CORE = 1, ZH_SET_FILES = 2, ZH_SET_BLOCKS = 4, ZH_SET_TRACE = 8, ZH_SET_FILE_OFF = 16, ZH_SET_VERIFY = 32, ZH_SET_FRAME = 64, ZH_SET_ZIP = 128, ZH_SET_ALL = 255 };
+enum { ZH_SET_CORE = 1, ZH_SET_FILES = 2, ZH_SET_BLOCKS = 4, ZH_SET_TRACE = 8, ZH_SET_FILE_OFF = 16, ZH_SET_VERIFY = 32, ZH_SET_FRAME = 64, ZH_SET_ZIP = 128, ZH_SET_STREAMS = 256, ZH_SET_ALL = 511 };
 #define ZH_TRACE_WORDS ((size_t)3 * ZH_TRACE_SLOTS * 4 * ZH_MAX_RUNS)   // (zultra_hip_chain_trace returns the first four runs)
 
 // Every buffer a context owns, stated once: X(sets, kind, field, count) — device (DEV) or pinned host (PIN) memory, the context field, whose own type gives the element
@@ -649,6 +664,10 @@ enum { ZH_SET_CORE = 1, ZH_SET_FILES = 2, ZH_SET_BLOCKS = 4, ZH_SET_TRACE = 8, Z
    X(ZH_SET_VERIFY, DEV, d_vreport, 1)                          /* ... the batch report ... */                                                                           \
    X(ZH_SET_VERIFY, PIN, h_vreport, 1)                          /* ... and its mirror */                                                                                 \
    X(ZH_SET_FRAME, DEV, d_members, B)                           /* zultra_hip_frame_members: a record per member */                                                      \
+   X(ZH_SET_STREAMS, DEV, d_stream_of, 2 * B + 1)                /* the grouped form: per max-block its stream and the start flag, then the streams' first max-blocks */  \
+   X(ZH_SET_STREAMS, DEV, d_sblocks, B)                         /* ... per stream {first byte, 0, size} ... */                                                            \
+   X(ZH_SET_STREAMS, DEV, d_scrc, B)                            /* ... its CRC-32, linear part ... */                                                                     \
+   X(ZH_SET_STREAMS, DEV, d_sadler, 2 * B)                      /* ... and its Adler-32 sums (zh_fold_streams) */                                                         \
    X(ZH_SET_ZIP, DEV, d_zip_report, 1)                          /* zultra_hip_zip_members: the report of zh_zip_scan ... */                                              \
    X(ZH_SET_ZIP, PIN, h_zip_report, 1)                          /* ... and its mirror */                                                                                 \
    X(ZH_SET_ZIP, DEV, d_zip, 0)                                 /* the archive's local part, and at zip_central_at the central part */                                   \
@@ -700,6 +719,7 @@ static int zh_need_events(zultra_hip_ctx_t *c, hipEvent_t *ev, int n) {
 static int zh_need_verify(zultra_hip_ctx_t *c) { return zh_buffers(c, ZH_BUF_ALLOC, ZH_SET_VERIFY) || zh_need_events(c, c->ev_verify, 2); }
 static int zh_need_frame(zultra_hip_ctx_t *c) { return zh_buffers(c, ZH_BUF_ALLOC, ZH_SET_FRAME) || zh_need_events(c, c->ev_frame, 4); }
 static int zh_need_zip(zultra_hip_ctx_t *c) { return zh_buffers(c, ZH_BUF_ALLOC, ZH_SET_ZIP) || zh_need_events(c, c->ev_zip, 4); }   // (the buffers sized by a call's entries grow there, zh_zip_grow)
+static int zh_need_streams(zultra_hip_ctx_t *c) { return zh_buffers(c, ZH_BUF_ALLOC, ZH_SET_STREAMS) || zh_need_events(c, c->ev_fold, 2); }
 static void zh_drop_events(hipEvent_t *ev, int n) {
    for (int i = 0; i < n; i++)
       if (ev[i]) (void)hipEventDestroy(ev[i]);
@@ -743,6 +763,7 @@ extern "C" void zultra_hip_destroy(zultra_hip_ctx_t *c) {
    zh_drop_events(c->ev_verify, 2);
    zh_drop_events(c->ev_frame, 4);
    zh_drop_events(c->ev_zip, 4);
+   zh_drop_events(c->ev_fold, 2);
    zh_drop_events(c->ev_stitch, ZH_STITCH_EVENTS);
    if (c->stream) (void)hipStreamDestroy(c->stream);
    delete c;
@@ -887,9 +908,10 @@ static int zh_look_at_streams(zultra_hip_ctx_t *c) {
 #endif
 
 // ---- the stitch jobs, and the record of what the stream buffer holds (zh_assembly_t) ----------------------------------------------------------------------
-static zh_stitch_job_t zh_job_stream(uint32_t phase, int final_block, bool scan_only = false) { return {phase & 7u, final_block, false, scan_only, false, {0, 0}}; }
-static zh_stitch_job_t zh_job_files(void) { return {0, -1, true, false, false, {0, 0}}; }   // (the plain files form)
-static zh_stitch_job_t zh_job_framed(uint32_t framing, uint32_t eof) { return {0, -1, true, false, true, {framing, eof}}; }
+static zh_stitch_job_t zh_job_stream(uint32_t phase, int final_block, bool scan_only = false) { return {phase & 7u, final_block, false, scan_only, false, {0, 0}, false, {0, 0}}; }
+static zh_stitch_job_t zh_job_files(void) { return {0, -1, true, false, false, {0, 0}, false, {0, 0}}; }   // (the plain files form)
+static zh_stitch_job_t zh_job_framed(uint32_t framing, uint32_t eof) { return {0, -1, true, false, true, {framing, eof}, false, {0, 0}}; }
+static zh_stitch_job_t zh_job_streams(uint32_t framing, zh_group_args_t group) { return {0, -1, false, false, true, {framing, 0}, true, group}; }   // (the grouped form; framing 0: plain)
 static int zh_enqueue_stitch(zultra_hip_ctx_t *c, hipStream_t st, const zh_stitch_job_t &job, bool clear);
 static int zh_stitch_verdict(zultra_hip_ctx_t *c, bool scan_only);
 
@@ -899,17 +921,22 @@ static void zh_assembly_record(zultra_hip_ctx_t *c, const zh_stitch_job_t &job, 
    zh_assembly_clear(c);
    if (job.scan_only || (rc != 0 && !with_batch)) return;
    const uint32_t gap = job.framed ? zh_frame_head(job.frame.framing) + zh_frame_tail(job.frame.framing) : 0u;
-   c->held = {job.files ? ZH_LAYOUT_FILES : ZH_LAYOUT_STREAM, job.phase, job.final_block, gap, with_batch, rc};
+   c->held = {job.streams ? ZH_LAYOUT_STREAMS : job.files ? ZH_LAYOUT_FILES : ZH_LAYOUT_STREAM, job.phase, job.final_block, gap, job.group, with_batch, rc};
 }
 static bool zh_assembly_usable(const zultra_hip_ctx_t *c) { return c->held.layout != ZH_LAYOUT_NONE && c->held.rc == 0; }   // the buffer holds a sound assembly ...
 static bool zh_assembly_is_files(const zultra_hip_ctx_t *c) { return c->held.layout == ZH_LAYOUT_FILES; }                    // ... in the files form ...
 static uint32_t zh_assembly_gap(const zultra_hip_ctx_t *c) { return c->held.gap; }                                           // ... with this many bytes between the streams
+static int zh_assembly_form(const zultra_hip_ctx_t *c) { return c->held.layout == ZH_LAYOUT_FILES ? 1 : c->held.layout == ZH_LAYOUT_STREAMS ? 2 : 0; }   // (what zh_verify_subblocks calls `files`)
+// ... in the plain grouped form of this grouping: its offsets in d_file_off, the streams' sizes and checksums in d_sblocks / d_scrc (zultra_hip_zip_streams)
+static bool zh_assembly_plain_streams(const zultra_hip_ctx_t *c, zh_group_args_t g) {
+   return zh_assembly_usable(c) && c->held.layout == ZH_LAYOUT_STREAMS && zh_assembly_gap(c) == 0 && c->held.group.nstreams == g.nstreams && c->held.group.hash == g.hash;
+}
 // ... in the plain files form: its offsets in d_file_off, its report in d_scan_out (zultra_hip_zip_members)
 static bool zh_assembly_plain_files(const zultra_hip_ctx_t *c) { return zh_assembly_usable(c) && zh_assembly_is_files(c) && zh_assembly_gap(c) == 0; }
 // The batch brought what `job` asks for: *rc is the verdict on it, and nothing needs to be launched
 static bool zh_assembly_brought(const zultra_hip_ctx_t *c, const zh_stitch_job_t &job, int *rc) {
    const zh_assembly_t &h = c->held;
-   if (!h.with_batch || h.layout != (job.files ? ZH_LAYOUT_FILES : ZH_LAYOUT_STREAM) || (!job.files && (h.phase != job.phase || h.final_block != job.final_block))) return false;
+   if (job.streams || !h.with_batch || h.layout != (job.files ? ZH_LAYOUT_FILES : ZH_LAYOUT_STREAM) || (!job.files && (h.phase != job.phase || h.final_block != job.final_block))) return false;
    *rc = h.rc;
    return true;
 }
@@ -1861,7 +1888,18 @@ static int zh_enqueue_stitch(zultra_hip_ctx_t *c, hipStream_t st, const zh_stitc
       snprintf(c->err, sizeof(c->err), "batch too large for the stream assembly's 32-bit chunk tables (%u max-blocks of %u bytes)", c->nblocks, c->max_block);
       return -1;
    }
-   if (frame)
+   if (job.streams) {
+      // the grouping goes up with the call; the fold of the streams' sizes and checksums stands behind the scan, in front of the kernels that read it
+      const size_t words = (size_t)c->nblocks + job.group.nstreams + 1;
+      ZH_CHECK(c, hipMemcpyAsync(c->d_stream_of, c->h_stream_of.data(), words * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+      ZH_LAUNCH(zh_stitch_scan_streams, 1, ZH_SCAN_THREADS, st, (const zh_subblock_t *)c->d_results_compact, (const uint32_t *)c->d_nsubs, c->nblocks, job.group.nstreams, block_size, head, tail,
+                (const uint32_t *)c->d_stream_of, c->d_blk_start, c->d_items, c->d_file_off, c->d_scan_out);
+      ZH_CHECK(c, hipEventRecord(c->ev_fold[0], st));
+      ZH_LAUNCH(zh_fold_streams, (uint32_t)zh_min64(job.group.nstreams, c->grid_cap ? c->grid_cap : 4096), ZH_FOLD_THREADS, st, (const zh_block_t *)c->d_blocks, (const uint32_t *)c->d_crc,
+                (const uint32_t *)c->d_adler, (const uint32_t *)c->d_stream_of + c->nblocks, job.group.nstreams, c->d_sblocks, c->d_scrc, c->d_sadler);
+      ZH_CHECK(c, hipEventRecord(c->ev_fold[1], st));
+   }
+   else if (frame)
       ZH_LAUNCH(zh_stitch_scan<true>, 1, ZH_SCAN_THREADS, st, (const zh_subblock_t *)c->d_results_compact, (const uint32_t *)c->d_nsubs, c->nblocks, job.phase,
                 job.files ? block_size : c->max_block, job.final_block, (int)job.files, head, tail, member_max, c->d_blk_start, c->d_items, c->d_file_off, c->d_scan_out);
    else
@@ -1869,7 +1907,7 @@ static int zh_enqueue_stitch(zultra_hip_ctx_t *c, hipStream_t st, const zh_stitc
                 job.files ? block_size : c->max_block, job.final_block, (int)job.files, 0u, 0u, 0u, c->d_blk_start, c->d_items, c->d_file_off, c->d_scan_out);
    if (frame) {
       // (a framed assembly clears behind its scan, which knows how much — and whether: a refused call writes nothing)
-      const uint64_t worst = zh_stream_clear_bytes(c, (uint64_t)c->nblocks * (head + tail) + eof);
+      const uint64_t worst = zh_stream_clear_bytes(c, (uint64_t)(job.streams ? job.group.nstreams : c->nblocks) * (head + tail) + eof);
       ZH_LAUNCH(zh_frame_clear, (uint32_t)zh_max64(1, zh_min64(worst / (16 * ZH_FRAME_CLEAR_THREADS), 4096)), ZH_FRAME_CLEAR_THREADS, st, (const zh_scan_out_t *)c->d_scan_out,
                 (uint64_t)c->stream_cap - eof, eof, (uint4 *)c->d_stream);
       ZH_CHECK(c, hipEventRecord(c->ev_frame[1], st));
@@ -1881,10 +1919,13 @@ static int zh_enqueue_stitch(zultra_hip_ctx_t *c, hipStream_t st, const zh_stitc
    }
    if (frame) {
       // one lane per member and one for the end marker, the kernel strides
+      // (the grouped form: the same kernel over the streams — their sizes and checksums' parts have the shape of a max-block's)
+      const uint32_t nmembers = job.streams ? job.group.nstreams : c->nblocks;
       uint32_t threads = ZH_FRAME_THREADS;
-      const uint32_t grid = zh_lane_grid(c, c->nblocks + 1, &threads);
+      const uint32_t grid = zh_lane_grid(c, nmembers + 1, &threads);
       ZH_CHECK(c, hipEventRecord(c->ev_frame[2], st));
-      ZH_LAUNCH(zh_frame_members, grid, threads, st, (const zh_block_t *)c->d_blocks, c->nblocks, (const uint64_t *)c->d_file_off, (const uint32_t *)c->d_crc, (const uint32_t *)c->d_adler,
+      ZH_LAUNCH(zh_frame_members, grid, threads, st, (const zh_block_t *)(job.streams ? c->d_sblocks : c->d_blocks), nmembers, (const uint64_t *)c->d_file_off,
+                (const uint32_t *)(job.streams ? c->d_scrc : c->d_crc), (const uint32_t *)(job.streams ? c->d_sadler : c->d_adler),
                 (const zh_scan_out_t *)c->d_scan_out, (uint64_t)c->stream_cap - eof, frame->framing, member_max, eof, (uint8_t *)c->d_stream, c->d_members);
       ZH_CHECK(c, hipEventRecord(c->ev_frame[3], st));
    }
@@ -1928,6 +1969,11 @@ static int zh_stitch_finish(zultra_hip_ctx_t *c) {
    if (!job.scan_only) (void)hipEventElapsedTime(&c->timing.stitch_ms, c->ev_stitch[ZH_STITCH_EV_START], c->ev_stitch[ZH_STITCH_EV_END]);
    if (job.framed)
       for (int i = 0; i < 3; i++) (void)hipEventElapsedTime(&c->frame_ms[i], c->ev_frame[i], c->ev_frame[i + 1]);
+   if (job.streams) {
+      (void)hipEventElapsedTime(&c->streams_ms[0], c->ev_frame[0], c->ev_fold[0]);
+      (void)hipEventElapsedTime(&c->streams_ms[1], c->ev_fold[0], c->ev_fold[1]);
+      c->streams_ms[2] = c->frame_ms[2];
+   }
    int rc = zh_stitch_verdict(c, job.scan_only);
    if (job.framed && c->h_scan_out->nsubs == c->nsubs && !c->h_scan_out->failed) {   // (what a framed assembly reports of its own; the end marker needs its room too)
       if (c->h_scan_out->oversize) {
@@ -2039,6 +2085,98 @@ extern "C" void zultra_hip_last_frame_ms(const zultra_hip_ctx_t *c, float *ms /*
    for (int i = 0; c && ms && i < 3; i++) ms[i] = c->frame_ms[i];
 }
 
+// The grouped form (zh_streams.h): the last batch's max-blocks as nstreams streams, stream s = max-blocks stream_first[s] .. stream_first[s + 1] - 1. What makes a
+// grouping valid is checked here, on the host, before anything is allocated or enqueued: 0 and the grouping in h_stream_of / *group / largest_stream; -1 for an
+// invalid one; -2 where a stream reaches 2^32 bytes (its size would not fit the writers' 32-bit fields).
+static int zh_streams_check(zultra_hip_ctx_t *c, const uint32_t *stream_first, uint32_t nstreams, zh_group_args_t *group) {
+   if (!stream_first || nstreams == 0 || c->nsubs == 0 || nstreams > c->nblocks || stream_first[0] != 0) {
+      snprintf(c->err, sizeof(c->err), "a grouping is 1 .. blocks streams of a compressed batch, the first at max-block 0");
+      return -1;
+   }
+   for (uint32_t s = 1; s < nstreams; s++)
+      if (stream_first[s] <= stream_first[s - 1] || stream_first[s] >= c->nblocks) {
+         snprintf(c->err, sizeof(c->err), "stream %u starts at max-block %u: the first max-blocks increase and lie inside the batch", s, stream_first[s]);
+         return -1;
+      }
+   c->h_stream_of.assign((size_t)c->nblocks + nstreams + 1, 0u);
+   uint64_t hash = 0xcbf29ce484222325ull, in_front = 0, largest = 0;
+   for (uint32_t s = 0, b = 0; b < c->nblocks; b++) {
+      const bool starts = s < nstreams && stream_first[s] == b;
+      const zh_block_t &k = c->blocks[b];
+      if (starts) {
+         c->h_stream_of[(size_t)c->nblocks + s] = b;
+         hash = (hash ^ b) * 0x100000001b3ull;
+         s++;
+         in_front = 0;
+         if (k.prev != 0) {
+            snprintf(c->err, sizeof(c->err), "max-block %u starts a stream and has history", b);
+            return -1;
+         }
+      }
+      else {
+         const zh_block_t &p = c->blocks[b - 1];
+         if (k.win_off + k.prev != p.win_off + p.prev + p.n || k.prev != (uint32_t)zh_min64(in_front, 32768) || p.n != c->max_block) {
+            snprintf(c->err, sizeof(c->err), "max-block %u does not continue max-block %u: a stream is contiguous, of full max-blocks but its last, each with the 32 KiB in front of it as history", b, b - 1);
+            return -1;
+         }
+      }
+      c->h_stream_of[b] = (s - 1) | (starts ? ZH_STREAM_START : 0u);
+      in_front += k.n;
+      largest = zh_max64(largest, in_front);
+   }
+   if (largest >= (1ull << 32)) {
+      snprintf(c->err, sizeof(c->err), "a stream reaches 4 GiB");
+      return -2;
+   }
+   c->h_stream_of[(size_t)c->nblocks + nstreams] = c->nblocks;
+   c->largest_stream = (uint32_t)largest;
+   *group = {nstreams, hash};
+   return 0;
+}
+
+// Framed streams: the grouped assembly with room around every stream, and zh_frame_members over the streams behind it — scan, fold, clearing, mover, frame
+// kernel, one synchronisation. Explicit only: nothing of it goes out with a batch.
+extern "C" int zultra_hip_frame_streams(zultra_hip_ctx_t *c, const uint32_t *stream_first, uint32_t nstreams, unsigned int framing, zultra_hip_member_t *members, uint64_t *total_bytes) {
+   ZH_EMU_SERIALIZE();
+   if (!c || !members || !total_bytes) return -1;
+   if (framing != ZH_FRAME_RAW && framing != ZH_FRAME_ZLIB && framing != ZH_FRAME_GZIP) {
+      snprintf(c->err, sizeof(c->err), "framing %u: one of raw (0), zlib (1), gzip (2) — a BGZF member cannot hold several max-blocks", framing);
+      return -1;
+   }
+   zh_group_args_t group;
+   int rc = zh_streams_check(c, stream_first, nstreams, &group);
+   if (rc != 0) return rc;
+   ZH_CHECK(c, hipSetDevice(c->device));
+   if (zh_need_file_off(c) || zh_need_frame(c) || zh_need_streams(c)) return -1;
+   rc = zh_stitch_on_device(c, zh_job_streams(framing, group));
+   if (rc != 0) return rc;
+   ZH_CHECK(c, hipMemcpy(members, c->d_members, (size_t)nstreams * sizeof(zh_member_t), hipMemcpyDeviceToHost));
+   *total_bytes = members[nstreams - 1].off + members[nstreams - 1].size;
+   return 0;
+}
+extern "C" void zultra_hip_last_streams_ms(const zultra_hip_ctx_t *c, float *ms /* [3]: scan, fold, frame kernel */) {
+   for (int i = 0; c && ms && i < 3; i++) ms[i] = c->streams_ms[i];
+}
+
+// Diagnostics (tests): where the last assembly put every sub-block — the items of zh_stitch_scan / zh_stitch_scan_streams, {dst_bit, stored, is_final}, 16 bytes each —
+// and what the host planner (zh_stitch_plan_streams) says of a grouping of the last batch: items (nsubs), file_off (nstreams + 1), *end_bit; -1 for an invalid
+// grouping or framing, -2 where the planner fails as the reference does with ZULTRA_ERROR_DST.
+extern "C" int zultra_hip_stitch_items(zultra_hip_ctx_t *c, void *items /* nsubs x 16 bytes */) {
+   if (!c || !items || c->nsubs == 0) return -1;
+   ZH_CHECK(c, hipSetDevice(c->device));
+   ZH_CHECK(c, hipMemcpy(items, c->d_items, (size_t)c->nsubs * sizeof(zh_stitch_item_t), hipMemcpyDeviceToHost));
+   return (int)c->nsubs;
+}
+extern "C" int zultra_hip_plan_streams(zultra_hip_ctx_t *c, const uint32_t *stream_first, uint32_t nstreams, unsigned int framing, void *items, uint64_t *file_off, uint64_t *end_bit) {
+   if (!c || !end_bit || (framing != ZH_FRAME_RAW && framing != ZH_FRAME_ZLIB && framing != ZH_FRAME_GZIP)) return -1;
+   zh_group_args_t group;
+   const int rc = zh_streams_check(c, stream_first, nstreams, &group);
+   if (rc != 0) return rc;
+   const uint32_t block_size = c->max_block < ZH_MIN_BLOCK ? (uint32_t)ZH_MIN_BLOCK : c->max_block;
+   return zh_stitch_plan_streams(c->results.data(), c->nsubs, c->nblocks, c->h_stream_of.data(), block_size, zh_frame_head(framing), zh_frame_tail(framing), (zh_stitch_item_t *)items, file_off,
+                                 end_bit) == 0 ? 0 : -2;
+}
+
 // A ZIP archive's entries (zh_zip.h): a gather behind the plain files-form assembly of the last batch. The assembly is the one the stream buffer holds — a files
 // context's graph ran it, zultra_hip_stitch_files did — or is enqueued here, in front of the three kernels; one synchronisation either way. Everything the host can
 // refuse it refuses before anything is allocated or enqueued; what only the device knows (the assembly's failure, the 32-bit limit) zh_zip_scan reports, and the
@@ -2053,15 +2191,25 @@ static int zh_zip_grow(zultra_hip_ctx_t *c, T **p, size_t have, size_t want, boo
    *p = q;
    return 0;
 }
-extern "C" int zultra_hip_zip_members(zultra_hip_ctx_t *c, const void *names, const uint32_t *name_off, const uint32_t *entry_block, uint32_t n, uint64_t base_off,
-                                      uint32_t dos_datetime, zultra_hip_zip_entry_t *entries, uint64_t *local_bytes, uint64_t *central_bytes) {
+// The entries are the batch's max-blocks (stream_first == NULL: zultra_hip_zip_members) or the streams of a grouping (zultra_hip_zip_streams): the same three kernels
+// either way — what they read per entry, a size, a CRC-32's linear part and two offsets, the fold (zh_fold_streams) has left per stream in the same shape.
+static int zh_zip_entries(zultra_hip_ctx_t *c, const uint32_t *stream_first, uint32_t nstreams, const void *names, const uint32_t *name_off, const uint32_t *entry_block, uint32_t n, uint64_t base_off,
+                          uint32_t dos_datetime, zultra_hip_zip_entry_t *entries, uint64_t *local_bytes, uint64_t *central_bytes) {
    ZH_EMU_SERIALIZE();
    if (!c || !names || !name_off || !n || !local_bytes || !central_bytes || c->nsubs == 0) return -1;
-   for (uint32_t b = 0; b < c->nblocks; b++)
-      if (c->blocks[b].prev != 0) {
-         snprintf(c->err, sizeof(c->err), "max-block %u has history: an entry stands alone", b);
-         return -1;
-      }
+   const bool grouped = stream_first != NULL;
+   zh_group_args_t group = {0, 0};
+   if (grouped) {
+      const int rc = zh_streams_check(c, stream_first, nstreams, &group);
+      if (rc != 0) return rc;
+   }
+   else
+      for (uint32_t b = 0; b < c->nblocks; b++)
+         if (c->blocks[b].prev != 0) {
+            snprintf(c->err, sizeof(c->err), "max-block %u has history: an entry stands alone", b);
+            return -1;
+         }
+   const uint32_t nunits = grouped ? nstreams : c->nblocks;   // what an entry names: a stream, or a max-block
    uint32_t next = 0;
    for (uint32_t i = 0; i < n; i++) {
       if (name_off[i + 1] <= name_off[i] || name_off[i + 1] - name_off[i] > 65535u) {
@@ -2074,8 +2222,8 @@ extern "C" int zultra_hip_zip_members(zultra_hip_ctx_t *c, const void *names, co
          return -1;
       }
    }
-   if (next != c->nblocks) {
-      snprintf(c->err, sizeof(c->err), "the entries name %u max-blocks, the batch has %u", next, c->nblocks);
+   if (next != nunits) {
+      snprintf(c->err, sizeof(c->err), "the entries name %u %s, the batch has %u", next, grouped ? "streams" : "max-blocks", nunits);
       return -1;
    }
    if (base_off >= ZH_ZIP_LIMIT) {
@@ -2084,8 +2232,11 @@ extern "C" int zultra_hip_zip_members(zultra_hip_ctx_t *c, const void *names, co
    }
    ZH_CHECK(c, hipSetDevice(c->device));
    hipStream_t st = c->stream;
-   const bool assembled = zh_assembly_plain_files(c);   // (the plain files form is in the stream buffer, its offsets in d_file_off, its report in d_scan_out)
-   if (zh_need_file_off(c) || zh_need_zip(c)) return -1;
+   // (the plain form is in the stream buffer, its offsets in d_file_off, its report in d_scan_out — for a grouping: of the same grouping, its fold in d_sblocks / d_scrc)
+   const bool assembled = grouped ? zh_assembly_plain_streams(c, group) : zh_assembly_plain_files(c);
+   if (zh_need_file_off(c) || zh_need_zip(c) || (grouped && (zh_need_frame(c) || zh_need_streams(c)))) return -1;
+   const zh_block_t *d_units = grouped ? c->d_sblocks : c->d_blocks;
+   const uint32_t *d_unit_crc = grouped ? c->d_scrc : c->d_crc;
    // what the call brings: name_off, entry_block, names — one upload
    const uint32_t names_bytes = name_off[n] - name_off[0];
    const size_t in_words = (size_t)n + 1 + (entry_block ? n : 0) + ((size_t)names_bytes + 3) / 4;
@@ -2114,23 +2265,23 @@ extern "C" int zultra_hip_zip_members(zultra_hip_ctx_t *c, const void *names, co
    const uint32_t *d_name_off = c->d_zip_in, *d_entry_block = entry_block ? c->d_zip_in + n + 1 : NULL;
    const uint8_t *d_names = (const uint8_t *)(c->d_zip_in + names_word) - name_off[0];   // (name i is at d_names + name_off[i])
 
-   if (!assembled && zh_stitch_begin(c, zh_job_files()) != 0) return -1;
+   if (!assembled && zh_stitch_begin(c, grouped ? zh_job_streams(ZH_FRAME_RAW, group) : zh_job_files()) != 0) return -1;
    ZH_CHECK(c, hipEventRecord(c->ev_zip[0], st));
-   ZH_LAUNCH(zh_zip_scan, 1, ZH_ZIP_SCAN_THREADS, st, d_name_off, d_entry_block, n, (const zh_block_t *)c->d_blocks, (const uint64_t *)c->d_file_off,
+   ZH_LAUNCH(zh_zip_scan, 1, ZH_ZIP_SCAN_THREADS, st, d_name_off, d_entry_block, n, d_units, (const uint64_t *)c->d_file_off,
              (const zh_scan_out_t *)c->d_scan_out, (uint64_t)c->stream_cap, base_off, c->d_zip_entries, c->d_zip_src, c->d_zip_report);
    ZH_CHECK(c, hipEventRecord(c->ev_zip[1], st));
    {
       uint32_t threads = ZH_ZIP_RECORD_THREADS;   // (one lane per entry)
       const uint32_t grid = zh_lane_grid(c, n, &threads);
-      ZH_LAUNCH(zh_zip_records, grid, threads, st, c->d_zip_entries, (const uint64_t *)c->d_zip_src, d_name_off, d_names, d_entry_block, (const uint32_t *)c->d_crc, n, base_off,
+      ZH_LAUNCH(zh_zip_records, grid, threads, st, c->d_zip_entries, (const uint64_t *)c->d_zip_src, d_name_off, d_names, d_entry_block, d_unit_crc, n, base_off,
                 dos_datetime ? dos_datetime : 0x00210000u, central_at, (const zh_zip_report_t *)c->d_zip_report, c->d_zip);
    }
    ZH_CHECK(c, hipEventRecord(c->ev_zip[2], st));
    {
       // (entry, slice): as many slices side by side as the batch's largest input can have at its worst, stored; along the entries a few workgroups per CU. The cap
       // of the tests caps the workgroups, so that a wave sees several entries and several slices
-      uint32_t largest = 0;
-      for (uint32_t b = 0; b < c->nblocks; b++) largest = max(largest, c->blocks[b].n);
+      uint32_t largest = grouped ? c->largest_stream : 0;
+      for (uint32_t b = 0; !grouped && b < c->nblocks; b++) largest = max(largest, c->blocks[b].n);
       const uint64_t worst = (uint64_t)largest + 5ull * (largest / 65535u + 1u) + 1;
       uint32_t yslices = (uint32_t)zh_max64(1, zh_min64((worst + 16ull * ZH_ZIP_SLICE_CHUNKS - 1) / (16ull * ZH_ZIP_SLICE_CHUNKS), ZH_ZIP_MAX_YSLICES));
       const uint32_t waves = ZH_ZIP_COPY_THREADS / 64;
@@ -2160,6 +2311,18 @@ extern "C" int zultra_hip_zip_members(zultra_hip_ctx_t *c, const void *names, co
    *local_bytes = c->h_zip_report->local_bytes;
    *central_bytes = c->h_zip_report->central_bytes;
    return 0;
+}
+extern "C" int zultra_hip_zip_members(zultra_hip_ctx_t *c, const void *names, const uint32_t *name_off, const uint32_t *entry_block, uint32_t n, uint64_t base_off,
+                                      uint32_t dos_datetime, zultra_hip_zip_entry_t *entries, uint64_t *local_bytes, uint64_t *central_bytes) {
+   return zh_zip_entries(c, NULL, 0, names, name_off, entry_block, n, base_off, dos_datetime, entries, local_bytes, central_bytes);
+}
+extern "C" int zultra_hip_zip_streams(zultra_hip_ctx_t *c, const uint32_t *stream_first, uint32_t nstreams, const void *names, const uint32_t *name_off, const uint32_t *entry_stream, uint32_t n,
+                                      uint64_t base_off, uint32_t dos_datetime, zultra_hip_zip_entry_t *entries, uint64_t *local_bytes, uint64_t *central_bytes) {
+   if (c && !stream_first) {
+      snprintf(c->err, sizeof(c->err), "no grouping");
+      return -1;
+   }
+   return zh_zip_entries(c, stream_first, nstreams, names, name_off, entry_stream, n, base_off, dos_datetime, entries, local_bytes, central_bytes);
 }
 extern "C" const void *zultra_hip_zip_device(const zultra_hip_ctx_t *c, uint64_t *central_at) {
    if (c && central_at) *central_at = c->zip_central_at;
@@ -2219,7 +2382,7 @@ extern "C" int zultra_hip_verify_device(zultra_hip_ctx_t *c, zultra_hip_verify_t
    }
    ZH_CHECK(c, hipSetDevice(c->device));
    if (zh_need_verify(c)) return -1;
-   const int files = zh_assembly_is_files(c);
+   const int files = zh_assembly_form(c);
    hipStream_t st = c->stream;
    ZH_CHECK(c, hipMemsetAsync(c->d_vreport, 0, sizeof(zh_verify_report_t), st));
    ZH_CHECK(c, hipMemsetAsync(&c->d_vreport->first_bad, 0xff, sizeof(uint32_t), st));
@@ -2227,7 +2390,7 @@ extern "C" int zultra_hip_verify_device(zultra_hip_ctx_t *c, zultra_hip_verify_t
    const uint32_t grid = (uint32_t)zh_min64(c->nsubs, zh_max64(12ull * c->total_cus, 64));   // (one wave per workgroup, three to a SIMD — zh_verify.h: a CU holds 12; more would only queue)
    ZH_LAUNCH(zh_verify_subblocks, grid, ZH_VERIFY_THREADS, st, (const uint32_t *)c->d_stream, (uint64_t)c->stream_cap, (const zh_stitch_item_t *)c->d_items,
              (const zh_subblock_t *)c->d_results_compact, (const zh_block_t *)c->d_blocks, c->nblocks, c->cur_data, (const zh_scan_out_t *)c->d_scan_out, (const uint64_t *)c->d_file_off, files,
-             zh_assembly_gap(c), c->d_vitems, c->d_vreport);
+             zh_assembly_gap(c), (const uint32_t *)c->d_stream_of, c->d_vitems, c->d_vreport);
    ZH_CHECK(c, hipEventRecord(c->ev_verify[1], st));
    ZH_CHECK(c, hipMemcpyAsync(c->h_vreport, c->d_vreport, sizeof(zh_verify_report_t), hipMemcpyDeviceToHost, st));
    ZH_CHECK(c, hipStreamSynchronize(st));

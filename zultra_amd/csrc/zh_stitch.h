@@ -85,6 +85,44 @@ static inline int zh_stitch_plan(uint32_t phase, const zh_subblock_t *subs, uint
    return 0;
 }
 
+// The same for the GROUPED form (zh_streams.h): the batch holds several streams, each a run of consecutive max-blocks. stream_of[b] = the stream of max-block b,
+// with ZH_STREAM_START set where b is its stream's first. A stream starts on a byte boundary, head bytes behind the end of the stream in front of it, at phase 0;
+// inside it the phase is carried from max-block to max-block as above; its last sub-block has BFINAL, and tail bytes are left free behind its last byte.
+// file_off (nstreams + 1, may be NULL): the first byte of every stream, and where a further one would start. *end_bit = the end of the last tail.
+#define ZH_STREAM_START 0x80000000u
+static inline int zh_stitch_plan_streams(const zh_subblock_t *subs, uint32_t nsubs, uint32_t nblocks, const uint32_t *stream_of, uint32_t max_block_size, uint32_t head, uint32_t tail,
+                                         zh_stitch_item_t *items, uint64_t *file_off, uint64_t *end_bit) {
+   const uint64_t blockbuf_cap = zh_stitch_blockbuf_cap(max_block_size);
+   uint64_t bit = 0, block_base = 0;
+   uint32_t cur_block = 0xFFFFFFFFu, nstreams = 0;
+   for (uint32_t k = 0; k < nsubs; k++) {
+      const zh_subblock_t *sb = &subs[k];
+      if (sb->block >= nblocks) return -1;
+      if (sb->block != cur_block) {
+         cur_block = sb->block;
+         if (stream_of[cur_block] & ZH_STREAM_START) {
+            bit = ((bit + 7) & ~7ull) + 8ull * head;
+            if (file_off) file_off[stream_of[cur_block] & ~ZH_STREAM_START] = bit >> 3;
+            nstreams++;
+         }
+         block_base = bit >> 3;
+      }
+      const int last_of_block = (k + 1 == nsubs) || (subs[k + 1].block != sb->block);
+      const int ends = last_of_block && (sb->block + 1 == nblocks || (stream_of[sb->block + 1] & ZH_STREAM_START));
+      if (items) {
+         items[k].dst_bit = bit;
+         items[k].is_final = ends ? 1u : 0u;
+      }
+      uint32_t stored = 0;
+      if (zh_stitch_step(&bit, block_base, sb->size, sb->nbits, sb->failed, blockbuf_cap, &stored) != 0) return -1;
+      if (items) items[k].stored = stored;
+      if (ends) bit = ((bit + 7) & ~7ull) + 8ull * tail;
+   }
+   if (file_off) file_off[nstreams] = (bit >> 3) + head;
+   *end_bit = bit;
+   return 0;
+}
+
 #if defined(__HIPCC__) || defined(ZH_EMU)
 #include <zh_platform.h>
 

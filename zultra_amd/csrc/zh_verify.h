@@ -166,6 +166,8 @@ __device__ __forceinline__ uint32_t zh_verify_one(zh_d_lds_t &S, const uint32_t 
 // One wave per sub-block of the last stitched batch, striding: the grid needs no count. files != 0: the batch was stitched as one stream per
 // max-block (zh_stitch_scan): a max-block's last sub-block ends within the last byte before the next file's first — or, where the assembly left `gap` bytes
 // of trailer and header between the streams (zh_frame.h; file_off[nblocks] counts a gap as well), that many bytes earlier.
+// files == 2: the grouped form (zh_streams.h) — stream_of[b] = the stream of max-block b, ZH_STREAM_START where b starts it, and file_off is indexed by stream:
+// the sub-block that ends a stream's last max-block ends like a file's, every other sub-block where the next one begins.
 #define ZH_VERIFY_THREADS 64
 #ifdef ZH_EMU
 #define ZH_VERIFY_WAVES_PER_SIMD
@@ -175,7 +177,7 @@ __device__ __forceinline__ uint32_t zh_verify_one(zh_d_lds_t &S, const uint32_t 
 __global__ void __launch_bounds__(ZH_VERIFY_THREADS) ZH_VERIFY_WAVES_PER_SIMD
 zh_verify_subblocks(const uint32_t *__restrict__ stream, uint64_t stream_cap, const zh_stitch_item_t *__restrict__ items, const zh_subblock_t *__restrict__ subs,
                     const zh_block_t *__restrict__ blocks, uint32_t nblocks, const uint8_t *__restrict__ data, const zh_scan_out_t *__restrict__ scan, const uint64_t *__restrict__ file_off,
-                    int files, uint32_t gap, zh_verify_item_t *out, zh_verify_report_t *report) {
+                    int files, uint32_t gap, const uint32_t *__restrict__ stream_of /* files == 2 */, zh_verify_item_t *out, zh_verify_report_t *report) {
    __shared__ zh_d_lds_t S;
    if (scan->failed) return;   // (nothing was stitched: the host does not ask then)
    const uint32_t nsubs = scan->nsubs;
@@ -195,7 +197,9 @@ zh_verify_subblocks(const uint32_t *__restrict__ stream, uint64_t stream_cap, co
             reason = zh_verify_one(S, stream, end_bit, it, data + blk.win_off + blk.prev + sb.start, blk.prev + sb.start, sb.size, &err_pos, &err_bit);
             if (reason == ZH_V_OK) {
                const bool last_of_block = k + 1u == nsubs || subs[k + 1u].block != sb.block;
-               const bool ends = (files && last_of_block) ? ((err_bit + 7u) >> 3) + gap == file_off[sb.block + 1u] : err_bit == (k + 1u < nsubs ? items[k + 1u].dst_bit : end_bit);
+               const bool last_of_stream = last_of_block && (files == 1 || (files == 2 && (sb.block + 1u == nblocks || (stream_of[sb.block + 1u] & ZH_STREAM_START))));
+               const uint32_t next = files == 2 ? (stream_of[sb.block] & ~ZH_STREAM_START) + 1u : sb.block + 1u;   // (what follows in file_off)
+               const bool ends = last_of_stream ? ((err_bit + 7u) >> 3) + gap == file_off[next] : err_bit == (k + 1u < nsubs ? items[k + 1u].dst_bit : end_bit);
                if (!ends) reason = ZH_V_END_BIT;
             }
          }

@@ -11,7 +11,7 @@
  *    zultra_amd_cli -x -m [-f gzip] [-d <device>] [-v] <infile> <outfile>
  *    zultra_amd_cli -x -m -r <first>:<length> [-i <file.gzi>] [-f gzip] [-d <device>] [-v] <infile> <outfile>
  *    zultra_amd_cli -f bgzf [-b <block size>] [-i <file.gzi>] [-d <device>] [-c] [-v] <infile> <outfile>
- *    zultra_amd_cli -a <archive.zip> [-d <device>] [-c] [-v] <file>...
+ *    zultra_amd_cli -a <archive.zip> [-b <max block size>] [-d <device>] [-c] [-v] <file>...
  *    zultra_amd_cli -x -a <archive.zip> [-d <device>] [-v] <outdir>
  *
  * -x -a: unzip(1) — the archive (this tool's, zip(1)'s, Python's zipfile's: stored and deflated entries) is listed, then decoded on the device
@@ -20,6 +20,7 @@
  *     or holds a ".." component, a backslash or a NUL byte. With -v one line per entry, and the entries, the index's tiles and the tiles walked again.
  * -a: a ZIP archive of the files named, every file an entry under its name as given, headers and central directory written on the device
  *     (zultra_memory_compress_zip). A file is one max-block: at most 2 MiB; an empty file is an empty entry. No dictionary.
+ *     With -b <max block size> a file is a stream of max-blocks of that size (zultra_memory_compress_zip_streams): files of any size that fit a device batch.
  * -f bgzf: bgzip(1) — <infile> in blocks of -b bytes (default and at most 65280), every block a BGZF member written on the device, and BGZF's end marker
  *     (zultra_memory_compress_bgzf); `-x -m -f gzip` is the way back. No dictionary: a member stands alone.
  * -r: with -x -m — only bytes <first> .. <first> + <length> of the concatenated output are written, and only the members that hold them are inflated
@@ -108,8 +109,9 @@ static int write_bgzf(FILE *fin, FILE *fout, unsigned block, int verbose, int ve
    return rc;
 }
 
-/* -a: the files named through zultra_memory_compress_zip */
-static int write_zip(const char *archive, char **files, int n, int verbose, int verify) {
+/* -a: the files named through zultra_memory_compress_zip; with -b (block != 0) through zultra_memory_compress_zip_streams, which takes files of any size */
+static int write_zip(const char *archive, char **files, int n, int verbose, int verify, unsigned block) {
+   const size_t largest = block ? (size_t)0xFFFFFFFEu : 2097152;
    size_t *in_off = (size_t *)calloc((size_t)n, sizeof(size_t)), *in_size = (size_t *)calloc((size_t)n, sizeof(size_t)), *name_off = (size_t *)calloc((size_t)n + 1, sizeof(size_t));
    size_t total = 0, cap = (size_t)1 << 20, names_total = 0;
    unsigned char *in = (unsigned char *)malloc(cap), *out = NULL;
@@ -123,7 +125,7 @@ static int write_zip(const char *archive, char **files, int n, int verbose, int 
          break;
       }
       in_off[k] = total;
-      for (size_t got = 1; got > 0 && total - in_off[k] <= 2097152;) {
+      for (size_t got = 1; got > 0 && total - in_off[k] <= largest;) {
          if (total == cap) {
             unsigned char *more = (unsigned char *)realloc(in, cap *= 2);
             if (!more) {
@@ -136,8 +138,8 @@ static int write_zip(const char *archive, char **files, int n, int verbose, int 
       }
       fclose(f);
       in_size[k] = total - in_off[k];
-      if (in_size[k] > 2097152) {
-         fprintf(stderr, "'%s' is larger than 2 MiB: an entry is one max-block\n", files[k]);
+      if (in_size[k] > largest) {
+         fprintf(stderr, block ? "'%s' reaches 4 GiB: ZIP64 entries are not written\n" : "'%s' is larger than 2 MiB: an entry is one max-block (-b <max block size> takes larger files)\n", files[k]);
          rc = 100;
       }
       name_off[k] = names_total;
@@ -147,7 +149,11 @@ static int write_zip(const char *archive, char **files, int n, int verbose, int 
    if (!rc) {
       names = (char *)malloc(names_total + 1);
       for (int k = 0; names && k < n; k++) memcpy(names + name_off[k], files[k], name_off[k + 1] - name_off[k]);
-      const size_t room = zultra_memory_bound_zip(total, names_total, (size_t)n);
+      size_t room = zultra_memory_bound_zip(total, names_total, (size_t)n);
+      if (block) {   /* (every stream at its bound, both copies of the names, the headers, the end records) */
+         room = 2 * names_total + 76 * (size_t)n + 98;
+         for (int k = 0; k < n; k++) room += zultra_memory_bound(in_size[k], ZULTRA_FLAG_DEFLATE_FRAMING, block);
+      }
       out = (unsigned char *)malloc(room);
       FILE *fout = names && out ? fopen(archive, "wb") : NULL;
       if (!names || !out)
@@ -157,10 +163,12 @@ static int write_zip(const char *archive, char **files, int n, int verbose, int 
       rc = fout ? 0 : 100;
       if (fout) {
          const double t0 = now_s();
-         const size_t size = zultra_memory_compress_zip(in, total, in_off, in_size, names, name_off, (size_t)n, out, room, 0);
+         const size_t size = block ? zultra_memory_compress_zip_streams(in, total, in_off, in_size, names, name_off, (size_t)n, out, room, 0, block)
+                                   : zultra_memory_compress_zip(in, total, in_off, in_size, names, name_off, (size_t)n, out, room, 0);
          const double dt = now_s() - t0;
          if (size == (size_t)-1) {
-            fprintf(stderr, "compression error (a failed verification, an empty or overlong name, a device failure, or no HIP device: this library has no CPU path)\n");
+            fprintf(stderr, "compression error (a failed verification, an empty or overlong name,%s a device failure, or no HIP device: this library has no CPU path)\n",
+                    block ? " a file of more max-blocks than a device batch holds," : "");
             rc = 100;
          }
          else if (fwrite(out, 1, size, fout) != size) {
@@ -484,12 +492,12 @@ int main(int argc, char **argv) {
                       "       %s -x -m [-f gzip] [-d <device>] [-v] <infile> <outfile>   (any number of gzip members: BGZF, pigz -i, cat a.gz b.gz)\n"
                       "       %s -x -m -r <first>:<length> [-i <file.gzi>] [-f gzip] [-d <device>] [-v] <infile> <outfile>   (a byte range of a BGZF file's output)\n"
                       "       %s -f bgzf [-b <block size, at most 65280>] [-i <file.gzi>] [-d <device>] [-c] [-v] <infile> <outfile>   (BGZF members and the end marker)\n"
-                      "       %s -a <archive.zip> [-d <device>] [-c] [-v] <file>...   (a ZIP archive: every file, of at most 2 MiB, an entry under its name)\n"
+                      "       %s -a <archive.zip> [-b <max block size>] [-d <device>] [-c] [-v] <file>...   (a ZIP archive: every file an entry under its name; of at most 2 MiB without -b)\n"
                       "       %s -x -a <archive.zip> [-d <device>] [-v] <outdir>   (unpack a ZIP archive: stored and deflated entries, checked on the device)\n", argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
       return 100;
    }
    if (archive && do_extract) return extract_zip(archive, argv[i], verbose, device);
-   if (archive) return write_zip(archive, argv + i, argc - i, verbose, verify);
+   if (archive) return write_zip(archive, argv + i, argc - i, verbose, verify, block);
    void *dict = NULL;
    int dict_size = 0;
    if (dict_name && (zultra_dictionary_load(dict_name, &dict, &dict_size) != ZULTRA_OK || dict_size <= 0)) {

@@ -70,6 +70,35 @@ int zultra_hip_device_count(void);
  * against plain LDS arithmetic. Returns 0 when they agree, a positive count of mismatches, negative on HIP errors. */
 int zultra_hip_selftest(void);
 
+/* Diagnostics: the kernels that build a sub-block's Huffman codes (zh_sb_init, zh_sb_build), run as they ship on `n` made-up
+ * sub-blocks — the test-suite compares them with the reference on histograms that no input would be found for. Needs no context.
+ *   mode INIT : sub-block i owns the tokens [tok_off[i], tok_off[i + 1]) of tok_info (one uint16 per token: literal/length symbol
+ *               below 288 | distance symbol << 9); the kernel takes their histogram, adds the end-of-block symbol, prices the
+ *               static and the dynamic form, and builds the first codes.
+ *   mode BUILD: sub-block i owns rows [i * ntasks, (i + 1) * ntasks) of hist_part, ZULTRA_HIP_ENTROPY_NSYM counts each (288
+ *               literal/length, 32 distance), which the kernel sums and adds the end-of-block symbol to; `pass` is 0..3 (3 = the
+ *               last: distance-code fix, RLE-friendly alternative, block header); in_force holds 320 code lengths per sub-block,
+ *               the ones a pass before would have left (passes 0..2 compare theirs with them: `settled`).
+ * Sub-blocks [0, grid) are worked on by the one-per-workgroup form of the kernel and [grid, n) by the striding form (1 <= grid <= n).
+ * recs[n] receives the coder states (codes of symbols without a length are undefined), slots[n * ZULTRA_HIP_ENTROPY_SLOT] the
+ * header bits of each sub-block (zero beyond hdr_bits), settled[2] — may be NULL — the run's two counters of settled sub-blocks
+ * (passes saved; the same weighted by the sub-block's KiB, which the probe sets to one). Returns 0, or a negative error. */
+#define ZULTRA_HIP_ENTROPY_INIT 0
+#define ZULTRA_HIP_ENTROPY_BUILD 1
+#define ZULTRA_HIP_ENTROPY_NSYM 320
+#define ZULTRA_HIP_ENTROPY_SLOT 1024
+typedef struct zultra_hip_entropy_rec_s {
+   uint8_t lit_len[288], dist_len[32];
+   uint16_t lit_code[288], dist_code[32];
+   uint8_t pre_lit_len[288], pre_dist_len[32];   /* lengths of the last pass before the RLE-friendly alternative */
+   uint32_t is_dynamic, failed, hdr_bits;
+   int32_t static_cost, dynamic_cost;
+   uint32_t settled;
+   uint32_t reserved[2];
+} zultra_hip_entropy_rec_t;
+int zultra_hip_entropy_probe(int mode, uint32_t n, uint32_t grid, int pass, uint32_t ntasks, const uint32_t *hist_part, const uint8_t *in_force,
+                             const uint16_t *tok_info, const uint32_t *tok_off, zultra_hip_entropy_rec_t *recs, uint8_t *slots, uint32_t *settled);
+
 /* Diagnostics: a streaming 4-byte-per-lane copy of `nbytes`, used to calibrate the rocprofv3 FETCH_SIZE / WRITE_SIZE
  * counters for this access width (profiles/, tools/pmc_traffic.py). Returns 0 on success. */
 int zultra_hip_traffic_probe(size_t nbytes);

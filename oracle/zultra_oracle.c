@@ -850,6 +850,78 @@ static int emit_tokens(zo_ctx_t *c, zo_bits_t *out, int start, int end) {
    return 0;
 }
 
+/* blockdeflate.c:893-913: at least two distance codes among 0..29, for pre-1.2.1.1 zlib inflate */
+static void fix_distance_codes(zo_huff_t *dist) {
+   int used = 0, s;
+   for (s = 0; used < 2 && s < NDIST - 2; s++)
+      if (dist->freq[s]) used++;
+   if (used == 0)
+      dist->freq[0] = dist->freq[1] = 1;
+   else if (used == 1) {
+      if (dist->freq[0])
+         dist->freq[1] = 1;
+      else
+         dist->freq[0] = 1;
+   }
+}
+
+/* blockdeflate.c:925-992: the RLE-friendlier alternative, the search over the 20 code-length masks and the block header.
+ * lit / dist hold the histograms of the last parse and the codes built from them; they leave with the codes that were chosen. */
+static int final_tables_and_header(zo_huff_t *lit, zo_huff_t *dist, zo_bits_t *out) {
+   {
+      /* blockdeflate.c:925-945: RLE-friendlier tables, adopted only if strictly cheaper overall */
+      zo_huff_t alt_lit = *lit, alt_dist = *dist;
+      int cur_cost = dynamic_cost(&alt_lit, &alt_dist), alt_cost;
+      smooth_for_rle(NLIT, alt_lit.freq);
+      smooth_for_rle(NDIST, alt_dist.freq);
+      if (huff_build_dynamic(&alt_lit) < 0 || huff_build_dynamic(&alt_dist) < 0) return -1;
+      alt_cost = dynamic_cost(&alt_lit, &alt_dist);
+      if (alt_cost < cur_cost) {
+         *lit = alt_lit;
+         *dist = alt_dist;
+      }
+   }
+
+   {
+      /* blockdeflate.c:947-992: header */
+      zo_huff_t tables;
+      int lens[NLIT + NDIST];
+      int nlit = huff_defined_count(lit, 257);
+      int ndist = huff_defined_count(dist, 1);
+      int best_mask = -1, best_cost = 0, mask, ncl, k;
+      cl_write_ctx w;
+
+      memcpy(lens, lit->len, (size_t)nlit * sizeof(int));
+      memcpy(lens + nlit, dist->len, (size_t)ndist * sizeof(int));
+
+      huff_init(&tables, NCL, 7);
+      for (mask = 0; mask <= 31; mask += (mask >= 7) ? 2 : 1) {
+         int cost;
+         cl_tokenize(lens, nlit + ndist, (unsigned)mask, cl_sink_count, &tables);
+         if (huff_build_dynamic(&tables) < 0) return -1;
+         cost = cl_size(&tables, lens, nlit + ndist, (unsigned)mask);
+         if (best_mask == -1 || best_cost >= cost) {   /* last minimal mask wins (:966) */
+            best_mask = mask;
+            best_cost = cost;
+         }
+         memset(tables.freq, 0, sizeof(tables.freq));
+      }
+      cl_tokenize(lens, nlit + ndist, (unsigned)best_mask, cl_sink_count, &tables);
+      if (huff_build_dynamic(&tables) < 0) return -1;
+
+      ncl = huff_raw_table_size(&tables);
+      if (nlit > 286 || ndist > 30 || ncl > NCL) return -1;
+      bits_put(out, (uint32_t)(nlit - 257), 5);
+      bits_put(out, (uint32_t)(ndist - 1), 5);
+      bits_put(out, (uint32_t)(ncl - 4), 4);
+      for (k = 0; k < ncl; k++) bits_put(out, (uint32_t)tables.len[g_cl_order[k]], 3);
+      w.h = &tables;
+      w.out = out;
+      cl_tokenize(lens, nlit + ndist, (unsigned)best_mask, cl_sink_write, &w);
+   }
+   return 0;
+}
+
 static int deflate_subblock(zo_ctx_t *c, zo_bits_t *out, int start, int size, int is_dynamic) {
    const int end = start + size;
    int s, pass;
@@ -883,76 +955,13 @@ static int deflate_subblock(zo_ctx_t *c, zo_bits_t *out, int start, int size, in
       memset(c->dist.freq, 0, sizeof(c->dist.freq));
       parse_histogram(c, start, end);
 
-      if (pass == 3) {
-         /* at least two distance codes among 0..29, for pre-1.2.1.1 zlib inflate (:893-913) */
-         int used = 0;
-         for (s = 0; used < 2 && s < NDIST - 2; s++)
-            if (c->dist.freq[s]) used++;
-         if (used == 0)
-            c->dist.freq[0] = c->dist.freq[1] = 1;
-         else if (used == 1) {
-            if (c->dist.freq[0])
-               c->dist.freq[1] = 1;
-            else
-               c->dist.freq[0] = 1;
-         }
-      }
+      if (pass == 3) fix_distance_codes(&c->dist);
       if (huff_build_dynamic(&c->lit) < 0 || huff_build_dynamic(&c->dist) < 0) return -1;
    }
 
    literalize_cheap_matches(c, start, end);   /* histograms intentionally left stale (:923) */
 
-   {
-      /* blockdeflate.c:925-945: RLE-friendlier tables, adopted only if strictly cheaper overall */
-      zo_huff_t alt_lit = c->lit, alt_dist = c->dist;
-      int cur_cost = dynamic_cost(&alt_lit, &alt_dist), alt_cost;
-      smooth_for_rle(NLIT, alt_lit.freq);
-      smooth_for_rle(NDIST, alt_dist.freq);
-      if (huff_build_dynamic(&alt_lit) < 0 || huff_build_dynamic(&alt_dist) < 0) return -1;
-      alt_cost = dynamic_cost(&alt_lit, &alt_dist);
-      if (alt_cost < cur_cost) {
-         c->lit = alt_lit;
-         c->dist = alt_dist;
-      }
-   }
-
-   {
-      /* blockdeflate.c:947-992: header */
-      zo_huff_t tables;
-      int lens[NLIT + NDIST];
-      int nlit = huff_defined_count(&c->lit, 257);
-      int ndist = huff_defined_count(&c->dist, 1);
-      int best_mask = -1, best_cost = 0, mask, ncl, k;
-      cl_write_ctx w;
-
-      memcpy(lens, c->lit.len, (size_t)nlit * sizeof(int));
-      memcpy(lens + nlit, c->dist.len, (size_t)ndist * sizeof(int));
-
-      huff_init(&tables, NCL, 7);
-      for (mask = 0; mask <= 31; mask += (mask >= 7) ? 2 : 1) {
-         int cost;
-         cl_tokenize(lens, nlit + ndist, (unsigned)mask, cl_sink_count, &tables);
-         if (huff_build_dynamic(&tables) < 0) return -1;
-         cost = cl_size(&tables, lens, nlit + ndist, (unsigned)mask);
-         if (best_mask == -1 || best_cost >= cost) {   /* last minimal mask wins (:966) */
-            best_mask = mask;
-            best_cost = cost;
-         }
-         memset(tables.freq, 0, sizeof(tables.freq));
-      }
-      cl_tokenize(lens, nlit + ndist, (unsigned)best_mask, cl_sink_count, &tables);
-      if (huff_build_dynamic(&tables) < 0) return -1;
-
-      ncl = huff_raw_table_size(&tables);
-      if (nlit > 286 || ndist > 30 || ncl > NCL) return -1;
-      bits_put(out, (uint32_t)(nlit - 257), 5);
-      bits_put(out, (uint32_t)(ndist - 1), 5);
-      bits_put(out, (uint32_t)(ncl - 4), 4);
-      for (k = 0; k < ncl; k++) bits_put(out, (uint32_t)tables.len[g_cl_order[k]], 3);
-      w.h = &tables;
-      w.out = out;
-      cl_tokenize(lens, nlit + ndist, (unsigned)best_mask, cl_sink_write, &w);
-   }
+   if (final_tables_and_header(&c->lit, &c->dist, out) < 0) return -1;
 
    return emit_tokens(c, out, start, end);
 }
@@ -983,6 +992,110 @@ int zo_subblock_deflate(const uint8_t *win, const zo_match_t *match, int prev, i
    free(c.cost);
    free(c.best);
    return r;
+}
+
+/* ---- the entropy stage on given histograms (twins of the device's zultra_hip_entropy_probe) ---------- */
+
+static void rec_codes(zo_entropy_rec_t *rec, const zo_huff_t *lit, const zo_huff_t *dist) {
+   int s;
+   for (s = 0; s < NLIT; s++) {
+      rec->lit_len[s] = (uint8_t)lit->len[s];
+      rec->lit_code[s] = (uint16_t)(lit->len[s] ? lit->code[s] : 0);   /* a symbol without a length has no code */
+   }
+   for (s = 0; s < NDIST; s++) {
+      rec->dist_len[s] = (uint8_t)dist->len[s];
+      rec->dist_code[s] = (uint16_t)(dist->len[s] ? dist->code[s] : 0);
+   }
+}
+
+static void rec_pre(zo_entropy_rec_t *rec, const zo_huff_t *lit, const zo_huff_t *dist) {
+   int s;
+   for (s = 0; s < NLIT; s++) rec->pre_lit_len[s] = (uint8_t)lit->len[s];
+   for (s = 0; s < NDIST; s++) rec->pre_dist_len[s] = (uint8_t)dist->len[s];
+}
+
+int zo_entropy_init(const uint16_t *tok, uint32_t ntok, zo_entropy_rec_t *rec) {
+   zo_huff_t lit, dist;
+   uint32_t t;
+   int s, d;
+
+   zo_init_tables();
+   memset(rec, 0, sizeof(*rec));
+   huff_init(&lit, NLIT, 15);
+   huff_init(&dist, NDIST, 15);
+   for (t = 0; t < ntok; t++) {
+      int sym = tok[t] & 511;
+      if (sym >= NLIT) return -1;
+      lit.freq[sym]++;
+      if (sym > EOB) dist.freq[(tok[t] >> 9) & 31]++;
+   }
+   lit.freq[EOB]++;
+
+   /* libzultra.c:317-324 */
+   s = static_cost(&lit, &dist);
+   huff_lengths(&lit);
+   huff_lengths(&dist);
+   d = dynamic_cost(&lit, &dist);
+   rec->static_cost = s;
+   rec->dynamic_cost = d;
+   rec->is_dynamic = (s <= d) ? 0u : 1u;
+
+   if (!rec->is_dynamic) {
+      /* blockdeflate.c:836-858 */
+      for (s = 0; s < NLIT; s++) lit.len[s] = static_lit_len(s);
+      for (s = 0; s < NDIST; s++) dist.len[s] = 5;
+      huff_build_static(&lit);
+      huff_build_static(&dist);
+   }
+   else {
+      /* blockdeflate.c:859-868 */
+      if (huff_build_dynamic(&lit) < 0) rec->failed = 1;
+      if (huff_build_dynamic(&dist) < 0) rec->failed = 1;
+   }
+   rec_codes(rec, &lit, &dist);
+   rec_pre(rec, &lit, &dist);
+   return 0;
+}
+
+int zo_entropy_build(const uint32_t *hist, int pass, const uint8_t *in_force, zo_entropy_rec_t *rec, uint8_t *hdr, size_t cap) {
+   zo_huff_t lit, dist;
+   zo_bits_t out;
+   int s;
+
+   zo_init_tables();
+   memset(rec, 0, sizeof(*rec));
+   rec->is_dynamic = 1;
+   huff_init(&lit, NLIT, 15);
+   huff_init(&dist, NDIST, 15);
+   for (s = 0; s < NLIT; s++) lit.freq[s] = (int)hist[s];
+   for (s = 0; s < NDIST; s++) dist.freq[s] = (int)hist[NLIT + s];
+   lit.freq[EOB]++;
+
+   /* blockdeflate.c:893-919 */
+   if (pass == 3) fix_distance_codes(&dist);
+   if (huff_build_dynamic(&lit) < 0) rec->failed = 1;
+   if (huff_build_dynamic(&dist) < 0) rec->failed = 1;
+
+   if (pass < 3) {
+      /* the next pass prices with these lengths, unused symbols at 9 / 6 bits (:873-881): are they the ones in force? */
+      int moved = 0;
+      for (s = 0; s < NLIT; s++) moved |= (lit.len[s] ? lit.len[s] : 9) != (in_force[s] ? in_force[s] : 9);
+      for (s = 0; s < NDIST; s++) moved |= (dist.len[s] ? dist.len[s] : 6) != (in_force[NLIT + s] ? in_force[NLIT + s] : 6);
+      rec->settled = (!moved && !rec->failed) ? 1u : 0u;
+      rec_codes(rec, &lit, &dist);
+      return 0;
+   }
+
+   rec_pre(rec, &lit, &dist);
+   out.buf = hdr;
+   out.cap = cap;
+   out.nbits = 0;
+   if (rec->failed || final_tables_and_header(&lit, &dist, &out) < 0)
+      rec->failed = 1;
+   else
+      rec->hdr_bits = (uint32_t)out.nbits;
+   rec_codes(rec, &lit, &dist);
+   return 0;
 }
 
 /* ------------------------------------------------------------------------------------------------ */

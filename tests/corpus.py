@@ -211,10 +211,13 @@ def table_like(size, seed=1):
 
 
 def fibonacci_bytes(k=19, seed=1):
-    """Bytes whose counts are the Fibonacci numbers F(1)..F(k), shuffled: the unlimited Huffman tree of such a histogram is
-    a chain of depth k-1 (> 15 from k = 17: the cost estimates price code lengths the format cannot even encode). Matches
-    flatten the token histogram, so this only leans on the deep-tree paths; the regression test for code lengths above 15
-    in the cost estimates is the 2 MiB block of source code in test_gpu_parity.py."""
+    """Bytes whose counts are the Fibonacci numbers F(1)..F(k), shuffled. As a HISTOGRAM such counts lean less than they look: next to the end-of-block
+    symbol's 1 they start with three counts of 1, the tie splits the chain into two interleaved ones, and the longest code of F(1)..F(20) plus end-of-block
+    is 11 bits, not 19 (F(2)..F(20) plus end-of-block does give 19: tests/entropy_cases.py builds its chains that way). And the kernels never see this
+    histogram: matches flatten it. Counted over every code build of the windows the suite makes of it, the longest unlimited literal/length code is 12 bits
+    for k = 19 and 13 for k = 22 — no length limiting at all (tests/test_entropy_emu.py). What it does give is a skewed literal alphabet with long
+    distances; code lengths above 15 in the cost estimates come from the 2 MiB block of source code in test_gpu_parity.py, and the limiter itself is
+    tested on chosen histograms (tests/test_entropy_emu.py, tests/test_entropy_gpu.py)."""
     rs = np.random.RandomState(seed)
     fib = [1, 1]
     while len(fib) < k:

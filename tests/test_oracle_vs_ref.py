@@ -257,3 +257,56 @@ def test_fuzz_streams(oracle, answers, live_ref):
 
 def test_checksums(oracle, answers, live_ref):
     _verify("checksums", oracle, answers, live_ref)
+
+
+# ---- the entropy stage on chosen histograms (tests/entropy_cases.py): the two oracle calls the emulator and GPU tests may be checked with, pinned to the
+# compiled reference over every case, and what the cases reach, asserted from the reference side alone ----------------------------------------------------
+
+def _entropy_ref(ref):
+    if not ref.has_entropy:
+        pytest.skip("this build of the compiled reference (oracle/_ref) is from before oracle/ref_probe.c had the entropy probes, and the sources to make it again are not here")
+    return ref
+
+
+def test_entropy_oracle_matches_reference_on_every_case(oracle, ref):
+    import entropy_cases as ec
+    ref = _entropy_ref(ref)
+    case_list = ec.cases(ec.FULL)
+    names, hist = [n for n, _ in case_list], ec.hist_of(case_list)
+    zeros = np.zeros((len(hist), ec.NSYM), dtype=np.uint8)
+    same = ec.lengths_of(ref.entropy_build(hist, 0, zeros)[0])
+    for in_force, settled in ((zeros, None), (same, 1), (ec.changed_lengths(same), 0)):
+        want = ref.entropy_build(hist, 0, in_force)
+        assert settled is None or (want[0]["settled"] == settled).all()
+        ec.assert_same(oracle.entropy_build(hist, 0, in_force), want, names, "oracle, pass 0")
+    want = ref.entropy_build(hist, 3, zeros)
+    ec.assert_same(oracle.entropy_build(hist, 3, zeros), want, names, "oracle, pass 3")
+    assert [n for n, r in zip(names, want[0]) if r["failed"]] == ["symbol_287"]
+    assert (want[0]["hdr_bits"][want[0]["failed"] == 0] > 14 + 3 * 4).all()
+    for i in range(0, len(case_list), 256):   # (token lists of up to 64 Ki entries each: a few at a time)
+        tok_info, tok_off = ec.init_input(case_list[i:i + 256])
+        want = ref.entropy_init(tok_info, tok_off)
+        ec.assert_same(oracle.entropy_init(tok_info, tok_off), want, names[i:i + 256], "oracle, init")
+        assert not want[0]["failed"].any()
+
+
+def test_entropy_cases_reach_the_limiter_and_never_run_off_its_list(ref):
+    """Observed (5 000 random cases and the fixed ones): profiles/entropy_probe.txt."""
+    import entropy_cases as ec
+    case_list = ec.cases(ec.FULL)   # (asked of the reference's encoder functions, which every build of it has)
+    table, alt_won, masks, hclens, past = ec.coverage(ref, case_list)
+    print("coverage of %d cases: %r, alternative won %d, masks %r, hclen %r" % (len(case_list), table, alt_won, sorted(masks.items()), sorted(hclens.items())))
+    assert past == [], "cases where the reference's repair reads past its symbol list are not cases: %s" % past
+    for alphabet, (limited, third) in table.items():
+        assert limited > 0 and third > 0, (alphabet, limited, third)
+    assert 0 < alt_won < len(case_list)
+    assert len(masks) >= 8 and 0 in masks and 31 in masks, sorted(masks)
+    assert 19 in hclens and min(hclens) == 16, sorted(hclens.items())   # (16: the smallest HCLEN the reference writes for any of the cases)
+    # the init mode builds from the same histograms (halved where the token list would be long), without the distance-code fix
+    init = [ec.init_facts(ref, ec.init_hist(n, h)) for n, h in case_list]
+    assert not any(lit[2] or dist[2] for lit, dist in init)
+    assert sum(lit[0] for lit, _ in init) > 0 and sum(dist[0] for _, dist in init) > 0 and sum(lit[1] for lit, _ in init) > 0 and sum(dist[1] for _, dist in init) > 0
+    # the smaller lists of the emulator and GPU tests are parts of this one
+    full = {n: h.tobytes() for n, h in case_list}
+    for part in (ec.EMU, ec.GPU):
+        assert all(full.get(n) == h.tobytes() for n, h in ec.cases(part))

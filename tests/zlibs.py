@@ -23,6 +23,38 @@ MAX_SPLITS = 64
 
 _u8p = C.POINTER(C.c_uint8)
 
+# the record of the entropy probes: zo_entropy_rec_t (oracle/zultra_oracle.h) = ref_entropy_rec_t (oracle/ref_probe.c) = zultra_hip_entropy_rec_t (include/zultra_hip.h)
+ENTROPY_REC = np.dtype([("lit_len", "u1", 288), ("dist_len", "u1", 32), ("lit_code", "<u2", 288), ("dist_code", "<u2", 32), ("pre_lit_len", "u1", 288), ("pre_dist_len", "u1", 32),
+                        ("is_dynamic", "<u4"), ("failed", "<u4"), ("hdr_bits", "<u4"), ("static_cost", "<i4"), ("dynamic_cost", "<i4"), ("settled", "<u4"), ("reserved", "<u4", 2)])
+ENTROPY_NSYM = 320
+ENTROPY_SLOT = 1024   # bytes of header a probe may write per sub-block (ZULTRA_HIP_ENTROPY_SLOT)
+
+
+def _entropy_init(f, tok_info, tok_off):
+    """f(tok, ntok, rec) over the sub-blocks of (tok_info, tok_off) -> (records, slots): the device probe's return, the slots empty."""
+    tok_info = np.ascontiguousarray(tok_info, dtype=np.uint16)
+    n = len(tok_off) - 1
+    recs = np.zeros(n, dtype=ENTROPY_REC)
+    for i in range(n):
+        rc = f(tok_info.ctypes.data + 2 * int(tok_off[i]), int(tok_off[i + 1]) - int(tok_off[i]), recs.ctypes.data + i * ENTROPY_REC.itemsize)
+        assert rc == 0, (i, rc)
+    return recs, np.zeros((n, ENTROPY_SLOT), dtype=np.uint8)
+
+
+def _entropy_build(f, hist, pass_, in_force):
+    """f(hist, pass, in_force, rec, hdr, cap) over the rows of hist[n, 320] -> (records, slots)"""
+    hist = np.ascontiguousarray(hist, dtype=np.uint32)
+    in_force = np.ascontiguousarray(in_force, dtype=np.uint8)
+    n = len(hist)
+    assert hist.shape == (n, ENTROPY_NSYM) and in_force.shape == (n, ENTROPY_NSYM)
+    recs = np.zeros(n, dtype=ENTROPY_REC)
+    slots = np.zeros((n, ENTROPY_SLOT), dtype=np.uint8)
+    for i in range(n):
+        rc = f(hist.ctypes.data + i * 4 * ENTROPY_NSYM, pass_, in_force.ctypes.data + i * ENTROPY_NSYM, recs.ctypes.data + i * ENTROPY_REC.itemsize,
+               slots.ctypes.data + i * ENTROPY_SLOT, ENTROPY_SLOT)
+        assert rc == 0, (i, rc)
+    return recs, slots
+
 
 def _ptr(a, t=_u8p):
     return a.ctypes.data_as(t)
@@ -39,6 +71,13 @@ def build_oracle():
             subprocess.run(["make", "-s", "-C", ORACLE_DIR, "ref"], check=True)
 
 
+def _exports(so, name):
+    """Does the shared library name this symbol? (asked of the file, before it is loaded: a library built from older sources may lie where a newer one belongs,
+    with a newer date than the sources of a fresh checkout)"""
+    with open(so, "rb") as f:
+        return name.encode() in f.read()
+
+
 def as_u8(data):
     if isinstance(data, np.ndarray):
         return np.ascontiguousarray(data, dtype=np.uint8)
@@ -49,7 +88,9 @@ class Oracle:
     def __init__(self):
         if not os.path.exists(ORACLE_SO) or os.path.getmtime(ORACLE_SO) < os.path.getmtime(
             os.path.join(ORACLE_DIR, "zultra_oracle.c")
-        ):
+        ) or not _exports(ORACLE_SO, "zo_entropy_build"):
+            if os.path.exists(ORACLE_SO):
+                os.remove(ORACLE_SO)   # (make goes by dates)
             build_oracle()
         L = self.lib = C.CDLL(ORACLE_SO)
         L.zo_find_matches.argtypes = [_u8p, C.c_int, C.c_int, C.c_void_p]
@@ -70,6 +111,10 @@ class Oracle:
         L.zo_adler32.argtypes = [C.c_uint32, _u8p, C.c_size_t]
         L.zo_adler32.restype = C.c_uint32
         L.zo_last_match_candidates.restype = C.c_uint64
+        L.zo_entropy_init.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
+        L.zo_entropy_init.restype = C.c_int
+        L.zo_entropy_build.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
+        L.zo_entropy_build.restype = C.c_int
 
     def find_matches(self, win, prev, n):
         """-> uint16 array [n, 8, 2] (length, offset)."""
@@ -105,6 +150,14 @@ class Oracle:
         nb = nbits.value
         return rc, nb, out[: min(cap, (nb + 7) // 8)].tobytes(), best, ll, dl
 
+    def entropy_init(self, tok_info, tok_off):
+        """Prices, type and first codes of sub-blocks given by their greedy tokens (zo_entropy_init) -> (records of ENTROPY_REC, slots)."""
+        return _entropy_init(self.lib.zo_entropy_init, tok_info, tok_off)
+
+    def entropy_build(self, hist, pass_, in_force):
+        """Codes after parse pass pass_ of sub-blocks given by the histogram of that parse (zo_entropy_build) -> (records, slots with the headers)."""
+        return _entropy_build(self.lib.zo_entropy_build, hist, pass_, in_force)
+
     def memory_bound(self, n, flags, max_block):
         return self.lib.zo_memory_bound(n, flags, max_block)
 
@@ -139,6 +192,16 @@ class Ref:
     """The compiled reference + probes (oracle/ref_probe.c)."""
 
     def __init__(self):
+        if not _exports(REF_SO, "ref_probe_entropy_build") and os.path.isdir("/root/reference/src"):
+            # a build of before oracle/ref_probe.c had the entropy probes, and the sources to make it again (once: a test process next to this one may have
+            # loaded the new file by the time this one holds the lock)
+            import fcntl
+            os.makedirs(os.path.join(ORACLE_DIR, "_build"), exist_ok=True)
+            with open(os.path.join(ORACLE_DIR, "_build", ".lock"), "w") as lock:
+                fcntl.flock(lock, fcntl.LOCK_EX)
+                if not _exports(REF_SO, "ref_probe_entropy_build"):
+                    os.remove(REF_SO)
+                    subprocess.run(["make", "-s", "-C", ORACLE_DIR, "ref"], check=True)
         L = self.lib = C.CDLL(REF_SO)
         L.zultra_memory_compress.argtypes = [_u8p, C.c_size_t, _u8p, C.c_size_t, C.c_uint, C.c_uint]
         L.zultra_memory_compress.restype = C.c_size_t
@@ -161,6 +224,19 @@ class Ref:
         L.ref_probe_get_codelens.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.zultra_frame_update_checksum.argtypes = [C.c_uint, _u8p, C.c_size_t, C.c_uint]
         L.zultra_frame_update_checksum.restype = C.c_uint
+        # the entropy probes: a compiled reference that travelled here from a build of before they were written lacks them, and every other leg still runs on it
+        self.has_entropy = hasattr(L, "ref_probe_entropy_init") and hasattr(L, "ref_probe_entropy_build")
+        if self.has_entropy:
+            L.ref_probe_entropy_init.argtypes = [C.c_void_p, C.c_uint, C.c_void_p]
+            L.ref_probe_entropy_init.restype = C.c_int
+            L.ref_probe_entropy_build.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+            L.ref_probe_entropy_build.restype = C.c_int
+
+    def entropy_init(self, tok_info, tok_off):
+        return _entropy_init(self.lib.ref_probe_entropy_init, tok_info, tok_off)
+
+    def entropy_build(self, hist, pass_, in_force):
+        return _entropy_build(self.lib.ref_probe_entropy_build, hist, pass_, in_force)
 
     def memory_bound(self, n, flags, max_block):
         return self.lib.zultra_memory_bound(n, flags, max_block)
@@ -278,6 +354,21 @@ class RefStages:
         p = self._probe
         assert p is not None and p.prev == prev, "deflate() follows find_matches() on the same window"
         return p.deflate(start, size, is_dynamic)
+
+    def _entropy(self):
+        """The compiled reference's entropy probes; where this build of it has none (and cannot be made again), the restatement that
+        tests/test_oracle_vs_ref.py pins to them — what the `checker` is wherever there is no compiled reference at all."""
+        if self.ref.has_entropy:
+            return self.ref
+        if getattr(self, "_oracle", None) is None:
+            self._oracle = Oracle()
+        return self._oracle
+
+    def entropy_init(self, tok_info, tok_off):
+        return self._entropy().entropy_init(tok_info, tok_off)
+
+    def entropy_build(self, hist, pass_, in_force):
+        return self._entropy().entropy_build(hist, pass_, in_force)
 
     def memory_bound(self, n, flags, max_block):
         return self.ref.memory_bound(n, flags, max_block)

@@ -116,6 +116,11 @@ ZIP_DIRENT_DTYPE = [("central_at", "<u8"), ("local_off", "<u8"), ("dst_off", "<u
 ZIP_INFO_DTYPE = np.dtype([("nNameAt", "<u8"), ("nNameLen", "<u4"), ("nMethod", "<u4"), ("nFlags", "<u4"), ("nCrc32", "<u4"), ("nCompSize", "<u4"), ("nSize", "<u4"),
                            ("nOutOff", "<u8"), ("nStatus", "<u4")], align=True)   # zultra_zip_info_t
 STITCH_ITEM_DTYPE = [("dst_bit", "<u8"), ("stored", "<u4"), ("is_final", "<u4")]   # zh_stitch_item_t (zultra_hip_stitch_items)
+# zultra_hip_entropy_rec_t (zultra_hip_entropy_probe)
+ENTROPY_REC_DTYPE = np.dtype([("lit_len", "u1", 288), ("dist_len", "u1", 32), ("lit_code", "<u2", 288), ("dist_code", "<u2", 32), ("pre_lit_len", "u1", 288), ("pre_dist_len", "u1", 32),
+                              ("is_dynamic", "<u4"), ("failed", "<u4"), ("hdr_bits", "<u4"), ("static_cost", "<i4"), ("dynamic_cost", "<i4"), ("settled", "<u4"), ("reserved", "<u4", 2)])
+ENTROPY_NSYM = 320    # ZULTRA_HIP_ENTROPY_NSYM
+ENTROPY_SLOT = 1024   # ZULTRA_HIP_ENTROPY_SLOT
 MEMBER_RESULT_DTYPE = [("reason", "<u4"), ("blocks", "<u4"), ("out_size", "<u8"), ("src_used", "<u8"), ("head_size", "<u4"), ("check", "<u4")]
 
 
@@ -127,7 +132,7 @@ EXPORTS = [
     "zultra_frame_update_checksum", "zultra_frame_get_footer_size", "zultra_frame_encode_footer",
     "zultra_dictionary_load", "zultra_dictionary_free",
     # include/zultra_hip.h
-    "zultra_hip_device_count", "zultra_hip_selftest", "zultra_hip_traffic_probe", "zultra_hip_create", "zultra_hip_destroy", "zultra_hip_last_error",
+    "zultra_hip_device_count", "zultra_hip_selftest", "zultra_hip_entropy_probe", "zultra_hip_traffic_probe", "zultra_hip_create", "zultra_hip_destroy", "zultra_hip_last_error",
     "zultra_hip_data_capacity", "zultra_hip_compress_blocks", "zultra_hip_subblocks", "zultra_hip_payload",
     "zultra_hip_last_timing", "zultra_hip_get_matches", "zultra_hip_get_splits", "zultra_hip_get_parse",
     "zultra_hip_stitch", "zultra_hip_stitch_finish",
@@ -222,6 +227,34 @@ class Lib:
     def traffic_probe(self, nbytes):
         self.L.zultra_hip_traffic_probe.argtypes = [C.c_size_t]
         return self.L.zultra_hip_traffic_probe(nbytes)
+
+    def entropy_probe(self, grid=None, hist_part=None, in_force=None, pass_=0, tok_info=None, tok_off=None):
+        """zh_sb_build on hist_part[n, ntasks, 320] with the lengths in_force[n, 320] (pass_ 0..3), or zh_sb_init on the tokens tok_info[tok_off[i]:tok_off[i + 1]]
+        of sub-block i; sub-blocks [0, grid) in the one-per-workgroup form, the rest in the striding form (grid None: all in the first).
+        -> (records [n] of ENTROPY_REC_DTYPE, slots uint8 [n, ENTROPY_SLOT], (settled, settled_kib))"""
+        f = self.L.zultra_hip_entropy_probe
+        f.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32] + [C.c_void_p] * 7
+        f.restype = C.c_int
+        if hist_part is not None:
+            hist_part = np.ascontiguousarray(hist_part, dtype=np.uint32)
+            n, ntasks, nsym = hist_part.shape
+            in_force = np.ascontiguousarray(in_force, dtype=np.uint8)
+            assert nsym == ENTROPY_NSYM and in_force.shape == (n, ENTROPY_NSYM)
+            args = (1, n, n if grid is None else grid, pass_, ntasks, hist_part.ctypes.data, in_force.ctypes.data, None, None)
+        else:
+            tok_info = np.ascontiguousarray(tok_info, dtype=np.uint16)
+            tok_off = np.ascontiguousarray(tok_off, dtype=np.uint32)
+            n = len(tok_off) - 1
+            assert n >= 1 and int(tok_off[-1]) == len(tok_info)
+            keep = np.zeros(1, dtype=np.uint16) if len(tok_info) == 0 else tok_info   # (a pointer that is not NULL)
+            args = (0, n, n if grid is None else grid, 0, 0, None, None, keep.ctypes.data, tok_off.ctypes.data)
+        recs = np.zeros(n, dtype=ENTROPY_REC_DTYPE)
+        slots = np.zeros((n, ENTROPY_SLOT), dtype=np.uint8)
+        settled = np.zeros(2, dtype=np.uint32)
+        rc = f(*args, recs.ctypes.data, slots.ctypes.data, settled.ctypes.data)
+        if rc != 0:
+            raise ZultraError("zultra_hip_entropy_probe failed: %d" % rc)
+        return recs, slots, (int(settled[0]), int(settled[1]))
 
     def runs_for(self, batch_bytes, nblocks, streams_setting=0):
         """Staggered runs a batch is cut into (zultra_hip_runs_for: pure, no device)."""

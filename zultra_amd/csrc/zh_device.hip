@@ -297,6 +297,17 @@ ZH_HIDDEN uint32_t zh_clamp_block(uint32_t n) {
    return n;
 }
 
+// A kernel whose item count only the device knows (sub-blocks, tasks, segment waves of a run): the <false> form over `grid_` workgroups, one item each (what data
+// usually gives; surplus workgroups leave at once), then — unless the run bets that there is nothing (no_more_) — the <true> form, ZH_MORE_GRID workgroups striding over
+// what lies beyond grid_: nearly always nothing. (bound_: what the item count cannot exceed — a grid that covers it needs no second launch: a call on a few max-blocks is
+// a matter of launches)
+#define ZH_MORE_GRID 256u
+#define ZH_LAUNCH_BOTH(kernel_, grid_, bound_, no_more_, stream_, ...)                                                                                \
+   do {                                                                                                                                               \
+      ZH_LAUNCH(kernel_<false>, (grid_), 64, stream_, __VA_ARGS__, 0u);                                                                               \
+      if ((uint64_t)(grid_) < (uint64_t)(bound_) && !(no_more_)) ZH_LAUNCH(kernel_<true>, ZH_MORE_GRID, 64, stream_, __VA_ARGS__, (uint32_t)(grid_)); \
+   } while (0)
+
 // ---- wave primitive self-check -------------------------------------------------------------------------------
 __global__ void __launch_bounds__(64) zh_selftest_kernel(uint32_t seed, uint32_t *bad) {
    __shared__ uint32_t v[64];
@@ -420,6 +431,88 @@ extern "C" int zultra_hip_selftest(void) {
    if (hipMemcpy(&bad, d_bad, sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess) return -4;
    (void)hipFree(d_bad);
    return (int)bad;
+}
+
+// ---- the code-building kernels on given histograms -------------------------------------------------------------------
+// zh_sb_init / zh_sb_build as they ship, on `n` made-up sub-blocks: no context, no input bytes, no parse. What a batch would have left
+// in HBM for them is fabricated here — a work item, a coder state, a payload slot per sub-block and a run's counter block that says
+// n sub-blocks and nothing else (no bet: zh_run_is_void is false) — and the state records and slots are copied back as they are.
+// Nothing of the kernels is restated: this fills buffers and launches.
+static_assert(sizeof(zultra_hip_entropy_rec_t) == sizeof(zh_sbstate_t), "the probe hands the coder states back as they lie in HBM");
+static_assert(ZULTRA_HIP_ENTROPY_NSYM == ZH_NSYM && ZULTRA_HIP_ENTROPY_SLOT % 4 == 0, "histogram rows and dword-aligned slots");
+extern "C" int zultra_hip_entropy_probe(int mode, uint32_t n, uint32_t grid, int pass, uint32_t ntasks, const uint32_t *hist_part, const uint8_t *in_force,
+                                        const uint16_t *tok_info, const uint32_t *tok_off, zultra_hip_entropy_rec_t *recs, uint8_t *slots, uint32_t *settled) {
+   int ndev = 0;
+   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return -1;
+   const bool build = mode == ZULTRA_HIP_ENTROPY_BUILD;
+   if (!n || !grid || grid > n || !recs || !slots) return -2;
+   if (build ? (!hist_part || !in_force || !ntasks || pass < 0 || pass > 3) : (mode != ZULTRA_HIP_ENTROPY_INIT || !tok_info || !tok_off)) return -2;
+
+   std::vector<zh_work_t> work(n);
+   std::vector<zh_sbstate_t> states(n);
+   memset(states.data(), 0, sizeof(zh_sbstate_t) * n);
+   for (uint32_t i = 0; i < n; i++) {
+      zh_work_t &w = work[i];
+      memset(&w, 0, sizeof(w));
+      w.size = 1024;   // (one KiB: a settled sub-block adds 3 - pass to either of the two counters)
+      w.out_off = (uint64_t)i * ZULTRA_HIP_ENTROPY_SLOT;
+      w.out_cap = ZULTRA_HIP_ENTROPY_SLOT;
+      w.index = i;
+      if (build) {
+         w.task_base = i * ntasks;
+         w.ntasks = ntasks;
+         memcpy(states[i].lit_len, in_force + (size_t)i * ZH_NSYM, ZH_NLIT);
+         memcpy(states[i].dist_len, in_force + (size_t)i * ZH_NSYM + ZH_NLIT, ZH_NDIST);
+         states[i].is_dynamic = 1;
+      }
+      else {
+         if (tok_off[i + 1] < tok_off[i]) return -2;
+         for (uint32_t t = tok_off[i]; t < tok_off[i + 1]; t++)
+            if (ZH_TOK_SYM(tok_info[t]) >= ZH_NLIT) return -2;   // (the tokenizer writes no other: the histogram in LDS has ZH_NLIT bins)
+         w.tok0 = tok_off[i];
+         w.tok1 = tok_off[i + 1];
+      }
+   }
+   uint32_t cnt[ZH_CNT_STRIDE];
+   memset(cnt, 0, sizeof(cnt));
+   cnt[ZH_CNT_NSUBS] = n;
+   if (zh_run_is_void(cnt)) return -3;
+
+   const size_t in_bytes = build ? (size_t)n * ntasks * ZH_NSYM * sizeof(uint32_t) : std::max<size_t>(tok_off[n], 1) * sizeof(uint16_t);
+   const size_t slot_bytes = (size_t)n * ZULTRA_HIP_ENTROPY_SLOT;
+   zh_work_t *d_work = NULL;
+   zh_sbstate_t *d_states = NULL;
+   uint32_t *d_cnt = NULL;
+   uint8_t *d_in = NULL, *d_slots = NULL;
+   int rc = 0;
+   if (hipMalloc((void **)&d_work, sizeof(zh_work_t) * n) != hipSuccess || hipMalloc((void **)&d_states, sizeof(zh_sbstate_t) * n) != hipSuccess ||
+       hipMalloc((void **)&d_cnt, sizeof(cnt)) != hipSuccess || hipMalloc((void **)&d_in, in_bytes) != hipSuccess || hipMalloc((void **)&d_slots, slot_bytes) != hipSuccess)
+      rc = -4;
+   if (!rc && (hipMemcpy(d_work, work.data(), sizeof(zh_work_t) * n, hipMemcpyHostToDevice) != hipSuccess ||
+               hipMemcpy(d_states, states.data(), sizeof(zh_sbstate_t) * n, hipMemcpyHostToDevice) != hipSuccess ||
+               hipMemcpy(d_cnt, cnt, sizeof(cnt), hipMemcpyHostToDevice) != hipSuccess ||
+               hipMemcpy(d_in, build ? (const void *)hist_part : (const void *)tok_info, build ? in_bytes : (size_t)tok_off[n] * sizeof(uint16_t), hipMemcpyHostToDevice) != hipSuccess ||
+               hipMemset(d_slots, 0, slot_bytes) != hipSuccess))
+      rc = -5;
+   if (!rc) {
+      if (build)
+         ZH_LAUNCH_BOTH(zh_sb_build, grid, n, false, 0, (const zh_work_t *)d_work, d_states, (const uint32_t *)d_in, d_slots, pass, d_cnt);
+      else
+         ZH_LAUNCH_BOTH(zh_sb_init, grid, n, false, 0, (const uint16_t *)d_in, (uint64_t)0, (const zh_work_t *)d_work, d_states, (const uint32_t *)d_cnt);
+      if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(recs, d_states, sizeof(zh_sbstate_t) * n, hipMemcpyDeviceToHost) != hipSuccess ||
+          hipMemcpy(slots, d_slots, slot_bytes, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(cnt, d_cnt, sizeof(cnt), hipMemcpyDeviceToHost) != hipSuccess)
+         rc = -6;
+   }
+   if (!rc && settled) {
+      settled[0] = cnt[ZH_CNT_SETTLED];
+      settled[1] = cnt[ZH_CNT_SETTLED_POS];
+   }
+   (void)hipFree(d_work);
+   (void)hipFree(d_states);
+   (void)hipFree(d_cnt);
+   (void)hipFree(d_in);
+   (void)hipFree(d_slots);
+   return rc;
 }
 
 // ---- PMC calibration probe ---------------------------------------------------------------------------------------
@@ -1292,17 +1385,6 @@ static bool zh_bets_settle(zultra_hip_ctx_t *c, int lanes) {
    if (again) c->bets.reruns++;
    return again;
 }
-
-// A kernel whose item count only the device knows (sub-blocks, tasks, segment waves of a run): the <false> form over `grid_` workgroups, one item each (what data
-// usually gives; surplus workgroups leave at once), then — unless the run bets that there is nothing (no_more_) — the <true> form, ZH_MORE_GRID workgroups striding over
-// what lies beyond grid_: nearly always nothing. (bound_: what the item count cannot exceed — a grid that covers it needs no second launch: a call on a few max-blocks is
-// a matter of launches)
-#define ZH_MORE_GRID 256u
-#define ZH_LAUNCH_BOTH(kernel_, grid_, bound_, no_more_, stream_, ...)                                                                                \
-   do {                                                                                                                                               \
-      ZH_LAUNCH(kernel_<false>, (grid_), 64, stream_, __VA_ARGS__, 0u);                                                                               \
-      if ((uint64_t)(grid_) < (uint64_t)(bound_) && !(no_more_)) ZH_LAUNCH(kernel_<true>, ZH_MORE_GRID, 64, stream_, __VA_ARGS__, (uint32_t)(grid_)); \
-   } while (0)
 
 static int zh_run_mark(zultra_hip_ctx_t *c, const zh_run_t &r, int e) {   // (timing marks: not in files mode, where they would be nodes of a captured graph)
    if (!r.files) ZH_CHECK(c, hipEventRecord(r.ev[e], r.st));
